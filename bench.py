@@ -8,7 +8,14 @@ ZF_UNET 224x224, bs=32 per GPU, bf16 compute, BCE+Dice, synthetic tiles resident
     --nnodes=1 --nproc-per-node N ... bench.py ...`, before anything touches the GPU) and forwards rank 0's line and
     the job's exit code; under a launcher that has already set RANK / WORLD_SIZE it just joins the job.
 
-Prints ONE JSON line on rank 0.  Besides the throughput it carries
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step`, `final_loss`); nothing else runs on the GPU or the host.
+
+    --dump-outputs DIR : after the timed steps, what the LAST timed step returned to its caller -- loss, logits, the
+                 parameters after the update and their gradients (--tiled: the probability mask) -- as DIR/<name>.npy in
+                 float32, 64 MB at most (larger arrays: a fixed, seeded sample of their elements).  The inputs are seeded, so
+                 two builds run with the same arguments can be compared output for output.
+    --full       : everything below besides the headline (off by default; it costs runs of its own):
   roofline     : the dominant kernel (the implicit-GEMM convolution) timed live with HIP events on its launch
                  stream during the timed region: achieved = algorithmic FLOPs / event time, against the dense
                  bf16 MFMA peak (2.5 PFLOP/s, MI355X_MICROARCH.md)
@@ -20,6 +27,8 @@ Prints ONE JSON line on rank 0.  Besides the throughput it carries
                  be compared.
   with_logging_syncs : the same step WITH the reference's per-batch logging (torch_train.py:195-210: loss .item(),
                  gradient abs-max, two metrics, each a host sync) -- SURVEY 8d / BASELINE.md section 2's second number.
+  host_enqueue_ms_per_step, kernels, roofline_hbm / step_bound (the committed PMC profile of this build), and for --tiled
+                 the model's own eval-forward rate it is measured against.
 """
 import argparse
 import json
@@ -172,6 +181,39 @@ def pmc_traffic(kernel, model='zf_unet'):
     return None if k is None else k['traffic_bytes_per_launch']
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_WHOLE_BYTES = 1 << 20      # arrays up to this size are always written whole
+
+
+def dump_outputs(out_dir, arrays, whole=(), seed=20240611):
+    """Write `arrays` ((name, tensor or ndarray) pairs) as out_dir/<name>.npy, float32 (float64 stays float64), 64 MB in
+    all at most: the arrays named in `whole` and those of up to 1 MB whole, the larger ones each reduced to the same fraction
+    of their elements, a sample drawn with a fixed seed from the array's size alone (flattened, sorted indices) -- the same
+    elements on every run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = []
+    for name, a in arrays:
+        if isinstance(a, torch.Tensor):
+            a = a.detach()
+            a = (a.double() if a.dtype == torch.float64 else a.float()).cpu().numpy()
+        a = np.asarray(a)
+        host.append((name, a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)))
+    keep = set(n for n, a in host if a.nbytes <= DUMP_WHOLE_BYTES or n in whole)
+    small = sum(a.nbytes for n, a in host if n in keep)
+    large = sum(a.nbytes for n, a in host if n not in keep)
+    headers = 256 * len(host)
+    frac = 1.0 if small + large + headers <= DUMP_BUDGET_BYTES else (DUMP_BUDGET_BYTES - small - headers) / float(large)
+    if frac <= 0:
+        raise ValueError('--dump-outputs: %d bytes of whole arrays alone exceed the budget' % small)
+    for name, a in host:
+        if name not in keep and frac < 1.0:
+            k = max(1, int(a.size * frac))
+            idx = np.sort(np.random.default_rng([seed, a.size]).choice(a.size, size=k, replace=False, shuffle=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
 def self_launch(n, argv):
     """--gpus N without a launcher: run the N ranks as CHILD processes (never exec: this process may not be replaced
     once anything has touched the GPU, and nothing here has) and return the job's exit code.  Rank 0's JSON line goes
@@ -234,18 +276,20 @@ def bench_tiled(args):
     rng = np.random.RandomState(1234)
     image = rng.randint(0, 256, size=(side, side, 3), dtype=np.uint8)
     norm = InputNorm(mean=(0.40, 0.42, 0.38), std=(0.19, 0.18, 0.18))       # (INRIA_MEAN / INRIA_STD stand-ins: lib/datasets/Inria.py:34)
-    # the model's own eval-forward rate at this batch (the ceiling predict_tiled is measured against)
-    x = torch.randn(B, 3, S, S, device=dev)
-    with torch.no_grad():
-        for _ in range(3):
-            model(x)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        nf = 30
-        for _ in range(nf):
-            model(x)
-        torch.cuda.synchronize()
-        fwd_ips = B * nf / (time.perf_counter() - t0)
+    # the model's own eval-forward rate at this batch (the ceiling predict_tiled is measured against): --full only
+    fwd_ips = None
+    if args.full:
+        x = torch.randn(B, 3, S, S, device=dev)
+        with torch.no_grad():
+            for _ in range(3):
+                model(x)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            nf = 30
+            for _ in range(nf):
+                model(x)
+            torch.cuda.synchronize()
+            fwd_ips = B * nf / (time.perf_counter() - t0)
     for _ in range(max(1, args.warmup)):
         predict_tiled(image, model, norm, S, B)
     if ws > 1:
@@ -264,6 +308,8 @@ def bench_tiled(args):
         dt = float(t.item())
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [('mask', mask)])
     items = timing['nitems']
     ms_img = dt / args.steps * 1e3
     tiles_s = items * args.steps / dt
@@ -281,8 +327,8 @@ def bench_tiled(args):
         'tiled': {'ms_per_image': round(ms_img, 2),
                   'gpu_ms_by_phase_last_image': {k: round(v, 2) for k, v in timing['ms'].items()},
                   'share_by_phase': {k: round(v / tot, 4) for k, v in timing['ms'].items()},
-                  'eval_forward_images_per_s_batch%d' % B: round(fwd_ips, 1),
-                  'fraction_of_eval_forward_ceiling': round(tiles_s / (fwd_ips * ws), 4),
+                  'eval_forward_images_per_s_batch%d' % B: None if fwd_ips is None else round(fwd_ips, 1),
+                  'fraction_of_eval_forward_ceiling': None if fwd_ips is None else round(tiles_s / (fwd_ips * ws), 4),
                   'note': ('gather of batch k+1 and the logits copy of batch k run on the launch stream between the forwards: '
                           'together < 2 %% of the image (share_by_phase), so no side stream is used; the merge is one launch '
                           'at the end over the logits of all %d items kept in HBM') % items,
@@ -323,9 +369,18 @@ def main():
     ap.add_argument('--image-size', type=int, default=5000, help='--tiled: side of the synthetic image')
     ap.add_argument('--dry-run', action='store_true',
                     help='join the job, count the ranks (all-reduce of ones), print n_gpus / ranks_seen and stop')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline: box probes, host-enqueue probe, logged steps, kernel timer / roofline, CPU baseline '
+                         '(each still off with its --no-* option), --tiled: the eval-forward ceiling')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step returned (loss, logits, updated parameters, gradients; --tiled: the mask) '
+                         'as DIR/<name>.npy, float32, 64 MB at most')
     args = ap.parse_args()
-    if args.timed_only:
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.timed_only or not args.full:
         args.no_cpu_baseline = args.no_kernel_timer = args.no_box = True
+    extras = args.full and not args.timed_only        # the host-enqueue probe and the logged steps
 
     if args.gpus > 1 and 'RANK' not in os.environ:
         # nothing above has touched the GPU (importing torch and parsing arguments do not)
@@ -395,14 +450,20 @@ def main():
         # flat gradient buffer itself when every .grad already aliases it
         flat_of().flat_g.zero_()
         out = model(x)
+        if keep_out:
+            last_out[0] = out
         loss = crit(out, y)
         (x.size(0) * loss).backward()
         opt.step()
         return loss
 
+    keep_out, last_out = args.dump_outputs is not None, [None]     # --dump-outputs: the logits of the last step
+
     def step():
         opt.zero_grad()
         out = model(x)
+        if keep_out:
+            last_out[0] = out
         loss = crit(out, y)
         (x.size(0) * loss).backward()
         opt.step()
@@ -450,6 +511,13 @@ def main():
         torch.distributed.barrier()
     dt = time.perf_counter() - t0
     ph.mark('timed_region')
+    if args.dump_outputs and rank == 0:
+        # before anything else runs: the --full probes below take further steps on the same buffers
+        dump = [('loss', loss), ('logits', last_out[0])]
+        dump += [('param.' + n, p) for n, p in model.named_parameters()]
+        dump += [('grad.' + n, p.grad) for n, p in model.named_parameters() if p.grad is not None]
+        dump_outputs(args.dump_outputs, dump, whole=('logits',))
+        ph.mark('dump_outputs')
     ranks_seen = 1
     if ws > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
@@ -462,7 +530,7 @@ def main():
     # host time to ENQUEUE one step (no synchronisation inside; the GPU is still busy with the first step when the last
     # one has been issued unless the host is the slower side) -- reported beside the step time, outside the timed region
     host_ms = None
-    if graph is None and not args.timed_only:
+    if graph is None and extras:
         # three steps from an idle GPU, best of three: a longer unsynchronised run can fill the HIP queue, and the host
         # then waits for the GPU inside a launch call (seen as 2.1-2.3 ms "enqueue" time on some boxes)
         for _ in range(3):
@@ -479,7 +547,7 @@ def main():
     # abs-max ('train/grad/global_abs_max': one fused reduction over the flat gradient buffer here, a per-parameter loop of
     # .abs().max().cpu().item() there), and the two metrics -- every one a host sync.  SURVEY 8d / BASELINE.md section 2.
     logging_ms = None
-    if graph is None and ws == 1 and not args.timed_only:
+    if graph is None and ws == 1 and extras:
         import torch_train as tt
         mets = tt.default_metrics()
 
@@ -586,21 +654,22 @@ def main():
                               'tflops': round(v[2] / (v[1] * 1e-3) / 1e12, 2)} for k, v in summ.items()}
     # second roofline figure: HBM.  bytes_per_step = measured HBM traffic of one step (PMC passes of this same command,
     # stamped with the kernel digest: tools/pmc_traffic.py); achieved = those bytes / the step time of THIS run.
-    prof = pmc_profile(args.model)
-    step_bytes = prof.get('bytes_per_step') if prof else None
-    algo_bytes = ALGO_MB_PER_IMAGE_224 * 1e6 * B * (S / 224.0) ** 2 if args.model == 'zf_unet' else None
-    hbm = {'peak': PEAK_HBM_TBS, 'unit': 'TB/s', 'bytes_per_step': step_bytes,
-           'algorithmic_bytes_per_step': None if algo_bytes is None else round(algo_bytes)}
-    if step_bytes:
-        hbm['achieved'] = round(step_bytes / (ms * 1e-3) / 1e12, 3)
-        hbm['frac'] = round(hbm['achieved'] / PEAK_HBM_TBS, 4)
-        if algo_bytes:
-            hbm['traffic_over_algorithmic'] = round(step_bytes / algo_bytes, 3)
-    out['roofline_hbm'] = hbm
-    if hbm.get('frac') is not None:
-        # the step sits under BOTH roofs at once (`roofline.frac` is a fraction of the MFMA peak, `roofline_hbm.frac` of the
-        # HBM peak); this names the one the whole step is closer to
-        out['step_bound'] = 'hbm' if hbm['frac'] > out['step_mfma_frac'] else 'mfma'
+    if args.full:
+        prof = pmc_profile(args.model)
+        step_bytes = prof.get('bytes_per_step') if prof else None
+        algo_bytes = ALGO_MB_PER_IMAGE_224 * 1e6 * B * (S / 224.0) ** 2 if args.model == 'zf_unet' else None
+        hbm = {'peak': PEAK_HBM_TBS, 'unit': 'TB/s', 'bytes_per_step': step_bytes,
+               'algorithmic_bytes_per_step': None if algo_bytes is None else round(algo_bytes)}
+        if step_bytes:
+            hbm['achieved'] = round(step_bytes / (ms * 1e-3) / 1e12, 3)
+            hbm['frac'] = round(hbm['achieved'] / PEAK_HBM_TBS, 4)
+            if algo_bytes:
+                hbm['traffic_over_algorithmic'] = round(step_bytes / algo_bytes, 3)
+        out['roofline_hbm'] = hbm
+        if hbm.get('frac') is not None:
+            # the step sits under BOTH roofs at once (`roofline.frac` is a fraction of the MFMA peak, `roofline_hbm.frac` of the
+            # HBM peak); this names the one the whole step is closer to
+            out['step_bound'] = 'hbm' if hbm['frac'] > out['step_mfma_frac'] else 'mfma'
     if ws == 1 and not args.no_cpu_baseline:
         out['cpu_baseline'] = cpu_baseline()
         ph.mark('cpu_baseline')

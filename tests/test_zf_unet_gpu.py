@@ -562,7 +562,7 @@ def test_bench_runs_over_rccl_single_rank():
     env = dict(os.environ, SEGNB_DP_FORCE='1', HSA_ENABLE_IPC_MODE_LEGACY='0')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr',
            '127.0.0.1', '--master-port', '29731', os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3',
-           '--warmup', '2', '--batch', '4', '--no-cpu-baseline']
+           '--warmup', '2', '--batch', '4', '--no-cpu-baseline', '--full']
     losses = {}
     # the launch lists replayed from C (cut at the gradient-ready hooks) / the eager launcher / the SGD update of each bucket
     # behind its all-reduce (DataParallel.fuse_optimizer)
@@ -590,7 +590,8 @@ def test_bench_executor_model_over_rccl_single_rank():
     env = dict(os.environ, SEGNB_DP_FORCE='1', HSA_ENABLE_IPC_MODE_LEGACY='0')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr',
            '127.0.0.1', '--master-port', '29741', os.path.join(root, 'bench.py'), '--gpus', '1', '--model', 'fcdensenet67',
-           '--batch', '2', '--size', '64', '--steps', '4', '--warmup', '4', '--no-cpu-baseline', '--no-kernel-timer']
+           '--batch', '2', '--size', '64', '--steps', '4', '--warmup', '4', '--no-cpu-baseline', '--no-kernel-timer',
+           '--full']
     losses = {}
     for cplan in ('1', '0'):
         out = subprocess.run(cmd, env=dict(env, SEGNB_CPLAN=cplan), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)

@@ -9,15 +9,15 @@ R=$(pwd)
 O=$R/gpurun_out
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err
-python3 $R/bench.py --size 512 --batch 16 --no-cpu-baseline > $O/${TAG}_bench_512.json 2>/dev/null
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_prof_stats -- python3 $R/bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-box > $O/${TAG}_prof_stats.log 2>&1
+python3 $R/bench.py --full > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err
+python3 $R/bench.py --full --size 512 --batch 16 --no-cpu-baseline > $O/${TAG}_bench_512.json 2>/dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_prof_stats -- python3 $R/bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-box > $O/${TAG}_prof_stats.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/${TAG}_pmc_fetch -- python3 $R/bench.py --steps 6 --warmup 2 --timed-only > $O/${TAG}_pmc_fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/${TAG}_pmc_write -- python3 $R/bench.py --steps 6 --warmup 2 --timed-only > $O/${TAG}_pmc_write.log 2>&1
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA --kernel-trace --output-format csv -d $O/${TAG}_pmc_sq1 -- python3 $R/bench.py --steps 4 --warmup 2 --timed-only > $O/${TAG}_pmc_sq1.log 2>&1
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR --kernel-trace --output-format csv -d $O/${TAG}_pmc_sq2 -- python3 $R/bench.py --steps 4 --warmup 2 --timed-only > $O/${TAG}_pmc_sq2.log 2>&1
 for m in linknet34 fcdensenet103 unet16; do
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_prof_$m -- python3 $R/bench.py --model $m --steps 10 --warmup 5 --no-cpu-baseline --no-kernel-timer --no-box > $O/${TAG}_prof_$m.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_prof_$m -- python3 $R/bench.py --full --model $m --steps 10 --warmup 5 --no-cpu-baseline --no-kernel-timer --no-box > $O/${TAG}_prof_$m.log 2>&1
   find $O/${TAG}_prof_$m -name '*kernel_stats.csv' | head -1 | xargs -I{} cp {} $O/${TAG}_${m}_kernel_stats.csv
   rm -rf $O/${TAG}_prof_$m
 done
@@ -36,7 +36,7 @@ find $O/${TAG}_prof_stats -name '*kernel_stats.csv' | head -1 | xargs -I{} cp {}
 python3 tools/layer_bench.py > $O/${TAG}_layers.txt 2>&1
 python3 tools/prologue_gap.py > $O/${TAG}_prologue_gap.txt 2>&1
 python3 tools/coresidency_probe.py > $O/${TAG}_coresidency.txt 2>&1
-python3 bench.py --model unet16 --tiled > $O/${TAG}_bench_tiled.json 2> $O/${TAG}_bench_tiled.log
+python3 bench.py --full --model unet16 --tiled > $O/${TAG}_bench_tiled.json 2> $O/${TAG}_bench_tiled.log
 python3 tools/bn_bench.py > $O/${TAG}_bn_passes.txt 2>&1
 python3 tools/step_timeline.py > $O/${TAG}_timeline.txt 2>&1
 python3 tools/upcat_bench.py > $O/${TAG}_upcat_layers.txt 2>&1
@@ -64,7 +64,7 @@ for m in linknet34 fcdensenet103 unet16; do
   rm -rf $O/${TAG}_trace_$m
 done
 # the same step replayed from ONE HIP graph (where does the two-branch overlap go?)
-python3 bench.py --graph on --no-cpu-baseline --no-kernel-timer > $O/${TAG}_bench_graph.json 2>/dev/null
+python3 bench.py --full --graph on --no-cpu-baseline --no-kernel-timer > $O/${TAG}_bench_graph.json 2>/dev/null
 (cd /tmp && rocprofv3 --kernel-trace --output-format csv -d $O/${TAG}_trace_graph -- python3 $R/bench.py --graph on --steps 12 --warmup 3 --timed-only > $O/${TAG}_trace_graph.log 2>&1)
 python3 tools/trace_step.py $O/${TAG}_trace_graph 4 list > $O/${TAG}_step_trace_graph.txt 2>&1
 rm -rf $O/${TAG}_trace_graph
@@ -74,6 +74,6 @@ python3 tools/model_bench.py --steps 10 > $O/${TAG}_model_bench.txt 2>&1
 python3 tools/conv_sites.py --model linknet34 --top 30 > $O/${TAG}_conv_sites_linknet34.txt 2>&1
 python3 tools/conv_sites.py --model fcdensenet103 --top 30 > $O/${TAG}_conv_sites_fcdensenet103.txt 2>&1
 python3 tools/conv_sites.py --model unet16 --size 1024 --batch 4 --top 30 > $O/${TAG}_conv_sites_unet16.txt 2>&1
-for m in linknet34 fcdensenet103 unet16; do python3 bench.py --model $m --no-cpu-baseline >> $O/${TAG}_bench_models.json 2>/dev/null; done
+for m in linknet34 fcdensenet103 unet16; do python3 bench.py --full --model $m --no-cpu-baseline >> $O/${TAG}_bench_models.json 2>/dev/null; done
 rm -rf $O/${TAG}_pmc_fetch $O/${TAG}_pmc_write $O/${TAG}_pmc_sq1 $O/${TAG}_pmc_sq2 $O/${TAG}_prof_stats
 echo evidence done
