@@ -127,9 +127,21 @@ int segnb_knob_rw_store_waves();  // 2 or 4 store waves in conv_fprop_rw_kernel
 int segnb_knob_bnreduce_fused();  // 1: segnb_conv_fprop_bnreduce_ok may say yes
 int segnb_knob_fprop_deepk();     // 1: conv_fprop_deepk_kernel serves the shapes it applies to
 int segnb_knob_fprop_thin();      // 1: conv_thin_kernel (fprop_thin.hip) serves <= 16 -> >= 48 channel stride-1 3x3 launches
-// 1 = launched, 0 = not served (fprop_thin.hip); bn: the BatchNorm-backward reduction epilogue of segnb_conv_fprop_bnreduce or NULL
-int segnb_fprop_thin_try(const segnb_conv_geom* g, const void* in, const void* wpacked, void* out, hipStream_t stream,
-                         const segnb_bn_reduce_epilogue* bn);
+// The segnb_*_try kernel selectors below report two things that never share a value: their int return is the error status
+// alone -- 0, or exactly what the calling entry point returns (hipError_t > 0, SEGNB_E_* < 0) -- and *did says what they did.
+enum segnb_try_outcome {
+    SEGNB_TRY_DECLINED = 0,     // not this kernel's geometry / operands: nothing launched, the caller tries the next one
+    SEGNB_TRY_LAUNCHED,         // launched
+    SEGNB_TRY_DELIVERED,        // launched, and the kernel wrote the armed segnb_wgrad_target itself (nothing left to deliver)
+};
+// the tail of a try whose launch helper returned rc (0 or an error): launched unless it failed
+inline int segnb_try_launched(segnb_try_outcome* did, int rc) {
+    if (rc == 0) *did = SEGNB_TRY_LAUNCHED;
+    return rc;
+}
+// fprop_thin.hip; bn: the BatchNorm-backward reduction epilogue of segnb_conv_fprop_bnreduce or NULL
+int segnb_fprop_thin_try(segnb_try_outcome* did, const segnb_conv_geom* g, const void* in, const void* wpacked, void* out,
+                         hipStream_t stream, const segnb_bn_reduce_epilogue* bn);
 int segnb_fprop_thin_ok(const segnb_conv_geom* g);
 int segnb_knob_fprop_upd();       // 1: 4x4 / stride-2 gathers (ntaps 16, in_step 2) on the plane-gather form of conv_fprop_ws_kernel
 int segnb_knob_fprop_drop();      // 1: segnb_conv_fprop_drop_ok may say yes
@@ -147,29 +159,28 @@ int segnb_knob_fprop_roll();     // 0: off, 1: conv_roll_kernel with 16-column s
 int segnb_knob_wg_cu_pct();      // segnb_tune "wg_cu_pct": 0 = default share of the CUs for the 64x64-tile weight gradients
 int segnb_knob_conv_cus();        // CUs the persistent fprop / dgrad kernels size their grids for (segnb_tune "conv_cu_pct")
 int segnb_fprop_dma_read_stamps(unsigned long long* host_dst);
-// fast path of segnb_conv_wgrad (wgrad_s1.hip): 1 = handled, 0 = not applicable, else error
+// fast path of segnb_conv_fprop (fprop_s1.hip)
 // (drop / ld_drop / stats_ld: the Dropout2d multipliers and the statistics row stride of segnb_conv_fprop_drop; NULL / 0 / 0: off)
-int segnb_fprop_s1_try(const segnb_conv_geom* g, const void* in, const void* wpacked, const float* bias, int bias_n,
-                       void* out, double* stats, hipStream_t stream, const float* drop = nullptr, int ld_drop = 0,
-                       int stats_ld = 0);
-// direct-to-LDS pipeline for Ci % 64 == 0 (fprop_dma.hip): 1 = handled, 0 = not applicable, else error
-int segnb_fprop_dma_try(const segnb_conv_geom* g, const void* in, unsigned in_bytes, const void* wpacked,
+int segnb_fprop_s1_try(segnb_try_outcome* did, const segnb_conv_geom* g, const void* in, const void* wpacked, const float* bias, int bias_n,
+                       void* out, double* stats, hipStream_t stream, const float* drop = nullptr, int ld_drop = 0, int stats_ld = 0);
+// direct-to-LDS pipeline for Ci % 64 == 0 (fprop_dma.hip)
+int segnb_fprop_dma_try(segnb_try_outcome* did, const segnb_conv_geom* g, const void* in, unsigned in_bytes, const void* wpacked,
                         unsigned w_bytes, const float* bias, int bias_n, void* out, double* stats,
                         hipStream_t stream, const segnb_act_epilogue* ep = nullptr, const segnb_upcat_src* uc = nullptr,
                         const segnb_bn_reduce_epilogue* bn = nullptr);
 // resident-weights pipeline for the thin layers, Ci <= 96 and Co <= 96 (fprop_rw.hip)
-int segnb_fprop_rw_try(const segnb_conv_geom* g, const void* in, unsigned in_bytes, const void* wpacked,
+int segnb_fprop_rw_try(segnb_try_outcome* did, const segnb_conv_geom* g, const void* in, unsigned in_bytes, const void* wpacked,
                        unsigned w_bytes, const float* bias, int bias_n, void* out, double* stats,
                        hipStream_t stream, const segnb_bn_reduce_epilogue* bn = nullptr,
                        const segnb_act_epilogue* ep = nullptr, const segnb_upcat_src* uc = nullptr,
                        const segnb_upcat_src* upsum = nullptr);
 // rolling-window kernel for the thin layers, weights in registers, no block-level synchronisation (fprop_roll.hip)
-int segnb_fprop_roll_try(const segnb_conv_geom* g, const void* in, unsigned in_bytes, const void* wpacked, unsigned w_bytes,
-                         const float* bias, int bias_n, void* out, double* stats, hipStream_t stream,
+int segnb_fprop_roll_try(segnb_try_outcome* did, const segnb_conv_geom* g, const void* in, unsigned in_bytes, const void* wpacked,
+                         unsigned w_bytes, const float* bias, int bias_n, void* out, double* stats, hipStream_t stream,
                          const segnb_bn_reduce_epilogue* bn = nullptr, const segnb_operand_tf* tf = nullptr,
                          const segnb_upcat_src* uc = nullptr);
 // first layer: 8-channel (3 padded) input, <= 32 output channels (fprop_c8.hip)
-int segnb_fprop_c8_try(const segnb_conv_geom* g, const void* in, const void* wpacked, const float* bias, int bias_n,
+int segnb_fprop_c8_try(segnb_try_outcome* did, const segnb_conv_geom* g, const void* in, const void* wpacked, const float* bias, int bias_n,
                        void* out, double* stats, hipStream_t stream, const segnb_act_epilogue* ep = nullptr);
 // bna (optional): the dy operand is not in memory -- it is the BatchNorm-backward apply of the layer, recomputed while
 // the tile is staged: dy = round(a (round(g act'(z)) - c1 - yhat c2)) from the incoming gradient g and the pre-BatchNorm
@@ -186,9 +197,9 @@ struct segnb_wgrad_bnapply {
     float slope;
 };
 // tgt: the armed segnb_wgrad_target or NULL.  With a target a single-slab launch writes the parameter's gradient from its
-// accumulators (returns 2 instead of 1: nothing left to do); launches with several slabs leave them unreduced for
+// accumulators (*did = SEGNB_TRY_DELIVERED: nothing left to do); launches with several slabs leave them unreduced for
 // segnb_wgrad_to_param
-int segnb_wgrad_s1_try(const segnb_conv_geom* g, const void* in, const void* dout, float* dwp, int nslab,
+int segnb_wgrad_s1_try(segnb_try_outcome* did, const segnb_conv_geom* g, const void* in, const void* dout, float* dwp, int nslab,
                        hipStream_t stream, bool partial, const segnb_wgrad_bnapply* bna = nullptr,
                        const segnb_upcat_src* uc = nullptr, const segnb_wgrad_target* tgt = nullptr);      // partial: leave the nslab slabs unreduced
 // runtime.hip: the target armed by segnb_wgrad_target_arm on this thread (disarmed by the call), or NULL
@@ -201,21 +212,26 @@ int segnb_wgrad_s1_slabs(const segnb_conv_geom* g);
 void segnb_slab_reduce(float* dwp, long long total, int nslab, hipStream_t stream);
 // rolling-window weight gradient of the thin layers (wgrad_roll.hip); tfx / tfd: operands recomputed on load (or NULL)
 bool segnb_wgrad_roll_applies(const segnb_conv_geom* g);
-int segnb_wgrad_roll_try(const segnb_conv_geom* g, const void* in, const void* dout, float* dwp, int nslab, hipStream_t stream,
-                         bool partial, const segnb_operand_tf* tfx = nullptr, const segnb_operand_tf* tfd = nullptr);
+int segnb_wgrad_roll_try(segnb_try_outcome* did, const segnb_conv_geom* g, const void* in, const void* dout, float* dwp, int nslab,
+                         hipStream_t stream, bool partial, const segnb_operand_tf* tfx = nullptr, const segnb_operand_tf* tfd = nullptr);
 int segnb_knob_wgrad_roll();
 // the first layer (8 padded input channels): conv_wgrad_c8roll_kernel; bna: dy recomputed from (g, y), dout ignored
 bool segnb_wgrad_c8roll_applies(const segnb_conv_geom* g);
-int segnb_wgrad_c8roll_try(const segnb_conv_geom* g, const void* in, const void* dout, float* dwp, int nslab, hipStream_t stream,
-                           bool partial, const segnb_wgrad_bnapply* bna = nullptr);
+int segnb_wgrad_c8roll_try(segnb_try_outcome* did, const segnb_conv_geom* g, const void* in, const void* dout, float* dwp, int nslab,
+                           hipStream_t stream, bool partial, const segnb_wgrad_bnapply* bna = nullptr);
 int segnb_knob_wgrad_c8roll();
 // strided / wide-window tile kernel (wgrad_s1.hip: conv_wgrad_sx_kernel): same protocol
-int segnb_wgrad_sx_try(const segnb_conv_geom* g, const void* in, const void* dout, float* dwp, int nslab, hipStream_t stream,
-                       bool partial);
+int segnb_wgrad_sx_try(segnb_try_outcome* did, const segnb_conv_geom* g, const void* in, const void* dout, float* dwp, int nslab,
+                       hipStream_t stream, bool partial);
 int segnb_wgrad_sx_slabs(const segnb_conv_geom* g);
+// the four output phases of an Upsample(x2) -> conv3x3 / ConvTranspose2d(4, 2, 1) on the low-resolution tensor (fprop_dma.hip)
+int segnb_fprop_upf_try(segnb_try_outcome* did, int N, int H, int W, int Ci, int ld_in, const void* in, unsigned in_bytes,
+                        const void* wpacked, unsigned w_bytes, int Co, int CoW, void* out, int ld_out, double* stats,
+                        hipStream_t stream, const float* bias = nullptr, int bias_n = 0, int no_prev = 0, int ep_act = -1,
+                        float ep_slope = 0.f);
 // forward / data gradient of strided, transposed-phase, 2x2, 1x1 and 16-channel-multiple convolutions on halo tiles (fprop_sx.hip)
-int segnb_fprop_sx_try(const segnb_conv_geom* g, const void* in, const void* wpacked, const float* bias, int bias_n, void* out,
-                       double* stats, hipStream_t stream);
+int segnb_fprop_sx_try(segnb_try_outcome* did, const segnb_conv_geom* g, const void* in, const void* wpacked, const float* bias,
+                       int bias_n, void* out, double* stats, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------------
 // element helpers: 8 channels per thread ("chunk8"), fp32 math

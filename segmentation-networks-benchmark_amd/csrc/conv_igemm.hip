@@ -1717,38 +1717,39 @@ static int conv_fprop_impl(const segnb_conv_geom* g, int dtype, const void* in, 
     a.stats = stats;
     a.M = g->N * g->QH * g->QW;
     a.Ktot = g->ntaps * g->Ci;
-    int rc;
+    int rc = 0;
     if (dtype == SEGNB_BF16) {
         // stride-1 3x3: image halo tile staged once in LDS, all taps from shifted rows (fprop_s1.hip)
         static const bool general_env = getenv("SEGNB_FPROP_GENERAL") != nullptr;   // A/B testing only
         const bool general_only = general_env || bn != nullptr || ap != nullptr;
+        const hipStream_t st = (hipStream_t)stream;
+        segnb_try_outcome did = SEGNB_TRY_DECLINED;       // (until a kernel below takes the launch)
         // (the affine + activation epilogue lives in the c8, rw, ws and general kernels: s1 is skipped for it)
-        rc = general_only ? 0 : segnb_fprop_c8_try(g, in, wpacked, bias, bias_n, out, stats, (hipStream_t)stream, ep);
-        if (rc == 0 && !general_env && ap == nullptr && bn_mode == 0 && out != nullptr && ep == nullptr && stats == nullptr && bias == nullptr)
-            rc = segnb_fprop_thin_try(g, in, wpacked, out, (hipStream_t)stream, bn);      // (thin input, wide output; bn or plain)
-        if (rc == 0 && !general_only && ep == nullptr)
-            rc = segnb_fprop_roll_try(g, in, a.in_bytes, wpacked, a.w_bytes, bias, bias_n, out, stats, (hipStream_t)stream);
-        if (rc == 0 && !general_only)
-            rc = segnb_fprop_rw_try(g, in, a.in_bytes, wpacked, a.w_bytes, bias, bias_n, out, stats,
-                                    (hipStream_t)stream, nullptr, ep);
-        if (rc == 0 && !general_only)
-            rc = segnb_fprop_dma_try(g, in, a.in_bytes, wpacked, a.w_bytes, bias, bias_n, out, stats,
-                                     (hipStream_t)stream, ep);
-        if (rc == 0 && !general_only && fprop_deepk_applies(a)) {
+        if (!general_only)
+            rc = segnb_fprop_c8_try(&did, g, in, wpacked, bias, bias_n, out, stats, st, ep);
+        if (!rc && !did && !general_env && ap == nullptr && bn_mode == 0 && out != nullptr && ep == nullptr && stats == nullptr &&
+            bias == nullptr)
+            rc = segnb_fprop_thin_try(&did, g, in, wpacked, out, st, bn);      // (thin input, wide output; bn or plain)
+        if (!rc && !did && !general_only && ep == nullptr)
+            rc = segnb_fprop_roll_try(&did, g, in, a.in_bytes, wpacked, a.w_bytes, bias, bias_n, out, stats, st);
+        if (!rc && !did && !general_only)
+            rc = segnb_fprop_rw_try(&did, g, in, a.in_bytes, wpacked, a.w_bytes, bias, bias_n, out, stats, st, nullptr, ep);
+        if (!rc && !did && !general_only)
+            rc = segnb_fprop_dma_try(&did, g, in, a.in_bytes, wpacked, a.w_bytes, bias, bias_n, out, stats, st, ep);
+        if (!rc && !did && !general_only && fprop_deepk_applies(a)) {
             // few pixels x few channels x deep K (before the halo-tile kernel below, whose blocks also walk K serially)
-            hipLaunchKernelGGL(conv_fprop_deepk_kernel, dim3(ceil_div(a.M, 32), ceil_div(g->Co, 32)), dim3(DK_WAVES * 64), 0,
-                               (hipStream_t)stream, a);
-            rc = 1;
+            hipLaunchKernelGGL(conv_fprop_deepk_kernel, dim3(ceil_div(a.M, 32), ceil_div(g->Co, 32)), dim3(DK_WAVES * 64), 0, st, a);
+            did = SEGNB_TRY_LAUNCHED;
         }
-        if (rc == 0 && !general_only && ep == nullptr)
-            rc = segnb_fprop_s1_try(g, in, wpacked, bias, bias_n, out, stats, (hipStream_t)stream);
-        if (rc == 0 && !general_only && ep == nullptr)
-            rc = segnb_fprop_sx_try(g, in, wpacked, bias, bias_n, out, stats, (hipStream_t)stream);
-        if (rc == 1) {
+        if (!rc && !did && !general_only && ep == nullptr)
+            rc = segnb_fprop_s1_try(&did, g, in, wpacked, bias, bias_n, out, stats, st);
+        if (!rc && !did && !general_only && ep == nullptr)
+            rc = segnb_fprop_sx_try(&did, g, in, wpacked, bias, bias_n, out, stats, st);
+        if (rc) return rc;
+        if (did) {
             SEGNB_LAUNCH_CHECK();
             return 0;
         }
-        if (rc != 0) return rc;
         a.ksteps = ceil_div(a.Ktot, 64);
         rc = dispatch_fprop<bf16_t>(a, (hipStream_t)stream);
     } else if (dtype == SEGNB_F32) {
@@ -1825,19 +1826,18 @@ extern "C" int segnb_conv_fprop_drop(const segnb_conv_geom* g, int dtype, const 
         SEGNB_LAUNCH_CHECK();
         return 0;
     }
-    const int rc = segnb_fprop_s1_try(g, in, wpacked, bias, bias_n, out, stats, (hipStream_t)stream, dropmul, ld_drop, stats_ld);
-    if (rc != 1) {
-        segnb_set_error("segnb_conv_fprop_drop: the kernel refused the launch (%d)", rc);
-        return rc > 1 ? rc : SEGNB_E_BADARG;
+    segnb_try_outcome did;
+    if (int rc = segnb_fprop_s1_try(&did, g, in, wpacked, bias, bias_n, out, stats, (hipStream_t)stream, dropmul, ld_drop, stats_ld))
+        return rc;
+    if (did == SEGNB_TRY_DECLINED) {
+        segnb_set_error("segnb_conv_fprop_drop: the kernel refused the launch");
+        return SEGNB_E_BADARG;
     }
     SEGNB_LAUNCH_CHECK();
     return 0;
 }
 
 // ---- forward of an Upsample(x2) -> conv3x3 segment on the low-resolution tensor, accumulating (fprop_dma.hip, WsCfg UP_ = 2)
-int segnb_fprop_upf_try(int N, int H, int W, int Ci, int ld_in, const void* in, unsigned in_bytes, const void* wpacked,
-                        unsigned w_bytes, int Co, int CoW, void* out, int ld_out, double* stats, hipStream_t stream,
-                        const float* bias = nullptr, int bias_n = 0, int no_prev = 0, int ep_act = -1, float ep_slope = 0.f);
 
 extern "C" int segnb_upconv_fprop_acc_ok(int N, int H, int W, int Ci, int Co, int ld_out, int dtype) {
     if (dtype != SEGNB_BF16 || getenv("SEGNB_FPROP_GENERAL") != nullptr || !segnb_knob_fprop_dma() || !segnb_knob_fprop_upd()) return 0;
@@ -1853,17 +1853,16 @@ extern "C" int segnb_upconv_fprop_acc(int dtype, int N, int H, int W, int Ci, in
     SEGNB_CHECK_ARG(CoW >= Co && ld_in >= Ci && ld_out >= Co, "bad strides");
     const long long inb = (((long long)N * H * W - 1) * ld_in + Ci) * 2, wb = 4ll * CoW * 4 * Ci * 2;
     SEGNB_CHECK_ARG(inb < (1ll << 31) && wb < (1ll << 31), "tensor larger than 2 GiB (32-bit buffer offsets)");
-    const int rc = segnb_fprop_upf_try(N, H, W, Ci, ld_in, in, (unsigned)inb, wpacked, (unsigned)wb, Co, CoW, out, ld_out, stats,
-                                       (hipStream_t)stream);
-    if (rc == 1) {
-        SEGNB_LAUNCH_CHECK();
-        return 0;
-    }
-    if (rc == 0) {
+    segnb_try_outcome did;
+    if (int rc = segnb_fprop_upf_try(&did, N, H, W, Ci, ld_in, in, (unsigned)inb, wpacked, (unsigned)wb, Co, CoW, out, ld_out, stats,
+                                     (hipStream_t)stream))
+        return rc;
+    if (did == SEGNB_TRY_DECLINED) {
         segnb_set_error("segnb_upconv_fprop_acc: no kernel for this shape");
         return SEGNB_E_UNSUPPORTED;
     }
-    return rc;
+    SEGNB_LAUNCH_CHECK();
+    return 0;
 }
 
 // ---- forward of a ConvTranspose2d(4, 2, 1) (unet16.py:30) on the same kernel: the four output phases in one launch, nothing to
@@ -1883,17 +1882,16 @@ extern "C" int segnb_upconv_fprop(int dtype, int N, int H, int W, int Ci, int ld
     SEGNB_CHECK_ARG(CoW >= Co && ld_in >= Ci && ld_out >= Co && bias_n >= 0 && bias_n <= Co, "bad strides");
     const long long inb = (((long long)N * H * W - 1) * ld_in + Ci) * 2, wb = 4ll * CoW * 4 * Ci * 2;
     SEGNB_CHECK_ARG(inb < (1ll << 31) && wb < (1ll << 31), "tensor larger than 2 GiB (32-bit buffer offsets)");
-    const int rc = segnb_fprop_upf_try(N, H, W, Ci, ld_in, in, (unsigned)inb, wpacked, (unsigned)wb, Co, CoW, out, ld_out, stats,
-                                       (hipStream_t)stream, bias_n > 0 ? bias : nullptr, bias_n, 1);
-    if (rc == 1) {
-        SEGNB_LAUNCH_CHECK();
-        return 0;
-    }
-    if (rc == 0) {
+    segnb_try_outcome did;
+    if (int rc = segnb_fprop_upf_try(&did, N, H, W, Ci, ld_in, in, (unsigned)inb, wpacked, (unsigned)wb, Co, CoW, out, ld_out, stats,
+                                     (hipStream_t)stream, bias_n > 0 ? bias : nullptr, bias_n, 1))
+        return rc;
+    if (did == SEGNB_TRY_DECLINED) {
         segnb_set_error("segnb_upconv_fprop: no kernel for this shape");
         return SEGNB_E_UNSUPPORTED;
     }
-    return rc;
+    SEGNB_LAUNCH_CHECK();
+    return 0;
 }
 
 // the same with the activation of unet16.py:38-40 (ConvTranspose2d -> ReLU) in the accumulator staging: no pass over the output
@@ -1909,17 +1907,16 @@ extern "C" int segnb_upconv_fprop_act(int dtype, int N, int H, int W, int Ci, in
     SEGNB_CHECK_ARG(CoW >= Co && ld_in >= Ci && ld_out >= Co && bias_n >= 0 && bias_n <= Co, "bad strides");
     const long long inb = (((long long)N * H * W - 1) * ld_in + Ci) * 2, wb = 4ll * CoW * 4 * Ci * 2;
     SEGNB_CHECK_ARG(inb < (1ll << 31) && wb < (1ll << 31), "tensor larger than 2 GiB (32-bit buffer offsets)");
-    const int rc = segnb_fprop_upf_try(N, H, W, Ci, ld_in, in, (unsigned)inb, wpacked, (unsigned)wb, Co, CoW, out, ld_out, nullptr,
-                                       (hipStream_t)stream, bias_n > 0 ? bias : nullptr, bias_n, 1, ep->act, ep->slope);
-    if (rc == 1) {
-        SEGNB_LAUNCH_CHECK();
-        return 0;
-    }
-    if (rc == 0) {
+    segnb_try_outcome did;
+    if (int rc = segnb_fprop_upf_try(&did, N, H, W, Ci, ld_in, in, (unsigned)inb, wpacked, (unsigned)wb, Co, CoW, out, ld_out, nullptr,
+                                     (hipStream_t)stream, bias_n > 0 ? bias : nullptr, bias_n, 1, ep->act, ep->slope))
+        return rc;
+    if (did == SEGNB_TRY_DECLINED) {
         segnb_set_error("segnb_upconv_fprop_act: no kernel for this shape");
         return SEGNB_E_UNSUPPORTED;
     }
-    return rc;
+    SEGNB_LAUNCH_CHECK();
+    return 0;
 }
 
 // ---- virtual concat: cat([Upsample x2(u), skip]) read from the two tensors (include/segnb_hip.h)
@@ -1946,23 +1943,22 @@ extern "C" int segnb_conv_fprop_upcat(const segnb_conv_geom* g, int dtype, const
     const long long inb = (((long long)g->N * g->Hi * g->Wi - 1) * g->ld_in + (g->Ci - src->Cu)) * 2;
     const long long wb = (long long)g->Co * g->ntaps * g->Ci * 2;
     SEGNB_CHECK_ARG(inb < (1ll << 31) && wb < (1ll << 31), "tensor larger than 2 GiB (32-bit buffer offsets)");
-    int rc = segnb_fprop_roll_try(g, in, (unsigned)inb, wpacked, (unsigned)wb, bias, bias_n, out, stats, (hipStream_t)stream,
+    segnb_try_outcome did;
+    int rc = segnb_fprop_roll_try(&did, g, in, (unsigned)inb, wpacked, (unsigned)wb, bias, bias_n, out, stats, (hipStream_t)stream,
                                   nullptr, nullptr, src);
-    if (rc == 0)
-        rc = segnb_fprop_rw_try(g, in, (unsigned)inb, wpacked, (unsigned)wb, bias, bias_n, out, stats, (hipStream_t)stream,
+    if (!rc && !did)
+        rc = segnb_fprop_rw_try(&did, g, in, (unsigned)inb, wpacked, (unsigned)wb, bias, bias_n, out, stats, (hipStream_t)stream,
                                 nullptr, nullptr, src);
-    if (rc == 0)
-        rc = segnb_fprop_dma_try(g, in, (unsigned)inb, wpacked, (unsigned)wb, bias, bias_n, out, stats, (hipStream_t)stream,
+    if (!rc && !did)
+        rc = segnb_fprop_dma_try(&did, g, in, (unsigned)inb, wpacked, (unsigned)wb, bias, bias_n, out, stats, (hipStream_t)stream,
                                  nullptr, src);
-    if (rc == 1) {
-        SEGNB_LAUNCH_CHECK();
-        return 0;
-    }
-    if (rc == 0) {
+    if (rc) return rc;
+    if (did == SEGNB_TRY_DECLINED) {
         segnb_set_error("segnb_conv_fprop_upcat: no kernel for this geometry");
         return SEGNB_E_UNSUPPORTED;
     }
-    return rc;
+    SEGNB_LAUNCH_CHECK();
+    return 0;
 }
 
 static bool upsum_geom_ok(const segnb_conv_geom* g, int dtype, int Cu) {
@@ -1982,39 +1978,60 @@ extern "C" int segnb_conv_fprop_upsum(const segnb_conv_geom* g, int dtype, const
     const long long inb = (((long long)g->N * g->Hi * g->Wi - 1) * g->ld_in + g->Ci) * 2;
     const long long wb = (long long)g->Co * g->ntaps * g->Ci * 2;
     SEGNB_CHECK_ARG(inb < (1ll << 31) && wb < (1ll << 31), "tensor larger than 2 GiB (32-bit buffer offsets)");
-    const int rc = segnb_fprop_rw_try(g, in, (unsigned)inb, wpacked, (unsigned)wb, nullptr, 0, out, nullptr, (hipStream_t)stream,
-                                      nullptr, nullptr, nullptr, dst);
-    if (rc == 1) {
-        SEGNB_LAUNCH_CHECK();
-        return 0;
-    }
-    if (rc == 0) {
+    segnb_try_outcome did;
+    if (int rc = segnb_fprop_rw_try(&did, g, in, (unsigned)inb, wpacked, (unsigned)wb, nullptr, 0, out, nullptr, (hipStream_t)stream,
+                                    nullptr, nullptr, nullptr, dst))
+        return rc;
+    if (did == SEGNB_TRY_DECLINED) {
         segnb_set_error("segnb_conv_fprop_upsum: no kernel for this geometry");
         return SEGNB_E_UNSUPPORTED;
     }
-    return rc;
+    SEGNB_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- the shared ends of the four weight-gradient entry points (segnb_conv_wgrad, _upcat, _bnapply, _tf)
+// The target armed for this call (segnb_wgrad_target_arm) or NULL, checked against g.  Each of them takes it right after
+// SEGNB_PLAN_RECORD, before anything can return: the call consumes an armed target whatever happens next, an argument error
+// included, so a target never leaks into the next call.
+static int take_wgrad_target(const char* fn, const segnb_conv_geom* g, const segnb_wgrad_target** tgt) {
+    const segnb_wgrad_target* t = *tgt = segnb_take_wgrad_target();
+    if (t != nullptr && (g == nullptr || t->ntaps != g->ntaps || t->Co > g->Co || g->Co - t->Co >= 8 || t->Ci > g->Ci)) {
+        segnb_set_error("%s: bad argument: the armed segnb_wgrad_target does not belong to this geometry (taps / channel counts)", fn);
+        return SEGNB_E_BADARG;
+    }
+    return 0;
+}
+
+// After the kernel (did: what it did): the nslab slabs it left for a target are summed into the parameter's gradient
+// (segnb_wgrad_to_param; rezero: slab 0 is cleared again for the general kernels' atomics), then the launch check.  A launch no
+// kernel took is SEGNB_E_UNSUPPORTED.
+static int finish_wgrad(const char* fn, segnb_try_outcome did, const segnb_conv_geom* g, float* dwp, int nslab,
+                        const segnb_wgrad_target* tgt, bool rezero, hipStream_t stream) {
+    if (did == SEGNB_TRY_DECLINED) {
+        segnb_set_error("%s: no kernel for this geometry", fn);
+        return SEGNB_E_UNSUPPORTED;
+    }
+    if (tgt != nullptr && did == SEGNB_TRY_LAUNCHED) segnb_wgrad_to_param(dwp, g->Co, g->ntaps, g->Ci, nslab, tgt, rezero, stream);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        segnb_set_error("%s: launch failed: %s", fn, hipGetErrorString(e));
+        return (int)e;
+    }
+    return 0;
 }
 
 extern "C" int segnb_conv_wgrad_upcat(const segnb_conv_geom* g, int dtype, const void* in, const segnb_upcat_src* src,
                                       const void* dout, float* dwp, int nslab, segnb_stream_t stream) {
     SEGNB_PLAN_RECORD(segnb_conv_wgrad_upcat, g, dtype, in, src, dout, dwp, nslab, stream);
-    const segnb_wgrad_target* const tgt = segnb_take_wgrad_target();
+    const segnb_wgrad_target* tgt;
+    if (int rc = take_wgrad_target(__func__, g, &tgt)) return rc;
     SEGNB_CHECK_ARG(in && src && src->u && dout && dwp, "NULL tensor");
-    SEGNB_CHECK_ARG(tgt == nullptr || (tgt->ntaps == g->ntaps && tgt->Co <= g->Co && g->Co - tgt->Co < 8 && tgt->Ci <= g->Ci),
-                    "the armed segnb_wgrad_target does not belong to this geometry (taps / channel counts)");
     SEGNB_CHECK_ARG(upcat_geom_ok(g, dtype, src->Cu), "geometry not served (segnb_conv_upcat_ok)");
     SEGNB_CHECK_ARG(nslab == segnb_conv_wgrad_slabs(g, dtype), "nslab differs from segnb_conv_wgrad_slabs()");
-    const int rc = segnb_wgrad_s1_try(g, in, dout, dwp, nslab, (hipStream_t)stream, false, nullptr, src, tgt);
-    if (rc == 1 || rc == 2) {
-        if (tgt != nullptr && rc == 1) segnb_wgrad_to_param(dwp, g->Co, g->ntaps, g->Ci, nslab, tgt, false, (hipStream_t)stream);
-        SEGNB_LAUNCH_CHECK();
-        return 0;
-    }
-    if (rc == 0) {
-        segnb_set_error("segnb_conv_wgrad_upcat: no kernel for this geometry");
-        return SEGNB_E_UNSUPPORTED;
-    }
-    return rc;
+    segnb_try_outcome did;
+    if (int rc = segnb_wgrad_s1_try(&did, g, in, dout, dwp, nslab, (hipStream_t)stream, false, nullptr, src, tgt)) return rc;
+    return finish_wgrad(__func__, did, g, dwp, nslab, tgt, false, (hipStream_t)stream);
 }
 
 // few input channels -> many output channels: the data gradient of a dense layer (tiramisu.py:9-20, growth 16 -> the prefix);
@@ -2044,37 +2061,35 @@ extern "C" int segnb_conv_fprop_bnreduce(const segnb_conv_geom* g, int dtype, co
     const long long wb = (long long)g->Co * g->ntaps * g->Ci * 2;
     SEGNB_CHECK_ARG(inb < (1ll << 31) && wb < (1ll << 31), "tensor larger than 2 GiB (32-bit buffer offsets)");
     int rc = 0;
+    segnb_try_outcome did;
     if (ep->coef == nullptr) {
         // activation mask of a producing layer without BatchNorm: out = dz (conv_roll_kernel, EPI = 3)
         SEGNB_CHECK_ARG(segnb_conv_fprop_actmask_ok(g, dtype), "geometry not served by a fused kernel (segnb_conv_fprop_actmask_ok)");
         if (segnb_fprop_roll_actmask_ok(g))
-            rc = segnb_fprop_roll_try(g, in, (unsigned)inb, wpacked, (unsigned)wb, nullptr, 0, out, nullptr, (hipStream_t)stream, ep);
+            rc = segnb_fprop_roll_try(&did, g, in, (unsigned)inb, wpacked, (unsigned)wb, nullptr, 0, out, nullptr, (hipStream_t)stream, ep);
         else      // 64-channel-chunk inputs: the MASK instantiation of conv_fprop_ws_kernel
-            rc = segnb_fprop_dma_try(g, in, (unsigned)inb, wpacked, (unsigned)wb, nullptr, 0, out, nullptr, (hipStream_t)stream, nullptr,
-                                     nullptr, ep);
-        if (rc != 1) {
-            segnb_set_error("segnb_conv_fprop_bnreduce: the fused kernel refused the launch (%d)", rc);
-            return rc > 1 ? rc : SEGNB_E_BADARG;
-        }
-        SEGNB_LAUNCH_CHECK();
-        return 0;
-    }
-    SEGNB_CHECK_ARG(segnb_conv_fprop_bnreduce_ok(g, dtype), "geometry not served by a fused kernel (segnb_conv_fprop_bnreduce_ok)");
-    if (bnreduce_general(g)) {
-        SEGNB_CHECK_ARG(ep->ld_y % 8 == 0 && (((long long)g->N * g->Ho * g->Wo - 1) * ep->ld_y + g->Co) * 2 < (1ll << 31), "bad y");
-        return conv_fprop_impl(g, dtype, in, wpacked, nullptr, 0, out, nullptr, stream, nullptr, ep);
-    }
-    if (g->Ci <= 96) {
-        rc = segnb_fprop_roll_try(g, in, (unsigned)inb, wpacked, (unsigned)wb, nullptr, 0, out, nullptr, (hipStream_t)stream, ep);
-        if (rc == 0)
-            rc = segnb_fprop_rw_try(g, in, (unsigned)inb, wpacked, (unsigned)wb, nullptr, 0, out, nullptr, (hipStream_t)stream, ep);
+            rc = segnb_fprop_dma_try(&did, g, in, (unsigned)inb, wpacked, (unsigned)wb, nullptr, 0, out, nullptr, (hipStream_t)stream,
+                                     nullptr, nullptr, ep);
     } else {
-        rc = segnb_fprop_dma_try(g, in, (unsigned)inb, wpacked, (unsigned)wb, nullptr, 0, out, nullptr, (hipStream_t)stream, nullptr,
-                                 nullptr, ep);
+        SEGNB_CHECK_ARG(segnb_conv_fprop_bnreduce_ok(g, dtype), "geometry not served by a fused kernel (segnb_conv_fprop_bnreduce_ok)");
+        if (bnreduce_general(g)) {
+            SEGNB_CHECK_ARG(ep->ld_y % 8 == 0 && (((long long)g->N * g->Ho * g->Wo - 1) * ep->ld_y + g->Co) * 2 < (1ll << 31), "bad y");
+            return conv_fprop_impl(g, dtype, in, wpacked, nullptr, 0, out, nullptr, stream, nullptr, ep);
+        }
+        if (g->Ci <= 96) {
+            rc = segnb_fprop_roll_try(&did, g, in, (unsigned)inb, wpacked, (unsigned)wb, nullptr, 0, out, nullptr, (hipStream_t)stream, ep);
+            if (!rc && !did)
+                rc = segnb_fprop_rw_try(&did, g, in, (unsigned)inb, wpacked, (unsigned)wb, nullptr, 0, out, nullptr, (hipStream_t)stream,
+                                        ep);
+        } else {
+            rc = segnb_fprop_dma_try(&did, g, in, (unsigned)inb, wpacked, (unsigned)wb, nullptr, 0, out, nullptr, (hipStream_t)stream,
+                                     nullptr, nullptr, ep);
+        }
     }
-    if (rc != 1) {
-        segnb_set_error("segnb_conv_fprop_bnreduce: the fused kernel refused the launch (%d)", rc);
-        return rc > 1 ? rc : SEGNB_E_BADARG;
+    if (rc) return rc;
+    if (did == SEGNB_TRY_DECLINED) {
+        segnb_set_error("segnb_conv_fprop_bnreduce: the fused kernel refused the launch");
+        return SEGNB_E_BADARG;
     }
     SEGNB_LAUNCH_CHECK();
     return 0;
@@ -2132,10 +2147,9 @@ extern "C" int segnb_conv_wgrad_slabs(const segnb_conv_geom* g, int dtype) {
 extern "C" int segnb_conv_wgrad(const segnb_conv_geom* g, int dtype, const void* in, const void* dout,
                                 float* dwp, int nslab, segnb_stream_t stream) {
     SEGNB_PLAN_RECORD(segnb_conv_wgrad, g, dtype, in, dout, dwp, nslab, stream);
-    const segnb_wgrad_target* const tgt = segnb_take_wgrad_target();
+    const segnb_wgrad_target* tgt;
+    if (int rc = take_wgrad_target(__func__, g, &tgt)) return rc;
     if (int rc = check_geom(g)) return rc;
-    SEGNB_CHECK_ARG(tgt == nullptr || (tgt->ntaps == g->ntaps && tgt->Co <= g->Co && g->Co - tgt->Co < 8 && tgt->Ci <= g->Ci),
-                    "the armed segnb_wgrad_target does not belong to this geometry (taps / channel counts)");
     SEGNB_CHECK_ARG(in && dout && dwp, "NULL tensor");
     SEGNB_CHECK_ARG(nslab == segnb_conv_wgrad_slabs(g, dtype), "nslab differs from segnb_conv_wgrad_slabs()");
     WgradArgs a;
@@ -2145,29 +2159,23 @@ extern "C" int segnb_conv_wgrad(const segnb_conv_geom* g, int dtype, const void*
     a.dwp = dwp;
     a.M = g->N * g->QH * g->QW;
     a.Ktot = g->ntaps * g->Ci;
-    int rc;
+    const hipStream_t st = (hipStream_t)stream;
+    int rc = 0;
     if (dtype == SEGNB_BF16) {
         // stride-1 3x3: pixel-major LDS tiles + transposing LDS reads, all taps per block (wgrad_s1.hip)
         // (with a target the fast kernels leave their slabs unreduced: segnb_wgrad_to_param sums them into the parameter's gradient)
-        const bool part = tgt != nullptr;
-        rc = (wgrad_general_only() || !segnb_knob_wgrad_roll()) ? 0 : segnb_wgrad_roll_try(g, in, dout, dwp, nslab, (hipStream_t)stream, part);
-        if (rc == 0 && !wgrad_general_only() && segnb_knob_wgrad_c8roll() && segnb_wgrad_s1_slabs(g) > 0)
-            rc = segnb_wgrad_c8roll_try(g, in, dout, dwp, nslab, (hipStream_t)stream, part);
-        if (rc == 0)
-            rc = wgrad_general_only() ? 0 : segnb_wgrad_s1_try(g, in, dout, dwp, nslab, (hipStream_t)stream, false, nullptr, nullptr, tgt);
-        if (rc == 1 || rc == 2) {
-            if (tgt != nullptr && rc == 1) segnb_wgrad_to_param(dwp, g->Co, g->ntaps, g->Ci, nslab, tgt, false, (hipStream_t)stream);
-            SEGNB_LAUNCH_CHECK();
-            return 0;
-        }
-        if (rc != 0) return rc;
-        rc = wgrad_general_only() ? 0 : segnb_wgrad_sx_try(g, in, dout, dwp, nslab, (hipStream_t)stream, part);
-        if (rc == 1) {
-            if (tgt != nullptr) segnb_wgrad_to_param(dwp, g->Co, g->ntaps, g->Ci, nslab, tgt, false, (hipStream_t)stream);
-            SEGNB_LAUNCH_CHECK();
-            return 0;
-        }
-        if (rc != 0) return rc;
+        const bool part = tgt != nullptr, general = wgrad_general_only();
+        segnb_try_outcome did = SEGNB_TRY_DECLINED;       // (until a kernel below takes the launch)
+        if (!general && segnb_knob_wgrad_roll())
+            rc = segnb_wgrad_roll_try(&did, g, in, dout, dwp, nslab, st, part);
+        if (!rc && !did && !general && segnb_knob_wgrad_c8roll() && segnb_wgrad_s1_slabs(g) > 0)
+            rc = segnb_wgrad_c8roll_try(&did, g, in, dout, dwp, nslab, st, part);
+        if (!rc && !did && !general)
+            rc = segnb_wgrad_s1_try(&did, g, in, dout, dwp, nslab, st, false, nullptr, nullptr, tgt);
+        if (!rc && !did && !general)
+            rc = segnb_wgrad_sx_try(&did, g, in, dout, dwp, nslab, st, part);
+        if (rc) return rc;
+        if (did) return finish_wgrad(__func__, did, g, dwp, nslab, tgt, false, st);
         if (wgrad_co8_applies(g)) {
             const int nslot = g->ntaps * (g->Ci / 8), PL = NT / nslot;
             int grid = segnb_num_cus() * 8;
@@ -2183,9 +2191,7 @@ extern "C" int segnb_conv_wgrad(const segnb_conv_geom* g, int dtype, const void*
     }
     if (rc) return rc;
     // general kernels: one slab, accumulated with atomics into the zeroed workspace -- delivered and re-zeroed in one pass
-    if (tgt != nullptr) segnb_wgrad_to_param(dwp, g->Co, g->ntaps, g->Ci, 1, tgt, true, (hipStream_t)stream);
-    SEGNB_LAUNCH_CHECK();
-    return 0;
+    return finish_wgrad(__func__, SEGNB_TRY_LAUNCHED, g, dwp, 1, tgt, true, st);
 }
 
 // weight gradient whose dy operand is the BatchNorm-backward apply of (g, y), recomputed in the kernel (first layer of a
@@ -2204,27 +2210,20 @@ extern "C" int segnb_conv_wgrad_bnapply(const segnb_conv_geom* g, int dtype, con
                                         const void* y, int ld_y, const float* coef, const float* bcoef, int Cp, int act,
                                         float slope, float* dwp, int nslab, segnb_stream_t stream) {
     SEGNB_PLAN_RECORD(segnb_conv_wgrad_bnapply, g, dtype, in, gsrc, ld_g, y, ld_y, coef, bcoef, Cp, act, slope, dwp, nslab, stream);
-    const segnb_wgrad_target* const tgt = segnb_take_wgrad_target();
+    const segnb_wgrad_target* tgt;
+    if (int rc = take_wgrad_target(__func__, g, &tgt)) return rc;
     if (int rc = check_geom(g)) return rc;
-    SEGNB_CHECK_ARG(tgt == nullptr || (tgt->ntaps == g->ntaps && tgt->Co <= g->Co && g->Co - tgt->Co < 8 && tgt->Ci <= g->Ci),
-                    "the armed segnb_wgrad_target does not belong to this geometry (taps / channel counts)");
     SEGNB_CHECK_ARG(in && gsrc && y && coef && bcoef && dwp, "NULL tensor");
     SEGNB_CHECK_ARG(segnb_conv_wgrad_bnapply_ok(g, dtype), "geometry not served (segnb_conv_wgrad_bnapply_ok)");
     SEGNB_CHECK_ARG(nslab == segnb_conv_wgrad_slabs(g, dtype), "nslab differs from segnb_conv_wgrad_slabs()");
     SEGNB_CHECK_ARG(Cp >= g->Co && ld_g >= g->Co && ld_y >= g->Co, "bad strides");
     const segnb_wgrad_bnapply bna = {gsrc, ld_g, y, ld_y, coef, bcoef, Cp, act, slope};
-    int rc = segnb_knob_wgrad_c8roll() ? segnb_wgrad_c8roll_try(g, in, nullptr, dwp, nslab, (hipStream_t)stream, tgt != nullptr, &bna) : 0;
-    if (rc == 0) rc = segnb_wgrad_s1_try(g, in, nullptr, dwp, nslab, (hipStream_t)stream, false, &bna, nullptr, tgt);
-    if (rc == 1 || rc == 2) {
-        if (tgt != nullptr && rc == 1) segnb_wgrad_to_param(dwp, g->Co, g->ntaps, g->Ci, nslab, tgt, false, (hipStream_t)stream);
-        SEGNB_LAUNCH_CHECK();
-        return 0;
-    }
-    if (rc == 0) {
-        segnb_set_error("segnb_conv_wgrad_bnapply: no kernel for this geometry");
-        return SEGNB_E_UNSUPPORTED;
-    }
-    return rc;
+    segnb_try_outcome did = SEGNB_TRY_DECLINED;
+    int rc = 0;
+    if (segnb_knob_wgrad_c8roll()) rc = segnb_wgrad_c8roll_try(&did, g, in, nullptr, dwp, nslab, (hipStream_t)stream, tgt != nullptr, &bna);
+    if (!rc && !did) rc = segnb_wgrad_s1_try(&did, g, in, nullptr, dwp, nslab, (hipStream_t)stream, false, &bna, nullptr, tgt);
+    if (rc) return rc;
+    return finish_wgrad(__func__, did, g, dwp, nslab, tgt, false, (hipStream_t)stream);
 }
 
 // weight gradient whose operands are recomputed on load (include/segnb_hip.h: segnb_operand_tf)
@@ -2237,27 +2236,18 @@ extern "C" int segnb_conv_wgrad_tf(const segnb_conv_geom* g, int dtype, const vo
                                    const void* dout, const segnb_operand_tf* tf_dout, float* dwp, int nslab,
                                    segnb_stream_t stream) {
     SEGNB_PLAN_RECORD(segnb_conv_wgrad_tf, g, dtype, in, tf_in, dout, tf_dout, dwp, nslab, stream);
-    const segnb_wgrad_target* const tgt = segnb_take_wgrad_target();
+    const segnb_wgrad_target* tgt;
+    if (int rc = take_wgrad_target(__func__, g, &tgt)) return rc;
     if (int rc = check_geom(g)) return rc;
-    SEGNB_CHECK_ARG(tgt == nullptr || (tgt->ntaps == g->ntaps && tgt->Co <= g->Co && g->Co - tgt->Co < 8 && tgt->Ci <= g->Ci),
-                    "the armed segnb_wgrad_target does not belong to this geometry (taps / channel counts)");
     SEGNB_CHECK_ARG(in && dout && dwp, "NULL tensor");
     SEGNB_CHECK_ARG(segnb_conv_wgrad_tf_ok(g, dtype), "geometry not served (segnb_conv_wgrad_tf_ok)");
     SEGNB_CHECK_ARG(nslab == segnb_conv_wgrad_slabs(g, dtype), "nslab differs from segnb_conv_wgrad_slabs()");
     SEGNB_CHECK_ARG(tf_in == nullptr || (tf_in->kind == SEGNB_TF_ACT && tf_in->coef != nullptr && tf_in->Cp >= g->Ci), "bad input transform");
     SEGNB_CHECK_ARG(tf_dout == nullptr || (tf_dout->kind == SEGNB_TF_BNBWD && tf_dout->coef && tf_dout->bcoef && tf_dout->y &&
                                            tf_dout->drop == nullptr && tf_dout->Cp >= g->Co), "bad dout transform");
-    const int rc = segnb_wgrad_roll_try(g, in, dout, dwp, nslab, (hipStream_t)stream, tgt != nullptr, tf_in, tf_dout);
-    if (rc == 1) {
-        if (tgt != nullptr) segnb_wgrad_to_param(dwp, g->Co, g->ntaps, g->Ci, nslab, tgt, false, (hipStream_t)stream);
-        SEGNB_LAUNCH_CHECK();
-        return 0;
-    }
-    if (rc == 0) {
-        segnb_set_error("segnb_conv_wgrad_tf: no kernel for this geometry");
-        return SEGNB_E_UNSUPPORTED;
-    }
-    return rc;
+    segnb_try_outcome did;
+    if (int rc = segnb_wgrad_roll_try(&did, g, in, dout, dwp, nslab, (hipStream_t)stream, tgt != nullptr, tf_in, tf_dout)) return rc;
+    return finish_wgrad(__func__, did, g, dwp, nslab, tgt, false, (hipStream_t)stream);
 }
 
 static int fill_pack_args(PackArgs& p, int Mp, int Cp, int ntaps, long long s_m, long long s_c,

@@ -240,19 +240,20 @@ static_assert(256 * 16 * 8 <= C8_SMEM, "statistics reduction scratch");
 
 }  // namespace
 
-static int c8_launch(const segnb_conv_geom* g, const void* in, const C8Norm* u8, const void* wpacked, const float* bias,
-                     int bias_n, void* out, double* stats, hipStream_t stream, const segnb_act_epilogue* ep = nullptr);
+// false: the geometry is not served (nothing launched)
+static bool c8_launch(const segnb_conv_geom* g, const void* in, const C8Norm* u8, const void* wpacked, const float* bias,
+                      int bias_n, void* out, double* stats, hipStream_t stream, const segnb_act_epilogue* ep = nullptr);
 
-// 1 = handled, 0 = not applicable, else error
-int segnb_fprop_c8_try(const segnb_conv_geom* g, const void* in, const void* wpacked, const float* bias, int bias_n,
+int segnb_fprop_c8_try(segnb_try_outcome* did, const segnb_conv_geom* g, const void* in, const void* wpacked, const float* bias, int bias_n,
                        void* out, double* stats, hipStream_t stream, const segnb_act_epilogue* ep) {
-    if (!segnb_knob_fprop_dma()) return 0;
-    return c8_launch(g, in, nullptr, wpacked, bias, bias_n, out, stats, stream, ep);
+    *did = SEGNB_TRY_DECLINED;
+    if (segnb_knob_fprop_dma() && c8_launch(g, in, nullptr, wpacked, bias, bias_n, out, stats, stream, ep)) *did = SEGNB_TRY_LAUNCHED;
+    return 0;
 }
 
-static int c8_launch(const segnb_conv_geom* g, const void* in, const C8Norm* u8, const void* wpacked, const float* bias,
-                     int bias_n, void* out, double* stats, hipStream_t stream, const segnb_act_epilogue* ep) {
-    if (g->ntaps != 9 || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return 0;
+static bool c8_launch(const segnb_conv_geom* g, const void* in, const C8Norm* u8, const void* wpacked, const float* bias,
+                      int bias_n, void* out, double* stats, hipStream_t stream, const segnb_act_epilogue* ep) {
+    if (g->ntaps != 9 || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return false;
     if (g->Co > 32 && g->Co <= 64 && g->Co % 8 == 0 && g->Ci == 8 && stats == nullptr && u8 == nullptr &&
         (ep == nullptr || ep->coef == nullptr)) {
         // 33..64 output channels (unet16.py:73: VGG's 3 -> 64 at 1024 x 1024) as two launches over channel halves: the input is
@@ -260,13 +261,12 @@ static int c8_launch(const segnb_conv_geom* g, const void* in, const C8Norm* u8,
         // general kernel against 2 x ~75).  Without per-channel side tables only (statistics and a folded BatchNorm index by Co)
         segnb_conv_geom h = *g;
         h.Co = 32;
-        const int rc = c8_launch(&h, in, nullptr, wpacked, bias, bias_n < 32 ? bias_n : 32, out, nullptr, stream, ep);
-        if (rc != 1) return rc;
+        if (!c8_launch(&h, in, nullptr, wpacked, bias, bias_n < 32 ? bias_n : 32, out, nullptr, stream, ep)) return false;
         h.Co = g->Co - 32;
         return c8_launch(&h, in, nullptr, (const bf16_t*)wpacked + 32 * 9 * 8, bias != nullptr && bias_n > 32 ? bias + 32 : nullptr,
                          bias_n > 32 ? bias_n - 32 : 0, (bf16_t*)out + 32, nullptr, stream, ep);
     }
-    if (g->QH != g->Ho || g->QW != g->Wo || g->Ci != 8 || g->Co > 32 || g->Wo < 12) return 0;
+    if (g->QH != g->Ho || g->QW != g->Wo || g->Ci != 8 || g->Co > 32 || g->Wo < 12) return false;
     int dhmin = g->dh[0], dhmax = g->dh[0], dwmin = g->dw[0], dwmax = g->dw[0];
     for (int t = 1; t < 9; ++t) {
         dhmin = g->dh[t] < dhmin ? g->dh[t] : dhmin;
@@ -274,7 +274,7 @@ static int c8_launch(const segnb_conv_geom* g, const void* in, const C8Norm* u8,
         dwmin = g->dw[t] < dwmin ? g->dw[t] : dwmin;
         dwmax = g->dw[t] > dwmax ? g->dw[t] : dwmax;
     }
-    if (dhmax - dhmin != 2 || dwmax - dwmin != 2) return 0;
+    if (dhmax - dhmin != 2 || dwmax - dwmin != 2) return false;
     C8Args a;
     a.ep_act = ep != nullptr ? ep->act : -1;
     a.ep_coef = ep != nullptr ? ep->coef : nullptr;
@@ -306,7 +306,7 @@ static int c8_launch(const segnb_conv_geom* g, const void* in, const C8Norm* u8,
         hipLaunchKernelGGL((conv_fprop_c8_kernel<false, true>), dim3(grid), dim3(256), 0, stream, a);
     else
         hipLaunchKernelGGL((conv_fprop_c8_kernel<false, false>), dim3(grid), dim3(256), 0, stream, a);
-    return 1;
+    return true;
 }
 
 // ---- uint8 HWC network input ----------------------------------------------------------------------
@@ -388,9 +388,8 @@ extern "C" int segnb_conv_fprop_u8(const segnb_conv_geom* g, const unsigned char
     SEGNB_CHECK_ARG(x_packed == nullptr || (ld_packed >= 8 && ld_packed % 8 == 0), "bad packed-input stride");
     u.packed_out = (bf16_t*)x_packed;
     u.ld_p = ld_packed;
-    const int rc = c8_launch(g, nullptr, &u, wpacked, bias, bias_n, out, stats, (hipStream_t)stream);
-    if (rc != 1) {
-        segnb_set_error("segnb_conv_fprop_u8: launch refused (%d)", rc);
+    if (!c8_launch(g, nullptr, &u, wpacked, bias, bias_n, out, stats, (hipStream_t)stream)) {
+        segnb_set_error("segnb_conv_fprop_u8: launch refused");
         return SEGNB_E_BADARG;
     }
     SEGNB_LAUNCH_CHECK();

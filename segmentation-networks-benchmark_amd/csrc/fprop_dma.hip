@@ -1410,10 +1410,11 @@ int dispatch_fd(FdArgs& a, hipStream_t stream) {
 
 // out[n, 2 Y + py, 2 X + px, :] += sum_{a, b < 2} in[n, Y + py - 1 + a, X + px - 1 + b, :] . W[phase][:, tap, :]  for the four
 // phases (py, px); wpacked = [4][CoW][4][Ci] (phase-major, the tap lists of segnb.convplan.convt_fwd(4, 2, 1)); statistics of
-// the sums.  1 = launched, 0 = not served
-int segnb_fprop_upf_try(int N, int H, int W, int Ci, int ld_in, const void* in, unsigned in_bytes, const void* wpacked,
-                        unsigned w_bytes, int Co, int CoW, void* out, int ld_out, double* stats, hipStream_t stream,
+// the sums
+int segnb_fprop_upf_try(segnb_try_outcome* did, int N, int H, int W, int Ci, int ld_in, const void* in, unsigned in_bytes,
+                        const void* wpacked, unsigned w_bytes, int Co, int CoW, void* out, int ld_out, double* stats, hipStream_t stream,
                         const float* bias, int bias_n, int no_prev, int ep_act, float ep_slope) {
+    *did = SEGNB_TRY_DECLINED;
     if (!segnb_knob_fprop_dma() || !segnb_knob_fprop_upd()) return 0;
     if (Ci % 64 != 0 || Ci < 128 || (Co <= 32 && !no_prev) || W < 12) return 0;
     FdArgs a;
@@ -1454,7 +1455,7 @@ int segnb_fprop_upf_try(int N, int H, int W, int Ci, int ld_in, const void* in, 
     const int rc = cfg == 0 ? launch_ws_upf<WsCfg<64, 8, 32, 4, false, true, 4, 2>>(a, stream)
                             : launch_ws_upf<WsCfg<64, 16, 16, 4, false, true, 4, 2>>(a, stream);
     if (rc == NOT_HANDLED) return 0;
-    return rc ? rc : 1;
+    return segnb_try_launched(did, rc);
 }
 
 // 1 when the MASK instantiation serves the data gradient g (segnb_conv_fprop_actmask_ok): what segnb_fprop_dma_try + dispatch_fd accept
@@ -1496,11 +1497,12 @@ int segnb_fprop_dma_read_stamps(unsigned long long* host_dst) {
     return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(g_stamps), sizeof(unsigned long long) * 3 * 256 * 4);
 }
 
-// 1 = handled, 0 = not applicable (caller falls through to fprop_s1 / the general gather kernel), else error
-int segnb_fprop_dma_try(const segnb_conv_geom* g, const void* in, unsigned in_bytes, const void* wpacked,
+// (declined: the caller falls through to fprop_s1 / the general gather kernel)
+int segnb_fprop_dma_try(segnb_try_outcome* did, const segnb_conv_geom* g, const void* in, unsigned in_bytes, const void* wpacked,
                         unsigned w_bytes, const float* bias, int bias_n, void* out, double* stats,
                         hipStream_t stream, const segnb_act_epilogue* ep, const segnb_upcat_src* uc,
                         const segnb_bn_reduce_epilogue* bn) {
+    *did = SEGNB_TRY_DECLINED;
     if (!segnb_knob_fprop_dma()) return 0;
     // (fused BatchNorm-backward REDUCTIONS: fprop_rw.hip / fprop_roll.hip; here only the activation mask of a layer without
     // BatchNorm -- coef NULL -- on a plain data gradient: the MASK instantiation)
@@ -1532,7 +1534,7 @@ int segnb_fprop_dma_try(const segnb_conv_geom* g, const void* in, unsigned in_by
         a.ep_slope = 0.f;
         const int rc = try_upd(g, a, stream);
         if (rc == NOT_HANDLED) return 0;
-        return rc ? rc : 1;
+        return segnb_try_launched(did, rc);
     }
     if (g->ntaps != 9 || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return 0;
     if (g->QH != g->Ho || g->QW != g->Wo || g->Ci % 64 != 0) return 0;
@@ -1602,5 +1604,5 @@ int segnb_fprop_dma_try(const segnb_conv_geom* g, const void* in, unsigned in_by
     a.ep_slope = ep != nullptr ? ep->slope : 0.f;
     const int rc = dispatch_fd(a, stream);
     if (rc == NOT_HANDLED) return 0;
-    return rc ? rc : 1;
+    return segnb_try_launched(did, rc);
 }

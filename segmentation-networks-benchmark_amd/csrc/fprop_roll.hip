@@ -636,10 +636,10 @@ int launch_roll_split(RollArgs& a, hipStream_t stream) {
 
 }  // namespace
 
-// 1 = handled, 0 = not applicable, else error
-int segnb_fprop_roll_try(const segnb_conv_geom* g, const void* in, unsigned in_bytes, const void* wpacked, unsigned w_bytes,
-                         const float* bias, int bias_n, void* out, double* stats, hipStream_t stream,
+int segnb_fprop_roll_try(segnb_try_outcome* did, const segnb_conv_geom* g, const void* in, unsigned in_bytes, const void* wpacked,
+                         unsigned w_bytes, const float* bias, int bias_n, void* out, double* stats, hipStream_t stream,
                          const segnb_bn_reduce_epilogue* bn, const segnb_operand_tf* tf, const segnb_upcat_src* uc) {
+    *did = SEGNB_TRY_DECLINED;
     const int knob = segnb_knob_fprop_roll();
     if (!knob) return 0;
     if (g->ntaps != 9 || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return 0;
@@ -700,11 +700,11 @@ int segnb_fprop_roll_try(const segnb_conv_geom* g, const void* in, unsigned in_b
     a.bn_y = nullptr;
     if (ksplit) {
         const int rc = launch_roll_split<2, 2, 1>(a, stream);
-        return rc ? rc : 1;
+        return segnb_try_launched(did, rc);
     }
     if (csplit) {
         const int rc = launch_roll_split<2, 1, 2>(a, stream);
-        return rc ? rc : 1;
+        return segnb_try_launched(did, rc);
     }
     if (bn != nullptr) {
         if (stats != nullptr) return 0;
@@ -741,12 +741,12 @@ int segnb_fprop_roll_try(const segnb_conv_geom* g, const void* in, unsigned in_b
         } else {
             return 0;
         }
-        return rc ? rc : 1;
+        return segnb_try_launched(did, rc);
     }
     // 32-column strips (more bytes in flight per wave, 6 % instead of 12 % halo columns) where the registers allow it: the
     // BatchNorm-reduce epilogue's per-channel constants do not fit beside them
     rc = (knob == 2 && bn == nullptr) ? launch_roll<1, 2, 2, 0, 3, 2>(a, stream) : launch_roll<1, 2, 1, 0, 3, 2>(a, stream);
-    return rc ? rc : 1;
+    return segnb_try_launched(did, rc);
 }
 
 // include/segnb_hip.h: segnb_conv_fprop_bnreduce with coef == NULL (the plain one-wave form of segnb_fprop_roll_try, any padding)
@@ -807,11 +807,13 @@ extern "C" int segnb_conv_fprop_tf(const segnb_conv_geom* g, int dtype, const vo
     const long long inb = (((long long)g->N * g->Hi * g->Wi - 1) * g->ld_in + g->Ci) * 2;
     const long long wb = (long long)g->Co * g->ntaps * g->Ci * 2;
     SEGNB_CHECK_ARG(inb < (1ll << 31) && wb < (1ll << 31), "tensor larger than 2 GiB (32-bit buffer offsets)");
-    const int rc = segnb_fprop_roll_try(g, in, (unsigned)inb, wpacked, (unsigned)wb, bias, bias_n, out, stats, (hipStream_t)stream,
-                                        bn, tf);
-    if (rc != 1) {
-        segnb_set_error("segnb_conv_fprop_tf: the kernel refused the launch (%d)", rc);
-        return rc > 1 ? rc : SEGNB_E_BADARG;
+    segnb_try_outcome did;
+    if (int rc = segnb_fprop_roll_try(&did, g, in, (unsigned)inb, wpacked, (unsigned)wb, bias, bias_n, out, stats, (hipStream_t)stream,
+                                      bn, tf))
+        return rc;
+    if (did == SEGNB_TRY_DECLINED) {
+        segnb_set_error("segnb_conv_fprop_tf: the kernel refused the launch");
+        return SEGNB_E_BADARG;
     }
     SEGNB_LAUNCH_CHECK();
     return 0;

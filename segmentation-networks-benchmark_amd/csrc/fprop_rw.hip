@@ -507,11 +507,11 @@ int launch_rw(FdArgs& a, hipStream_t stream) {
 
 }  // namespace
 
-// 1 = handled, 0 = not applicable, else error
-int segnb_fprop_rw_try(const segnb_conv_geom* g, const void* in, unsigned in_bytes, const void* wpacked,
+int segnb_fprop_rw_try(segnb_try_outcome* did, const segnb_conv_geom* g, const void* in, unsigned in_bytes, const void* wpacked,
                        unsigned w_bytes, const float* bias, int bias_n, void* out, double* stats,
                        hipStream_t stream, const segnb_bn_reduce_epilogue* bn, const segnb_act_epilogue* ep,
                        const segnb_upcat_src* uc, const segnb_upcat_src* upsum) {
+    *did = SEGNB_TRY_DECLINED;
     if (!segnb_knob_fprop_dma() || !segnb_knob_fprop_rw()) return 0;
     if (g->ntaps != 9 || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return 0;
     if (g->QH != g->Ho || g->QW != g->Wo || g->Ci % 32 != 0 || g->Ci > 96 || g->Co > 96 || g->Wo < 12) return 0;
@@ -610,5 +610,5 @@ int segnb_fprop_rw_try(const segnb_conv_geom* g, const void* in, unsigned in_byt
     else
         return 0;
     if (rc == -12345) return 0;
-    return rc ? rc : 1;
+    return segnb_try_launched(did, rc);
 }

@@ -358,9 +358,10 @@ int dispatch_fs1(FpS1Args& a, hipStream_t stream) {
 
 }  // namespace
 
-// 1 = handled, 0 = not a stride-1 3x3 case (caller uses the general gather kernel), else error
-int segnb_fprop_s1_try(const segnb_conv_geom* g, const void* in, const void* wpacked, const float* bias, int bias_n,
+// declined: not a stride-1 3x3 case (the caller uses the general gather kernel)
+int segnb_fprop_s1_try(segnb_try_outcome* did, const segnb_conv_geom* g, const void* in, const void* wpacked, const float* bias, int bias_n,
                        void* out, double* stats, hipStream_t stream, const float* drop, int ld_drop, int stats_ld) {
+    *did = SEGNB_TRY_DECLINED;
     if (g->ntaps != 9 || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return 0;
     if (g->QH != g->Ho || g->QW != g->Wo || g->Ci < 32) return 0;
     int dhmin = g->dh[0], dhmax = g->dh[0], dwmin = g->dw[0], dwmax = g->dw[0];
@@ -391,5 +392,5 @@ int segnb_fprop_s1_try(const segnb_conv_geom* g, const void* in, const void* wpa
     }
     const int rc = (g->Ci % 64 == 0) ? dispatch_fs1<64>(a, stream) : dispatch_fs1<32>(a, stream);
     if (rc == NOT_HANDLED) return 0;
-    return rc ? rc : 1;
+    return segnb_try_launched(did, rc);
 }

@@ -294,9 +294,10 @@ int launch_fx(FxArgs& a, hipStream_t stream) {
 
 }  // namespace
 
-// 1 = launched, 0 = geometry not served (the caller falls through to the general gather kernel), else an error
-int segnb_fprop_sx_try(const segnb_conv_geom* g, const void* in, const void* wpacked, const float* bias, int bias_n, void* out,
-                       double* stats, hipStream_t stream) {
+// declined: geometry not served (the caller falls through to the general gather kernel)
+int segnb_fprop_sx_try(segnb_try_outcome* did, const segnb_conv_geom* g, const void* in, const void* wpacked, const float* bias,
+                       int bias_n, void* out, double* stats, hipStream_t stream) {
+    *did = SEGNB_TRY_DECLINED;
     if ((g->in_step != 1 && g->in_step != 2) || g->QW < 24 || g->ntaps > 49) return 0;
     int dhmin = g->dh[0], dhmax = g->dh[0], dwmin = g->dw[0], dwmax = g->dw[0];
     for (int t = 1; t < g->ntaps; ++t) {
@@ -329,5 +330,5 @@ int segnb_fprop_sx_try(const segnb_conv_geom* g, const void* in, const void* wpa
         a.dw[t] = (signed char)(g->dw[t] - dwmin);
     }
     const int rc = launch_fx<2, 8, 8, 32, 7, 7, 64>(a, stream);
-    return rc ? rc : 1;
+    return segnb_try_launched(did, rc);
 }

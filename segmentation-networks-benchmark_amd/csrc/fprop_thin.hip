@@ -274,9 +274,9 @@ bool thin_geometry(const segnb_conv_geom* g) {
 
 }  // namespace
 
-// 1 = launched, 0 = not served
-int segnb_fprop_thin_try(const segnb_conv_geom* g, const void* in, const void* wpacked, void* out, hipStream_t stream,
-                         const segnb_bn_reduce_epilogue* bn) {
+int segnb_fprop_thin_try(segnb_try_outcome* did, const segnb_conv_geom* g, const void* in, const void* wpacked, void* out,
+                         hipStream_t stream, const segnb_bn_reduce_epilogue* bn) {
+    *did = SEGNB_TRY_DECLINED;
     if (!segnb_knob_fprop_thin() || !thin_geometry(g)) return 0;
     ThinArgs a;
     a.x = (const bf16_t*)in;
@@ -322,7 +322,8 @@ int segnb_fprop_thin_try(const segnb_conv_geom* g, const void* in, const void* w
         hipLaunchKernelGGL((conv_thin_kernel<true, 2>), dim3(grid), dim3(256), 0, stream, a);
     else
         hipLaunchKernelGGL((conv_thin_kernel<false, 4>), dim3(grid), dim3(256), 0, stream, a);
-    return 1;
+    *did = SEGNB_TRY_LAUNCHED;
+    return 0;
 }
 
 int segnb_fprop_thin_ok(const segnb_conv_geom* g) { return segnb_knob_fprop_thin() && thin_geometry(g) ? 1 : 0; }

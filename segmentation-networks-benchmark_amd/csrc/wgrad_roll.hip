@@ -670,10 +670,11 @@ bool segnb_wgrad_roll_applies(const segnb_conv_geom* g) {
     return true;
 }
 
-// 1 = handled, 0 = not applicable, else error.  nslab: the slab count of the workspace (segnb_conv_wgrad_slabs): one block per
+// nslab: the slab count of the workspace (segnb_conv_wgrad_slabs): one block per
 // slab.  tfx / tfd: operand transforms (NULL: the operand is in memory)
-int segnb_wgrad_roll_try(const segnb_conv_geom* g, const void* in, const void* dout, float* dwp, int nslab, hipStream_t stream,
-                         bool partial, const segnb_operand_tf* tfx, const segnb_operand_tf* tfd) {
+int segnb_wgrad_roll_try(segnb_try_outcome* did, const segnb_conv_geom* g, const void* in, const void* dout, float* dwp, int nslab,
+                         hipStream_t stream, bool partial, const segnb_operand_tf* tfx, const segnb_operand_tf* tfd) {
+    *did = SEGNB_TRY_DECLINED;
     if (!segnb_wgrad_roll_applies(g) || nslab < 1) return 0;
     WRollArgs a;
     for (int t = 0; t < 9; ++t) a.tap[(g->dh[t] + 1) * 3 + (g->dw[t] + 1)] = t;
@@ -727,7 +728,8 @@ int segnb_wgrad_roll_try(const segnb_conv_geom* g, const void* in, const void* d
     else rc = launch_wroll<0, 0>(a, nslab, stream);
     if (rc) return rc;
     if (nslab > 1 && !partial) segnb_slab_reduce(dwp, a.slab_stride, nslab, stream);
-    return 1;
+    *did = SEGNB_TRY_LAUNCHED;
+    return 0;
 }
 
 bool segnb_wgrad_c8roll_applies(const segnb_conv_geom* g) {
@@ -745,8 +747,9 @@ bool segnb_wgrad_c8roll_applies(const segnb_conv_geom* g) {
 }
 
 // the first layer's weight gradient (conv_wgrad_c8roll_kernel).  bna: dy recomputed from (g, y) (dout is then ignored)
-int segnb_wgrad_c8roll_try(const segnb_conv_geom* g, const void* in, const void* dout, float* dwp, int nslab, hipStream_t stream,
-                           bool partial, const segnb_wgrad_bnapply* bna) {
+int segnb_wgrad_c8roll_try(segnb_try_outcome* did, const segnb_conv_geom* g, const void* in, const void* dout, float* dwp, int nslab,
+                           hipStream_t stream, bool partial, const segnb_wgrad_bnapply* bna) {
+    *did = SEGNB_TRY_DECLINED;
     if (!segnb_wgrad_c8roll_applies(g) || nslab < 1) return 0;
     WRollArgs a;
     for (int t = 0; t < 9; ++t) a.tap[(g->dh[t] + 1) * 3 + (g->dw[t] + 1)] = t;
@@ -793,5 +796,6 @@ int segnb_wgrad_c8roll_try(const segnb_conv_geom* g, const void* in, const void*
     const int rc = bna != nullptr ? launch_c8roll<3>(a, nslab, stream) : launch_c8roll<0>(a, nslab, stream);
     if (rc) return rc;
     if (nslab > 1 && !partial) segnb_slab_reduce(dwp, a.slab_stride, nslab, stream);
-    return 1;
+    *did = SEGNB_TRY_LAUNCHED;
+    return 0;
 }

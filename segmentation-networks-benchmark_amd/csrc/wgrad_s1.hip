@@ -1054,7 +1054,7 @@ int launch_s1(WgS1Args& a, int nslab, hipStream_t stream, bool partial, const se
             hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((total + 63) / 64)), dim3(256), 0, stream, a.dwp,
                                total, S);
     }
-    return a.gw != nullptr ? -1000 : 0;       // (-1000: written to the target by the kernel itself)
+    return 0;
 }
 
 // tile configuration of the fast path for a geometry: 0 = not handled here (general kernel, one slab)
@@ -1415,11 +1415,11 @@ int segnb_wgrad_s1_slabs(const segnb_conv_geom* g) {
     return s1_slabs(((g->Co + c.bco - 1) / c.bco) * ((g->Ci + c.bci - 1) / c.bci), c.bco == 32, c.cfg == 4 || c.cfg == 5);
 }
 
-// returns 1 when the launch was handled here, 0 when the geometry is not a stride-1 3x3 bf16 case
-// (caller falls through to the general kernel), <0 / hipError on failure
-int segnb_wgrad_s1_try(const segnb_conv_geom* g, const void* in, const void* dout, float* dwp, int nslab,
+// declined when the geometry is not a stride-1 3x3 bf16 case (the caller falls through to the general kernel)
+int segnb_wgrad_s1_try(segnb_try_outcome* did, const segnb_conv_geom* g, const void* in, const void* dout, float* dwp, int nslab,
                        hipStream_t stream, bool partial, const segnb_wgrad_bnapply* bna, const segnb_upcat_src* uc,
                        const segnb_wgrad_target* tgt) {
+    *did = SEGNB_TRY_DECLINED;
     const S1Choice c = s1_choose(g);
     if (!c.cfg) return 0;
     if (tgt != nullptr) partial = true;           // the slabs are summed by segnb_wgrad_to_param
@@ -1451,9 +1451,7 @@ int segnb_wgrad_s1_try(const segnb_conv_geom* g, const void* in, const void* dou
         a.bna = *bna;
         rc = c.cfg == 1 ? launch_s1<32, 32, 8, 32, false, true>(a, nslab, stream, partial, tgt)
                         : launch_s1<32, 32, 16, 32, false, true>(a, nslab, stream, partial, tgt);
-        return rc == -1000 ? 2 : (rc ? rc : 1);
-    }
-    if (c.cfg == 1) rc = launch_s1<32, 32, 8, 32>(a, nslab, stream, partial, tgt);
+    } else if (c.cfg == 1) rc = launch_s1<32, 32, 8, 32>(a, nslab, stream, partial, tgt);
     else if (c.cfg == 6) rc = launch_s1<32, 32, 16, 32>(a, nslab, stream, partial, tgt);
     else if (c.cfg == 2) rc = launch_s1<64, 64, 4, 32>(a, nslab, stream, partial, tgt);
     else if (c.cfg == 7) rc = launch_s1<64, 64, 8, 32>(a, nslab, stream, partial, tgt);
@@ -1461,7 +1459,10 @@ int segnb_wgrad_s1_try(const segnb_conv_geom* g, const void* in, const void* dou
     else if (c.cfg == 3) rc = launch_s1<64, 64, 8, 16>(a, nslab, stream, partial, tgt);
     else if (c.cfg == 4) rc = launch_s1<64, 64, 4, 7, true>(a, nslab, stream, partial, tgt);
     else rc = launch_s1<64, 64, 1, 14, true>(a, nslab, stream, partial, tgt);
-    return rc == -1000 ? 2 : (rc ? rc : 1);           // 2: the single-slab launch wrote the target itself
+    if (rc) return rc;
+    // (launch_s1 checked nslab against the geometry's slab count: a single-slab launch writes the target from its accumulators)
+    *did = tgt != nullptr && nslab == 1 ? SEGNB_TRY_DELIVERED : SEGNB_TRY_LAUNCHED;
+    return 0;
 }
 
 
@@ -1472,8 +1473,9 @@ int segnb_wgrad_sx_slabs(const segnb_conv_geom* g) {
     return s1_slabs(((g->Co + c.bco - 1) / c.bco) * ((g->Ci + c.bci - 1) / c.bci), true);
 }
 
-int segnb_wgrad_sx_try(const segnb_conv_geom* g, const void* in, const void* dout, float* dwp, int nslab, hipStream_t stream,
-                       bool partial) {
+int segnb_wgrad_sx_try(segnb_try_outcome* did, const segnb_conv_geom* g, const void* in, const void* dout, float* dwp, int nslab,
+                       hipStream_t stream, bool partial) {
+    *did = SEGNB_TRY_DECLINED;
     const SxChoice c = sx_choose(g);
     if (!c.cfg) return 0;
     int dhmin = g->dh[0], dwmin = g->dw[0];
@@ -1502,7 +1504,7 @@ int segnb_wgrad_sx_try(const segnb_conv_geom* g, const void* in, const void* dou
            : c.cfg == 5 ? launch_sx<1, 32, 1, 256, 1, 1>(a, nslab, stream, partial)
            : c.cfg == 6 ? launch_sx<1, 64, 1, 256, 1, 1>(a, nslab, stream, partial)
                         : launch_sx<1, 128, 1, 256, 1, 1>(a, nslab, stream, partial);
-        return rc ? rc : 1;
+        return segnb_try_launched(did, rc);
     }
     if (c.cfg == 8) rc = launch_sx<1, 32, 8, 32, 2, 2, 32>(a, nslab, stream, partial);
     else if (c.cfg == 1) rc = launch_sx<2, 8, 8, 32, 7, 7>(a, nslab, stream, partial);
@@ -1510,5 +1512,5 @@ int segnb_wgrad_sx_try(const segnb_conv_geom* g, const void* in, const void* dou
     else if (c.cfg == 9) rc = launch_sx<2, 32, 4, 32, 4, 4>(a, nslab, stream, partial);
     else if (c.cfg == 10) rc = launch_sx<2, 32, 8, 16, 4, 4>(a, nslab, stream, partial);
     else rc = launch_sx<2, 32, 8, 16, 3, 3>(a, nslab, stream, partial);
-    return rc ? rc : 1;
+    return segnb_try_launched(did, rc);
 }

@@ -649,11 +649,7 @@ class _ZFUnetPlan(object):
     # ---- backward --------------------------------------------------------------------------------------
     def backward(self, dlogits):
         self._guard_mode, self._guard_active = (None, None), False
-        from segnb import engine as _engine
-        try:
-            out = self._backward(dlogits)
-        finally:
-            _engine.DW_OVERWRITE = False
+        out = self._backward(dlogits)
         self._guard_b.end(self._guard_active, *self._guard_mode)
         return out
 
@@ -669,8 +665,11 @@ class _ZFUnetPlan(object):
         N, H, W = self._last
         b = self.buffers(N, H, W)
         accumulate_in_place = flat.begin_backward()
-        from segnb import engine as _engine
-        _engine.DW_OVERWRITE = not accumulate_in_place           # (reset by backward(): see ConvOp._arm_target)
+        with rt.weight_grads(store=not accumulate_in_place):     # (stored or added: ConvOp._arm_target; part of the list's key)
+            return self._backward_lists(dlogits, b, N, H, W, accumulate_in_place)
+
+    def _backward_lists(self, dlogits, b, N, H, W, accumulate_in_place):
+        rt, flat, wp = self.rt, self.flat, self.wp
         drop_now = {n: self.stages[n][1]._saved[2] if self.stages[n][1]._saved is not None else None for n in ENCODER + DECODER}
         ckey = self._cplan_key('bwd', N, H, W, True, True, drop_now)
         if ckey is not None:

@@ -6,6 +6,7 @@ stream; every FLOP and every byte moved on the hot path happens inside libsegnb_
 code drives any device the ABI backend can address, which is what lets tests check the plan logic
 (buffer wiring, tap tables, channel maps, backward routing) on CPU against an ABI emulator.
 """
+import contextlib
 import os
 
 import numpy as np
@@ -134,6 +135,29 @@ class Runtime(object):
             self.code, self.tdtype = nv.F32, torch.float32
         else:
             raise ValueError('dtype must be bf16 or f32, got %r' % (dtype,))
+        self._stored = None
+
+    @contextlib.contextmanager
+    def weight_grads(self, store):
+        """Opened by a model's backward driver around one backward, right after FlatParams.begin_backward(): store = True when that
+        cleared the flat gradient buffer (no .grad aliased it), so a directly delivered weight gradient may be STORED into a range
+        nothing has written yet (ConvOp._arm_target).  Outside a backward, and with store = False (gradients accumulate in place),
+        every delivery is added."""
+        self._stored = {} if store else None
+        try:
+            yield
+        finally:
+            self._stored = None
+
+    def first_delivery(self, grad_w, lo, hi):
+        """True when input channels [lo, hi) of grad_w are delivered to for the first time in a storing backward; every delivery
+        is noted, so a later one that overlaps it (a weight used at two call sites) is added."""
+        if self._stored is None:
+            return False
+        seen = self._stored.setdefault(grad_w.data_ptr(), [])
+        first = all(hi <= a or b <= lo for a, b in seen)
+        seen.append((lo, hi))
+        return first
 
     @property
     def stream(self):
@@ -258,12 +282,6 @@ def vptr(v):
 
 def vld(v):
     return 0 if v is None else v.ld
-
-
-# Set by a model's backward driver for the duration of one backward: True when FlatParams.begin_backward() cleared the flat
-# gradient buffer (no .grad aliased it), i.e. every directly delivered weight gradient may be STORED; False (the default, and
-# whenever gradients accumulate in place across backward calls) = added.  Part of the recorded backward lists' keys.
-DW_OVERWRITE = False
 
 
 class ConvOp(object):
@@ -686,7 +704,8 @@ class ConvOp(object):
 
     def wgrad_tf(self, xv, tfx, dv, tfd, grad_w=None):
         """weight gradient with x = tfx(xv) and dy = tfd(dv) (either transform may be None); the result is left in the
-        packed workspace for the batched unpack, like wgrad(..., unpack=False), or delivered into grad_w (direct_ok)"""
+        packed workspace (slab 0), or delivered into grad_w (direct_ok).  grad_w None on a direct_ok op also leaves it in the
+        workspace -- for a caller that reads it there: unpack_jobs() has no job for such an op, so a backward passes grad_w"""
         p, rt = self.plan(xv.H, xv.W), self.rt
         l = p['fwd'][0]
         g = self._geom(p, 'f', 0, l, xv.N, xv.H, xv.W, self.Cip, xv.ld, dv.H, dv.W, self.Cop, dv.ld)
@@ -724,13 +743,14 @@ class ConvOp(object):
 
     def wgrad_bnapply(self, xv, gv, yv, coef, bcoef, act, slope, grad_w=None):
         """the weight gradient with dy = BatchNorm-backward apply of (gv, yv); result left in the packed workspace, or delivered
-        into grad_w (direct_ok)"""
+        into grad_w (direct_ok: required, as for wgrad_tf)"""
+        assert grad_w is not None or not self.direct_ok(), 'a directly delivering op needs grad_w'
         p, rt = self.plan(xv.H, xv.W), self.rt
         l = p['fwd'][0]
         g = self._geom(p, 'f', 0, l, xv.N, xv.H, xv.W, self.Cip, xv.ld, yv.H, yv.W, self.Cop, yv.ld)
 
         def launch():
-            if self.direct_ok() and grad_w is not None:
+            if self.direct_ok():
                 self._arm_target(p, 0, grad_w)
             nv.call('segnb_conv_wgrad_bnapply', g, rt.code, xv.ptr, gv.ptr, gv.ld, yv.ptr, yv.ld, nv.ptr(coef), nv.ptr(bcoef),
                     self.Cop, act, slope, nv.ptr(p['dwp'][0]), p['nslab'][0], rt.stream)
@@ -752,11 +772,14 @@ class ConvOp(object):
 
     def _arm_target(self, p, li, grad_w):
         """segnb_wgrad_target_arm for forward launch li: the next weight-gradient call adds its result to grad_w (the fp32
-        gradient of the whole parameter, reference layout [Co][Ci_total][KH][KW]) -- or STORES it when the backward that is
-        running said the flat gradient buffer holds fresh zeros (DW_OVERWRITE: 0 + x == x, so the read half of the
-        read-modify-write -- a dependent round trip per output row of the delivering kernels -- is dropped; a forward
-        convolution has exactly one weight-gradient launch)"""
-        over = bool(DW_OVERWRITE and self.dw_store and len(p['fwd']) == 1)
+        gradient of the whole parameter, reference layout [Co][Ci_total][KH][KW]) -- or STORES it when it is the first delivery
+        into this op's input-channel range of grad_w in a backward that began on a cleared gradient buffer (Runtime.weight_grads:
+        0 + x == x, so the read half of the read-modify-write -- a dependent round trip per output row of the delivering kernels
+        -- is dropped).  Stored only where the forward is one launch (one weight-gradient launch covers the range); a later
+        delivery into an overlapping range -- a weight shared by two call sites -- is added.  UpCatConvOp's segments cover
+        disjoint ranges and each store."""
+        first = self.rt.first_delivery(grad_w, self._ci_offset, self._ci_offset + self.Ci)
+        over = bool(first and self.dw_store and len(p['fwd']) == 1)
         key = ('tgt', li, grad_w.data_ptr(), over)
         t = p.get(key)
         if t is None:
@@ -1739,14 +1762,17 @@ class FlatParams(object):
     # prezero_grads = False (class attribute): the flat gradient buffer is cleared at the start of backward, on the dependent chain (A/B)
     prezero_grads = True
 
-    def prezero(self, rt, forked=False):
-        """(forked: the caller has just made the side stream wait for this one -- no second marker on the main queue)
+    def prezero(self, rt, forked=False, aliased=None):
+        """(forked: the caller has just made the side stream wait for this one -- no second marker on the main queue; aliased: the
+        caller's grads_alias() of this forward, None = ask here)
         Called by a differentiated training forward: when the coming backward will have to clear the flat gradient buffer
         (no .grad aliases it: zero_grad()'s default, torch_train.py:180), clear it NOW on the side stream -- idle during the
         forward -- behind everything issued so far (the optimizer step / logging that read the last gradients).  126 MB for
         ZF_UNET: 18 us off the start of every backward."""
         self._prezeroed = None
-        if not self.prezero_grads or self.flat_g is None or self.flat_g.device.type != 'cuda' or self.grads_alias():
+        if not self.prezero_grads or self.flat_g is None or self.flat_g.device.type != 'cuda':
+            return
+        if aliased if aliased is not None else self.grads_alias():
             return
         side = rt.side_stream()
         if side is None:

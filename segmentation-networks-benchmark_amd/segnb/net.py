@@ -1173,14 +1173,18 @@ class HipNet(nn.Module):
     # dropout pools are redrawn in Tape.begin, BatchNorm statistics are cleared by the kernels that consume them.
     use_cplan = os.environ.get('SEGNB_CPLAN', '1') != '0'
 
-    def _plan_key(self, x, need_grad):
+    def _plan_key(self, x, need_grad, grads_alias):
+        """grads_alias: FlatParams.grads_alias() at this forward (None without grad).  A backward may only meet it turned False
+        (.grad re-aliases flat_g in publish_grads, at the end of a backward), so a list recorded storing its weight gradients
+        (Runtime.weight_grads) always replays on a cleared buffer; one recorded adding them is right either way."""
         from . import engine
         tape = self._tape
         rt = tape.rt
         if not self.use_cplan or rt.device.type != 'cuda' or engine.TIMER is not None:
             return None
         side = rt.side_stream()
-        return (tuple(x.shape), x.dtype, bool(self.training), bool(need_grad), rt.stream, side.cuda_stream if side is not None else 0,
+        return (tuple(x.shape), x.dtype, bool(self.training), bool(need_grad), grads_alias, rt.stream,
+                side.cuda_stream if side is not None else 0,
                 tape.flat.flat_p.data_ptr(), tape.flat.flat_g.data_ptr(), tuple(b.data_ptr() for b in tape.flat.buffer_list()),
                 tuple(sorted((p, pool['used']) for p, pool in tape._drop_pools.items())) if self.training else (),
                 tape._ready_hook() is not None)
@@ -1211,13 +1215,15 @@ class HipNet(nn.Module):
     def _run_(self, x, need_grad):
         tape = self._tape
         tape.begin(self.training, need_grad)
+        self._grads_alias = tape.flat.grads_alias() if need_grad else None
         if self.training and need_grad:
-            tape.flat.prezero(tape.rt)          # the coming backward's gradient-buffer clear, on the side stream beside the forward
+            # the coming backward's gradient-buffer clear, on the side stream beside the forward
+            tape.flat.prezero(tape.rt, aliased=self._grads_alias)
         if x.dtype == torch.uint8:
             N, H, W, C = x.shape
         else:
             N, C, H, W = x.shape
-        key = self._plan_key(x, need_grad)
+        key = self._plan_key(x, need_grad, self._grads_alias)
         ent, recording = None, False
         self._plan_live = None
         # the batch enters through ONE launch outside the recorded list (it reads the caller's tensor, whatever its address):
@@ -1266,11 +1272,7 @@ class HipNet(nn.Module):
 
     def _run_backward(self, dlogits):
         self._guard_mode, self._guard_active = (None, None), False
-        from . import engine as _engine
-        try:
-            out = self._run_backward_(dlogits)
-        finally:
-            _engine.DW_OVERWRITE = False
+        out = self._run_backward_(dlogits)
         self._guards()[1].end(self._guard_active, *self._guard_mode)
         return out
 
@@ -1284,16 +1286,16 @@ class HipNet(nn.Module):
         self._plan_live = None
         acc = tape.flat.begin_backward()
         # directly delivered weight gradients are STORED when the gradient buffer was just cleared, ADDED when gradients accumulate in
-        # place (engine.DW_OVERWRITE); the recorded backward lists carry the flag they were recorded under
-        from . import engine as _engine
-        _engine.DW_OVERWRITE = not acc
-        # a list recorded with STORES replayed by a backward that accumulates on top of earlier gradients: the fresh gradient goes to a
-        # cleared buffer and the earlier one is added back (rare: lib/train_utils.find_optimal_lr never zeroes; a list recorded with
-        # ADDS is right either way)
-        stash = None
-        if ent is not None and ent['state'] == 'ready' and acc and ent.get('acc') is False:
-            stash = tape.flat.flat_g.clone()
-            tape.flat.flat_g.zero_()
+        # place -- and added when the forward saw .grad aliasing flat_g, so that the list this backward may record matches its key
+        # (_plan_key)
+        with tape.rt.weight_grads(store=not acc and not self._grads_alias):
+            self._backward_lists(tape, ent, dlogits)
+        hook = getattr(self, '_grad_sync_hook', None)
+        if hook is not None:
+            hook(tape.flat)
+        tape.flat.publish_grads(acc)
+
+    def _backward_lists(self, tape, ent, dlogits):
         if ent is not None:
             din = ent.get('dlogits_in')
             if din is None:
@@ -1360,14 +1362,8 @@ class HipNet(nn.Module):
                     self._plan_drop(ent)
                     ent['state'] = 'eager'
                 else:
-                    ent.update(bwd=[(h, c) for h, _, c in segs], nbwd=sum(n for _, n, _ in segs), state='ready', acc=acc)
+                    ent.update(bwd=[(h, c) for h, _, c in segs], nbwd=sum(n for _, n, _ in segs), state='ready')
                     self._guard_mode = (id(ent), 'record')
             table = tape.finish()                                           # (7x7 / strided jobs take host tap arrays: eager)
             if recording and ent['state'] == 'ready':
                 ent['unpack'] = table
-        if stash is not None:
-            tape.flat.flat_g.add_(stash)
-        hook = getattr(self, '_grad_sync_hook', None)
-        if hook is not None:
-            hook(tape.flat)
-        tape.flat.publish_grads(acc)

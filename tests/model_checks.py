@@ -566,3 +566,63 @@ def check_executor_fused_reduce(device, size=32):
     gmax = max(float(g.abs().max()) for g in gb.values())
     for n in gb:
         assert float((ga[n] - gb[n]).abs().max()) <= 2e-2 * max(float(gb[n].abs().max()), 1e-3 * gmax), n
+
+
+def check_weight_shared_by_two_call_sites(device, zeroed_steps=1, accumulating_steps=1, size=32):
+    """segnb.net: one nn.Conv2d applied at two call sites (conv -> ReLU, twice, with the same weight), bf16.  Each site
+    has its own ConvOp, both deliver into the same weight gradient: the first delivery of a backward that cleared the gradient
+    buffer may be stored, the second must be added (ConvOp._arm_target).  The shared weight's gradient against torch autograd of
+    the same net in fp32 (oracle loss, on the host), after `zeroed_steps` steps with zero_grad() (on the GPU: eager, recorded,
+    replayed) and then after each of `accumulating_steps` steps without it (k times the single gradient)."""
+    import torch.nn.functional as F
+    from torch import nn
+    from segnb import net as _net
+    from segnb import _native as nv
+    from segnb import convplan as cp
+    from lib.losses import BCEWithLogitsLossAndSmoothJaccard
+
+    class Shared(_net.HipNet):
+        def __init__(self):
+            super(Shared, self).__init__()
+            self.c1, self.c2 = nn.Conv2d(3, 32, 3, padding=1), nn.Conv2d(32, 32, 3, padding=1)
+            self.final = nn.Conv2d(32, 1, 1)
+            self._init_engine(3)
+
+        def _build(self, tape, x, dlogits):
+            a1 = _net.conv_unit(tape, x, self.c1.weight, self.c1.bias, [(3, cp.pad8(3))], act=nv.ACT_RELU, tag='c1')
+            a2 = _net.conv_unit(tape, a1, self.c2.weight, self.c2.bias, [(32, 32)], act=nv.ACT_RELU, tag='c2a')
+            a3 = _net.conv_unit(tape, a2, self.c2.weight, self.c2.bias, [(32, 32)], act=nv.ACT_RELU, tag='c2b')
+            return _net.head_1x1(tape, a3, self.final.weight, self.final.bias, dlogits)
+
+    def reference(ps, x):
+        def unit(t, c):
+            return F.relu(F.conv2d(t, ps[c + '.weight'], ps[c + '.bias'], padding=1))
+        t = unit(unit(unit(x, 'c1'), 'c2'), 'c2')
+        return F.conv2d(t, ps['final.weight'], ps['final.bias'])
+
+    crit = BCEWithLogitsLossAndSmoothJaccard()
+    gen = torch.Generator().manual_seed(5)
+    B = 2
+    x = torch.randn(B, 3, size, size, generator=gen)
+    y = (torch.rand(B, 1, size, size, generator=gen) > 0.6).long()
+    torch.manual_seed(13)
+    m = Shared().train()
+    ps = {n: p.detach().clone().requires_grad_() for n, p in m.named_parameters()}
+    # (the oracle's loss: lib.losses runs the library's loss kernels, which take device tensors only)
+    (B * losses_ref.bce_jaccard(reference(ps, x), y)).backward()
+    ref = ps['c2.weight'].grad
+    m = m.to(device)
+    xd, yd = x.to(device), y.to(device)
+
+    def step():
+        (B * crit(m(xd), yd)).backward()
+        return m.c2.weight.grad.detach().cpu().clone()
+    for k in range(zeroed_steps):
+        m.zero_grad()
+        got = step()
+        rel = float((got - ref).abs().max() / ref.abs().max())
+        assert rel < 2e-2, ('zeroed step', k, rel)
+    for k in range(2, 2 + accumulating_steps):
+        got = step()                    # no zero_grad: every .grad aliases the flat buffer and is accumulated into
+        rel = float((got - k * ref).abs().max() / (k * ref).abs().max())
+        assert rel < 2e-2, ('accumulated', k, rel)

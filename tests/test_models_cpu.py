@@ -296,3 +296,7 @@ def test_frozen_parameters_keep_grad_none():
         p.requires_grad = False
     out = m(x)
     assert not out.requires_grad
+
+
+def test_weight_shared_by_two_call_sites():
+    mc.check_weight_shared_by_two_call_sites('cpu', zeroed_steps=1, accumulating_steps=1)

@@ -492,3 +492,9 @@ def test_find_optimal_lr_gpu():
     # trajectory amplifies that noise (random-init net, batch of 2): bounded relative to the loss
     np.testing.assert_allclose(loss[:14], ref[:14], rtol=0, atol=2e-5)
     np.testing.assert_allclose(loss[14:], ref[14:], rtol=2e-2, atol=0)
+
+
+def test_weight_shared_by_two_call_sites():
+    """One nn.Conv2d at two call sites of a HipNet: its gradient is delivered twice per backward, stored once and added once.
+    Three zeroed steps (eager, recorded, replayed), then two accumulating ones, each against torch autograd in fp32."""
+    mc.check_weight_shared_by_two_call_sites('cuda', zeroed_steps=3, accumulating_steps=2)

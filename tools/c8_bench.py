@@ -43,7 +43,7 @@ def main():
         'apply pass (g, y -> dz)': lambda: nv.call('segnb_bn_bwd_apply_direct', rt.code, yv.ptr, yv.ld, N, H, W, Cp, nv.ptr(coef),
                                                    nv.ptr(bcoef), nv.ACT_RELU, 0.0, gv.ptr, gv.ld, dz.ptr, dz.ld, None, Co, rt.stream),
         'wgrad on stored dz': lambda: op.wgrad(xv, dz, gw, unpack=False),
-        'wgrad recomputing dz': lambda: op.wgrad_bnapply(xv, gv, yv, coef, bcoef, nv.ACT_RELU, 0.0),
+        'wgrad recomputing dz': lambda: op.wgrad_bnapply(xv, gv, yv, coef, bcoef, nv.ACT_RELU, 0.0, grad_w=gw),
     }
     for name, fn in fns.items():
         fn()
