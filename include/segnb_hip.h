@@ -603,8 +603,10 @@ int segnb_conv_fprop_bnreduce(const segnb_conv_geom* g, int dtype, const void* i
                               const segnb_bn_reduce_epilogue* ep, segnb_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
- * 1x1 classifier head with a handful of classes (zf_unet.py:58,93; tiramisu.py:162; unet16.py:111):
- * fp32 NCHW logits out, fp32 NCHW dlogits in.
+ * 1x1 classifier head with up to 32 classes (zf_unet.py:58,93; tiramisu.py:162; unet16.py:111):
+ * fp32 NCHW logits out, fp32 NCHW dlogits in.  K = 1 .. 8 run one register set of classes; K = 9 .. 32 run the
+ * 16 / 32-class forward instantiations and a backward over class chunks of 8 (dw / db rows summed by the same
+ * reproducible finish pass).
  * ------------------------------------------------------------------------------------------- */
 int segnb_head_fwd(int dtype, const void* a, int ld_a, int N, int H, int W, int C, const float* w,
                    const float* bias, int K, float* logits, segnb_stream_t stream);

@@ -11,12 +11,13 @@
 
 namespace {
 
-constexpr int MAXK = 8;  // classes handled by the direct head kernels
+constexpr int MAXK = 8;        // classes handled by the direct head kernels in one register set
+constexpr int HEAD_MAXK = 32;  // classes of segnb_head_fwd / _bwd: 9 .. 32 run the class-chunked instantiations
 
 // ------------------------------------------------------------------------------------------------
 // head forward: one thread per pixel, weights in LDS
 // ------------------------------------------------------------------------------------------------
-template <typename T>
+template <typename T, int KM = MAXK>
 __global__ __launch_bounds__(256) void head_fwd_kernel(const T* __restrict__ a, int ld_a, long long npix,
                                                        long long hw, int C, const float* __restrict__ w,
                                                        const float* __restrict__ bias, int K,
@@ -30,14 +31,14 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const T* __restrict__ a, 
     __syncthreads();
     for (long long pix = blockIdx.x * (long long)blockDim.x + threadIdx.x; pix < npix;
          pix += (long long)gridDim.x * blockDim.x) {
-        float acc[MAXK];
+        float acc[KM];
 #pragma unroll
-        for (int k = 0; k < MAXK; ++k) acc[k] = 0.f;
+        for (int k = 0; k < KM; ++k) acc[k] = 0.f;
         for (int c0 = 0; c0 < C8; c0 += 8) {
             float v[8];
             load8(a + pix * ld_a + c0, v);
 #pragma unroll
-            for (int k = 0; k < MAXK; ++k)
+            for (int k = 0; k < KM; ++k)
                 if (k < K) {
 #pragma unroll
                     for (int e = 0; e < 8; ++e) acc[k] = fmaf(v[e], sw[k * C8 + c0 + e], acc[k]);
@@ -45,7 +46,7 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const T* __restrict__ a, 
         }
         const long long n = pix / hw, r = pix - n * hw;
 #pragma unroll
-        for (int k = 0; k < MAXK; ++k)
+        for (int k = 0; k < KM; ++k)
             if (k < K) logits[(n * K + k) * hw + r] = acc[k] + (bias != nullptr ? bias[k] : 0.f);
     }
 }
@@ -193,6 +194,94 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const T* __restrict__ a, 
                 float sum = 0.f;
                 for (int j = 0; j < PY; ++j) sum += sg[j];
                 prow[k * (CT * 8 + 1) + CT * 8] = sum;
+            }
+        }
+}
+
+// head backward for 9 .. 32 classes: head_bwd_kernel's mapping and partial-sum rows, the classes in chunks of MAXK along
+// gridDim.z (the per-class register arrays of 32 classes would leave one wave per SIMD).  Block z accumulates dw / db of classes
+// 8 z .. 8 z + 7 into its rows' class slots; the z == 0 blocks also write da, summing all K classes with the block's weight
+// slice in LDS.  The finish kernel is head_bwd_finish_kernel, unchanged.
+template <typename T>
+__global__ __launch_bounds__(256) void head_bwd_many_kernel(const T* __restrict__ a, int ld_a, long long npix, long long hw, int C,
+                                                            int Cp, const float* __restrict__ w, int K,
+                                                            const float* __restrict__ dl, T* __restrict__ da, int ld_da,
+                                                            float* __restrict__ part, int CT) {
+    extern __shared__ float swk[];                      // [K][CT * 8]: the weights of this block's channel slice
+    __shared__ float sred[256 * 8];
+    const int PY = 256 / CT;
+    const int tx = threadIdx.x % CT, ty = threadIdx.x / CT;
+    const int cc = blockIdx.y * CT + tx;
+    const bool active = cc * 8 < Cp;
+    const int c0 = active ? cc * 8 : 0;
+    const int k0 = blockIdx.z * MAXK;
+    const bool do_da = da != nullptr && blockIdx.z == 0;
+    for (int i = threadIdx.x; i < K * CT * 8; i += 256) {
+        const int k = i / (CT * 8), c = blockIdx.y * CT * 8 + (i - k * CT * 8);
+        swk[i] = c < C ? w[k * C + c] : 0.f;
+    }
+    __syncthreads();
+    float gw[MAXK][8], gb[MAXK];
+#pragma unroll
+    for (int k = 0; k < MAXK; ++k) {
+        gb[k] = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) gw[k][e] = 0.f;
+    }
+    if (active) {
+        const int stride = gridDim.x * PY;
+        for (int pix = blockIdx.x * PY + ty; pix < (int)npix; pix += stride) {     // npix < 2^30 (checked)
+            float av[8];
+            load8(a + (long long)pix * ld_a + c0, av);
+            const int n = pix / (int)hw, r = pix - n * (int)hw;
+            const float* dlp = dl + (long long)n * K * hw + r;
+#pragma unroll
+            for (int k = 0; k < MAXK; ++k)
+                if (k0 + k < K) {
+                    const float gk = dlp[(long long)(k0 + k) * hw];
+                    gb[k] += gk;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) gw[k][e] = fmaf(gk, av[e], gw[k][e]);
+                }
+            if (do_da) {
+                float d[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) d[e] = 0.f;
+                for (int k = 0; k < K; ++k) {
+                    const float gk = dlp[(long long)k * hw];
+                    const float4 w0 = *reinterpret_cast<const float4*>(swk + k * CT * 8 + tx * 8);
+                    const float4 w1 = *reinterpret_cast<const float4*>(swk + k * CT * 8 + tx * 8 + 4);
+                    d[0] = fmaf(gk, w0.x, d[0]); d[1] = fmaf(gk, w0.y, d[1]);
+                    d[2] = fmaf(gk, w0.z, d[2]); d[3] = fmaf(gk, w0.w, d[3]);
+                    d[4] = fmaf(gk, w1.x, d[4]); d[5] = fmaf(gk, w1.y, d[5]);
+                    d[6] = fmaf(gk, w1.z, d[6]); d[7] = fmaf(gk, w1.w, d[7]);
+                }
+                store8(da + (long long)pix * ld_da + c0, d);
+            }
+        }
+    }
+    // reproducible reduction: as head_bwd_kernel, into the class slots k0 .. k0 + 7 of this block's row
+    float* sg = sred;
+    float* prow = part + (long long)(blockIdx.y * gridDim.x + blockIdx.x) * (K * (CT * 8 + 1));
+#pragma unroll
+    for (int k = 0; k < MAXK; ++k)
+        if (k0 + k < K) {
+            __syncthreads();
+#pragma unroll
+            for (int e = 0; e < 8; ++e) sg[(ty * CT + tx) * 8 + e] = gw[k][e];
+            __syncthreads();
+            if (threadIdx.x < CT * 8) {
+                float sum = 0.f;
+                for (int j = 0; j < PY; ++j) sum += sg[j * CT * 8 + threadIdx.x];
+                prow[(k0 + k) * (CT * 8 + 1) + threadIdx.x] = sum;
+            }
+            __syncthreads();
+            if (tx == 0) sg[ty] = gb[k];
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                float sum = 0.f;
+                for (int j = 0; j < PY; ++j) sum += sg[j];
+                prow[(k0 + k) * (CT * 8 + 1) + CT * 8] = sum;
             }
         }
 }
@@ -733,7 +822,7 @@ extern "C" int segnb_head_fwd(int dtype, const void* a, int ld_a, int N, int H, 
                               const float* bias, int K, float* logits, segnb_stream_t stream) {
     SEGNB_PLAN_RECORD(segnb_head_fwd, dtype, a, ld_a, N, H, W, C, w, bias, K, logits, stream);
     SEGNB_CHECK_ARG(a && w && logits, "NULL tensor");
-    SEGNB_CHECK_ARG(K >= 1 && K <= MAXK, "head supports 1..8 classes");
+    SEGNB_CHECK_ARG(K >= 1 && K <= HEAD_MAXK, "head supports 1..32 classes");
     SEGNB_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && ld_a % 8 == 0 && ld_a >= ((C + 7) & ~7), "bad shape");
     const long long npix = (long long)N * H * W;
     if (C > 64) {
@@ -747,11 +836,15 @@ extern "C" int segnb_head_fwd(int dtype, const void* a, int ld_a, int N, int H, 
         const size_t wsm = (size_t)K * cpp * 8 * sizeof(float);
         SEGNB_CHECK_ARG(wsm <= 48 * 1024, "head: K * C too large");
         if (dtype == SEGNB_BF16)
-            (K == 1 ? head_fwd_wide_kernel<bf16_t, 1> : head_fwd_wide_kernel<bf16_t, MAXK>)<<<dim3((unsigned)gx), dim3(256), wsm, (hipStream_t)stream>>>(
-                (const bf16_t*)a, ld_a, npix, (long long)H * W, C, w, bias, K, logits, ct);
+            (K == 1 ? head_fwd_wide_kernel<bf16_t, 1> : K <= MAXK ? head_fwd_wide_kernel<bf16_t, MAXK>
+                                                    : K <= 16 ? head_fwd_wide_kernel<bf16_t, 16> : head_fwd_wide_kernel<bf16_t, HEAD_MAXK>)
+                <<<dim3((unsigned)gx), dim3(256), wsm, (hipStream_t)stream>>>((const bf16_t*)a, ld_a, npix, (long long)H * W, C, w, bias, K,
+                                                                             logits, ct);
         else if (dtype == SEGNB_F32)
-            (K == 1 ? head_fwd_wide_kernel<float, 1> : head_fwd_wide_kernel<float, MAXK>)<<<dim3((unsigned)gx), dim3(256), wsm, (hipStream_t)stream>>>(
-                (const float*)a, ld_a, npix, (long long)H * W, C, w, bias, K, logits, ct);
+            (K == 1 ? head_fwd_wide_kernel<float, 1> : K <= MAXK ? head_fwd_wide_kernel<float, MAXK>
+                                                   : K <= 16 ? head_fwd_wide_kernel<float, 16> : head_fwd_wide_kernel<float, HEAD_MAXK>)
+                <<<dim3((unsigned)gx), dim3(256), wsm, (hipStream_t)stream>>>((const float*)a, ld_a, npix, (long long)H * W, C, w, bias, K,
+                                                                             logits, ct);
         else {
             segnb_set_error("segnb_head_fwd: unknown dtype %d", dtype);
             return SEGNB_E_BADARG;
@@ -763,11 +856,17 @@ extern "C" int segnb_head_fwd(int dtype, const void* a, int ld_a, int N, int H, 
     if (grid > 4096) grid = 4096;
     const int smem = K * ((C + 7) & ~7) * 4;
     SEGNB_CHECK_ARG(smem <= 60 * 1024, "head too wide");
-    if (dtype == SEGNB_BF16)
+    if (dtype == SEGNB_BF16 && K <= MAXK)
         hipLaunchKernelGGL(head_fwd_kernel<bf16_t>, dim3(grid), dim3(256), smem, (hipStream_t)stream,
                            (const bf16_t*)a, ld_a, npix, (long long)H * W, C, w, bias, K, logits);
-    else if (dtype == SEGNB_F32)
+    else if (dtype == SEGNB_F32 && K <= MAXK)
         hipLaunchKernelGGL(head_fwd_kernel<float>, dim3(grid), dim3(256), smem, (hipStream_t)stream, (const float*)a,
+                           ld_a, npix, (long long)H * W, C, w, bias, K, logits);
+    else if (dtype == SEGNB_BF16)        // 9 .. 32 classes
+        hipLaunchKernelGGL((head_fwd_kernel<bf16_t, HEAD_MAXK>), dim3(grid), dim3(256), smem, (hipStream_t)stream,
+                           (const bf16_t*)a, ld_a, npix, (long long)H * W, C, w, bias, K, logits);
+    else if (dtype == SEGNB_F32)
+        hipLaunchKernelGGL((head_fwd_kernel<float, HEAD_MAXK>), dim3(grid), dim3(256), smem, (hipStream_t)stream, (const float*)a,
                            ld_a, npix, (long long)H * W, C, w, bias, K, logits);
     else {
         segnb_set_error("segnb_head_fwd: unknown dtype %d", dtype);
@@ -842,7 +941,7 @@ extern "C" int segnb_head_bwd(int dtype, const void* a, int ld_a, int N, int H, 
                               float* db, segnb_stream_t stream) {
     SEGNB_PLAN_RECORD(segnb_head_bwd, dtype, a, ld_a, N, H, W, C, Cp, w, K, dlogits, da, ld_da, dw, db, stream);
     SEGNB_CHECK_ARG(a && w && dlogits, "NULL tensor");
-    SEGNB_CHECK_ARG(K >= 1 && K <= MAXK, "head supports 1..8 classes");
+    SEGNB_CHECK_ARG(K >= 1 && K <= HEAD_MAXK, "head supports 1..32 classes");
     SEGNB_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && Cp % 8 == 0 && Cp >= C, "bad shape");
     const long long npix = (long long)N * H * W;
     SEGNB_CHECK_ARG(npix < (1ll << 30), "pixel count exceeds the 32-bit index range");
@@ -863,7 +962,17 @@ extern "C" int segnb_head_bwd(int dtype, const void* a, int ld_a, int N, int H, 
     // per (device, stream), grown on demand
     float* part = head_scratch((size_t)gx * gy * K * (ct * 8 + 1) * sizeof(float), (hipStream_t)stream);
     if (part == nullptr) return SEGNB_E_BADARG;
-    if (dtype == SEGNB_BF16)
+    if (K > MAXK) {
+        // 9 .. 32 classes: class chunks of MAXK along z, the weight slice [K][ct * 8] in LDS (32 KB at most)
+        const dim3 gridz((unsigned)gx, (unsigned)gy, (unsigned)ceil_div(K, MAXK));
+        const size_t wsm = (size_t)K * ct * 8 * sizeof(float);
+        if (dtype == SEGNB_BF16)
+            head_bwd_many_kernel<bf16_t><<<gridz, dim3(256), wsm, (hipStream_t)stream>>>(
+                (const bf16_t*)a, ld_a, npix, (long long)H * W, C, Cp, w, K, dlogits, (bf16_t*)da, ld_da, part, ct);
+        else
+            head_bwd_many_kernel<float><<<gridz, dim3(256), wsm, (hipStream_t)stream>>>(
+                (const float*)a, ld_a, npix, (long long)H * W, C, Cp, w, K, dlogits, (float*)da, ld_da, part, ct);
+    } else if (dtype == SEGNB_BF16)
         (K == 1 ? head_bwd_kernel<bf16_t, 1> : head_bwd_kernel<bf16_t, MAXK>)<<<grid, dim3(256), 0, (hipStream_t)stream>>>(
             (const bf16_t*)a, ld_a, npix, (long long)H * W, C, Cp, w, K, dlogits, (bf16_t*)da, ld_da, part, ct);
     else

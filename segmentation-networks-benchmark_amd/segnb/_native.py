@@ -198,6 +198,25 @@ SIGNATURES = {
 }
 PLAIN = {'segnb_version': (c_int, []), 'segnb_pack_pair_job_bytes': (c_int, []), 'segnb_pack_pair_job_blocks': (c_int, [c_int, c_int, c_int, c_int]), 'segnb_pack_elem_job_blocks': (c_int, [c_int, c_int, c_int]), 'segnb_bias_grad_job_bytes': (c_int, []), 'segnb_head_fused_ok': (c_int, [c_int, c_int]), 'segnb_head_conv_ok': (c_int, [c_int, c_int, c_int, c_int]), 'segnb_conv_fprop_tf_ok': (c_int, [ctypes.POINTER(ConvGeom), c_int, c_int]), 'segnb_conv_wgrad_tf_ok': (c_int, [ctypes.POINTER(ConvGeom), c_int]), 'segnb_conv_fprop_bnreduce_ok': (c_int, [ctypes.POINTER(ConvGeom), c_int]), 'segnb_conv_fprop_actmask_ok': (c_int, [ctypes.POINTER(ConvGeom), c_int]), 'segnb_conv_fprop_drop_ok': (c_int, [ctypes.POINTER(ConvGeom), c_int]), 'segnb_conv_fprop_bnapply_ok': (c_int, [ctypes.POINTER(ConvGeom), c_int]), 'segnb_conv_fprop_u8_ok': (c_int, [ctypes.POINTER(ConvGeom), c_int]), 'segnb_conv_fprop_upd_ok': (c_int, [ctypes.POINTER(ConvGeom), c_int]), 'segnb_conv_upcat_ok': (c_int, [ctypes.POINTER(ConvGeom), c_int, c_int]), 'segnb_conv_fprop_upsum_ok': (c_int, [ctypes.POINTER(ConvGeom), c_int, c_int]), 'segnb_conv_wgrad_bnapply_ok': (c_int, [ctypes.POINTER(ConvGeom), c_int]), 'segnb_upconv_fprop_acc_ok': (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]), 'segnb_upconv_fprop_ok': (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]), 'segnb_conv_wgrad_slabs': (c_int, [ctypes.POINTER(ConvGeom), c_int]), 'segnb_pack_job_bytes': (c_int, []), 'segnb_pack_job_blocks': (c_int, [c_int, c_int, c_int, c_ll, c_ll]), 'segnb_device_cus': (c_int, []), 'segnb_last_error': (ctypes.c_char_p, [])}
 
+
+
+class McLossSpec(ctypes.Structure):
+    """segnb_mc_loss_spec (include/segnb_mc_loss.h)"""
+    _fields_ = [('C', c_int), ('mode', c_int), ('ignore_index', c_ll), ('gamma', c_float), ('w_focal', c_float),
+                ('w_nll', c_float), ('w_jaccard', c_float), ('norm', c_float), ('focal_mean', c_int), ('reduce', c_int),
+                ('reserved', c_int), ('nll_weight', c_void_p), ('jac_weight', c_void_p)]
+
+
+# the multi-class loss family, declared in include/segnb_mc_loss.h (a header of its own: SIGNATURES | PLAIN is exactly
+# include/segnb_hip.h)
+MC_SIGNATURES = {
+    'segnb_mc_loss_reduce': [_P, _P, c_int, c_int, ctypes.POINTER(McLossSpec), _P, _P, _P],
+    'segnb_mc_loss_finalize': [_P, ctypes.POINTER(McLossSpec), _P, _P],
+    'segnb_mc_loss_reduce_finalize': [_P, _P, c_int, c_int, ctypes.POINTER(McLossSpec), _P, _P, _P],
+    'segnb_mc_loss_bwd': [_P, _P, c_int, c_int, ctypes.POINTER(McLossSpec), _P, _P, _P, _P],
+}
+MC_PLAIN = {'segnb_mc_loss_work_doubles': (c_int, [c_int])}
+
 _lib = None
 _test_backend = None
 
@@ -221,11 +240,11 @@ def load():
     # anything imported torch.  With torch's runtime already loaded the dynamic linker resolves this library's HIP symbols to it.
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in SIGNATURES.items():
+    for name, argtypes in list(SIGNATURES.items()) + list(MC_SIGNATURES.items()):
         fn = getattr(lib, name)         # AttributeError if the ABI and the header drift apart
         fn.argtypes = argtypes
         fn.restype = c_int
-    for name, (res, argtypes) in PLAIN.items():
+    for name, (res, argtypes) in list(PLAIN.items()) + list(MC_PLAIN.items()):
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = res
