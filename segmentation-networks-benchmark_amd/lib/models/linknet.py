@@ -54,6 +54,27 @@ def _resnet_layer(inplanes, planes, blocks, stride):
     return nn.Sequential(*layers)
 
 
+def resnet_encoder(tape, h, layers, c=64):
+    """The BasicBlock stages of the ResNet34 encoder (``layers``: the four _resnet_layer stacks) on the executor, from the
+    pooled stem output h (c channels) -> the four stage outputs.  Shared by LinkNet34 and GCN34 (lib.models.gcn)."""
+    feats = []
+    for li, layer in enumerate(layers):
+        for bi, blk in enumerate(layer):
+            tag = 'enc%d.%d' % (li + 1, bi)
+            planes = blk.conv1.out_channels
+            a = conv_unit(tape, h, blk.conv1.weight, None, [(c, cp.pad8(c))], stride=blk.stride, pad=1, bn=blk.bn1,
+                          act=nv.ACT_RELU, tag=tag + '.c1')
+            ident = h
+            if blk.downsample is not None:
+                ident = conv_unit(tape, h, blk.downsample[0].weight, None, [(c, cp.pad8(c))], stride=blk.stride, pad=0,
+                                  bn=blk.downsample[1], act=nv.ACT_NONE, tag=tag + '.ds')
+            h = conv_unit(tape, a, blk.conv2.weight, None, [(planes, cp.pad8(planes))], stride=1, pad=1, bn=blk.bn2,
+                          act=nv.ACT_RELU, res=ident, tag=tag + '.c2')
+            c = planes
+        feats.append(h)
+    return feats
+
+
 class DecoderBlockLinkNet(nn.Module):
     def __init__(self, in_channels, n_filters):
         super(DecoderBlockLinkNet, self).__init__()
@@ -115,22 +136,7 @@ class LinkNet34(HipNet):
         h = conv_unit(tape, x, self.firstconv.weight, None, seg(3), stride=2, pad=3, bn=self.firstbn,
                       act=nv.ACT_RELU, tag='stem')
         h = maxpool(tape, h, 3, 2, 1, tag='stempool')
-        feats, c = [], 64
-        for li, layer in enumerate((self.encoder1, self.encoder2, self.encoder3, self.encoder4)):
-            for bi, blk in enumerate(layer):
-                tag = 'enc%d.%d' % (li + 1, bi)
-                planes = blk.conv1.out_channels
-                a = conv_unit(tape, h, blk.conv1.weight, None, seg(c), stride=blk.stride, pad=1, bn=blk.bn1,
-                              act=nv.ACT_RELU, tag=tag + '.c1')
-                ident = h
-                if blk.downsample is not None:
-                    ident = conv_unit(tape, h, blk.downsample[0].weight, None, seg(c), stride=blk.stride, pad=0,
-                                      bn=blk.downsample[1], act=nv.ACT_NONE, tag=tag + '.ds')
-                h = conv_unit(tape, a, blk.conv2.weight, None, seg(planes), stride=1, pad=1, bn=blk.bn2,
-                              act=nv.ACT_RELU, res=ident, tag=tag + '.c2')
-                c = planes
-            feats.append(h)
-        e1, e2, e3, e4 = feats
+        e1, e2, e3, e4 = resnet_encoder(tape, h, (self.encoder1, self.encoder2, self.encoder3, self.encoder4))
 
         def decoder(blk, inp, cin, tag, dropmul=None):
             mid = cin // 4

@@ -217,6 +217,18 @@ MC_SIGNATURES = {
 }
 MC_PLAIN = {'segnb_mc_loss_work_doubles': (c_int, [c_int])}
 
+# the GCN decoder kernels, declared in include/segnb_gcn.h (csrc/gcn.hip)
+GCN_SIGNATURES = {
+    'segnb_gcm_fwd': [c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    'segnb_gcm_bwd': [c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int,
+                      _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    'segnb_brm_fwd': [c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P],
+    'segnb_brm_bwd': [c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    'segnb_resize_bilinear_ac_fwd': [c_int, c_int, c_int, c_int, _P, c_int, c_int, _P, _P, _P],
+    'segnb_resize_bilinear_ac_bwd': [c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P],
+}
+GCN_PLAIN = {'segnb_gcn_ok': (c_int, [c_int, c_int, c_int, c_int, c_int])}
+
 _lib = None
 _test_backend = None
 
@@ -240,11 +252,11 @@ def load():
     # anything imported torch.  With torch's runtime already loaded the dynamic linker resolves this library's HIP symbols to it.
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in list(SIGNATURES.items()) + list(MC_SIGNATURES.items()):
+    for name, argtypes in list(SIGNATURES.items()) + list(MC_SIGNATURES.items()) + list(GCN_SIGNATURES.items()):
         fn = getattr(lib, name)         # AttributeError if the ABI and the header drift apart
         fn.argtypes = argtypes
         fn.restype = c_int
-    for name, (res, argtypes) in list(PLAIN.items()) + list(MC_PLAIN.items()):
+    for name, (res, argtypes) in list(PLAIN.items()) + list(MC_PLAIN.items()) + list(GCN_PLAIN.items()):
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = res

@@ -47,6 +47,9 @@ def get_model(model_name, patch_size=None, num_channels=3):
     if name == 'linknet34':
         from lib.models.linknet import LinkNet34
         return LinkNet34(pretrained=True, num_channels=num_channels, num_classes=1)
+    if name == 'gcn34':
+        from lib.models.gcn import GCN34
+        return GCN34(input_size=patch_size, num_classes=1)
     if name == 'tiramisu67':
         from lib.models.tiramisu import FCDenseNet67
         return FCDenseNet67(n_classes=1)
