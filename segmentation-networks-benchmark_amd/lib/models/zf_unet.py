@@ -13,6 +13,7 @@ libsegnb_hip.so launches (segnb.engine) -- implicit-GEMM MFMA convolutions with 
 the epilogue, one fused BN+ReLU+Dropout2d+MaxPool/Upsample pass per conv writing straight into the
 decoder's concat buffers (no torch.cat), hand-written backward.
 """
+import contextlib
 import os
 
 import torch
@@ -20,6 +21,7 @@ from torch import nn
 
 from segnb import _native as nv
 from segnb import convplan as cp
+from segnb.launchlist import Recorder
 from segnb.engine import ConvOp, FlatParams, InputNorm, PackTable, Runtime, Stage, UpCatConvOp, View, pack_input
 
 ENCODER = ('conv_224', 'conv_112', 'conv_56', 'conv_28', 'conv_14', 'conv_7')
@@ -307,11 +309,9 @@ class _ZFUnetPlan(object):
             # a recorded launch list is cut where the hook runs, and the hook itself runs OUTSIDE the recording: what it
             # launches (the optimizer update of a bucket behind its all-reduce, DataParallel.fuse_optimizer) is issued by the
             # live hook of every step -- recorded as well, a replay applied those updates twice
-            self._plan_cut(('ready', gi, side is not None), resume=False)
-            try:
+            rec = self._rec
+            with rec.pause((gi, side is not None)) if rec is not None else contextlib.nullcontext():
                 hook(self.flat, los[gi], (side,) if side is not None else ())
-            finally:
-                self._plan_resume()
 
     _last_N = None
 
@@ -424,79 +424,42 @@ class _ZFUnetPlan(object):
                 rt.stream, side.cuda_stream if side is not None else 0, self.flat.flat_p.data_ptr(),
                 self.flat.flat_g.data_ptr(), tuple(p.data_ptr() for p in self.flat.buffer_list()))
 
-    # ---- recorded launch lists (segnb_plan_*) ---------------------------------------------------------------------
-    # A list is a sequence of segments [(handle, launches, mark)]: the data-parallel "gradients ready" hook is host code that
-    # must run BETWEEN launches (it starts an all-reduce behind what has been issued so far), so the recording is cut there
-    # and the replay calls the hook after the segment that ends at the cut.
-    _rec = None
+    # ---- recorded launch lists (segnb.launchlist) -------------------------------------------------------------------
+    # The data-parallel "gradients ready" hook is host code that must run BETWEEN launches (it starts an all-reduce behind
+    # what has been issued so far), so the recording is cut there (_unpack_group) and the replay calls the hook after the
+    # segment that ends at the cut.
+    _rec = None           # the Recorder of the step being recorded
 
-    def _plan_begin(self):
+    @contextlib.contextmanager
+    def _recording(self, ckey):
+        """Record the launches of the body as the list of configuration ckey (None: the body runs eagerly).  A body that
+        raises (e.g. an allocation failure the caller catches) or makes a call that cannot be replayed leaves the
+        configuration remembered as eager: never recorded again."""
+        if ckey is None:
+            yield
+            return
         from segnb import engine
         if engine.TIMER is not None:
             engine.TIMER.persistent = True
-        self._rec = []
-        nv.plan_record_begin()
-
-    def _plan_cut(self, mark, resume=True):
-        if self._rec is not None:
-            handle, nops = nv.plan_record_end()
-            self._rec.append((handle, nops, mark))
-            self._paused = not resume
-            if resume:
-                nv.plan_record_begin()
-
-    _paused = False
-
-    def _plan_resume(self):
-        if self._rec is not None and self._paused:
-            self._paused = False
-            nv.plan_record_begin()
-
-    def _plan_end(self, ckey):
-        handle, nops = nv.plan_record_end()
-        segs, self._rec = self._rec + [(handle, nops, None)], None
-        if any(h is None for h, _, _ in segs):           # a call that cannot be replayed: remembered, never recorded again
-            for h, _, _ in segs:
-                if h is not None:
-                    nv.call('segnb_plan_destroy', h)
-            segs = None
-        self._cplans[ckey] = (segs, self._stage_state(), sum(n for _, n, _ in segs) if segs else 0)
-
-    def _plan_abort(self, ckey):
-        """An exception escaped a step that was being recorded (e.g. an allocation failure the caller catches): close the
-        recording, free its segments and remember the configuration as eager."""
-        if self._rec is None:
-            return
-        segs, self._rec = self._rec, None
-        if not self._paused:
-            nv.plan_record_abort()
-        self._paused = False
-        for h, _, _ in segs:
-            if h is not None:
-                try:
-                    nv.call('segnb_plan_destroy', h)
-                except Exception:
-                    pass
-        self._cplans[ckey] = (None, self._stage_state(), 0)
+        with Recorder() as rec:
+            self._rec, lst = rec, None       # (_unpack_group pauses it around the data-parallel hook)
+            try:
+                yield
+                lst = rec.finish()
+            finally:
+                self._rec = None
+                self._cplans[ckey] = (lst, self._stage_state(), lst.launches if lst else 0)
+        if lst:
+            self._guard_mode = (ckey, 'record')
 
     def _plan_replay(self, plan, H=None, W=None):
-        for handle, _, mark in plan[0]:
-            nv.call('segnb_plan_run', handle)
-            if mark is not None:
-                hook = getattr(self.module, '_grad_ready_hook', None)
-                if hook is not None:
-                    los = self._tables(H, W)[3]
-                    hook(self.flat, los[mark[1]], (self.rt.side_stream(),) if mark[2] else ())
+        def ready(mark):
+            hook = getattr(self.module, '_grad_ready_hook', None)
+            if hook is not None:
+                gi, on_side = mark
+                hook(self.flat, self._tables(H, W)[3][gi], (self.rt.side_stream(),) if on_side else ())
+        plan[0].replay(ready)
         self._restore_stage_state(plan[1])
-
-    def __del__(self):
-        try:                       # recorded lists are owned by this plan: free them with it
-            for plan in self._cplans.values():
-                for handle, _, _ in (plan[0] or ()):
-                    if handle is not None:
-                        nv.call('segnb_plan_destroy', handle)
-        except Exception:          # (interpreter shutdown: the library may be gone already)
-            pass
 
     def _stage_state(self):
         return [(st, st._stats_stale, st._fused_fwd, getattr(st, '_saved', None))
@@ -559,11 +522,9 @@ class _ZFUnetPlan(object):
                 self._last_train = bool(train)
                 self.generation += 1
                 return self._head(b, N, H, W, hf)
-            if plan is None:
-                self._plan_begin()
-            else:
+            if plan is not None:
                 ckey = None                               # recorded before and found not replayable: eager
-        try:
+        with self._recording(ckey):
             wp = self.wp
             cur = b['x']
             for i, name in enumerate(ENCODER):
@@ -597,14 +558,6 @@ class _ZFUnetPlan(object):
                     s2.forward(x2, train, drop[name], need_grad=need_grad, x_tf=tf2, defer_act='head')
                 else:
                     s2.forward(x2, train, drop[name], out=b['f0'], need_grad=need_grad, x_tf=tf2)
-        except BaseException:
-            if ckey is not None:
-                self._plan_abort(ckey)
-            raise
-        if ckey is not None:
-            self._plan_end(ckey)
-            if self._cplans[ckey][0] is not None:
-                self._guard_mode = (ckey, 'record')
         self._last = (N, H, W) if need_grad else None
         self.generation += 1                       # every forward overwrites the activation buffers
         self._last_train = bool(train)
@@ -688,11 +641,9 @@ class _ZFUnetPlan(object):
                 self._after_backward()
                 flat.publish_grads(accumulate_in_place)
                 return [None] * len(flat._off)
-            if plan is None:
-                self._plan_begin()
-            else:
+            if plan is not None:
                 ckey = None
-        try:
+        with self._recording(ckey):
             if self._dg_pack_on_side and rt.side_stream() is not None:
                 # the data gradients' matrices were packed on the side stream (recorded: a replayed list waits too)
                 nv.call('segnb_stream_join', rt.stream, rt.side_stream().cuda_stream)
@@ -740,14 +691,6 @@ class _ZFUnetPlan(object):
                 s1.backward(flat, g_direct=b['da1_%d' % i], dx=(b['dp_%d' % i] if i > 0 else None), reduced=red)
             rt.join_side()                        # the weight gradients ran on the side stream
             self._tables(H, W)[2][2].run()       # the remaining packed weight-gradient workspaces -> flat gradient buffer
-        except BaseException:
-            if ckey is not None:
-                self._plan_abort(ckey)
-            raise
-        if ckey is not None:
-            self._plan_end(ckey)
-            if self._cplans[ckey][0] is not None:
-                self._guard_mode = (ckey, 'record')
         self._after_backward()
         # gradients live in ONE flat buffer; parameter.grad tensors are views of it (installed here, not
         # returned through autograd, so they never get cloned and a flat optimizer / all-reduce can run)

@@ -12,6 +12,7 @@ Gradients of multi-consumer tensors (ResNet identity branches, dense concatenati
 Used by lib.models.{unet16, linknet, tiramisu}; ZF_UNET keeps its hand-scheduled plan (fused pool/upsample
 routing, batched pack/unpack).
 """
+import contextlib
 import os
 
 import numpy as np
@@ -22,6 +23,7 @@ from . import _native as nv
 from . import convplan as cp
 from .engine import (BN_EPS, BN_MOMENTUM, STAT_REPLICAS, ConvOp, FlatParams, InputNorm, PackTable, Runtime, View,
                      pack_input, vld, vptr)
+from .launchlist import Recorder
 
 
 class Act(object):
@@ -130,15 +132,6 @@ class Tape(object):
 
     def note_fused_stats(self, stats):
         self.fused_stats.append(stats)
-
-    def __del__(self):
-        try:                       # recorded launch lists are owned by this tape: free them with it
-            for ent in self.plans.values():
-                for h in [ent.get('fwd')] + [h for h, _ in (ent.get('bwd') or [])]:
-                    if h:
-                        nv.call('segnb_plan_destroy', h)
-        except Exception:          # (interpreter shutdown: the library may be gone already)
-            pass
 
     # ---- per-step bookkeeping ------------------------------------------------------------------------------
     def begin(self, train, need_grad):
@@ -338,9 +331,23 @@ class Tape(object):
         # gradient is the unpack of that layer alone -- measured +-0 on LinkNet34 and UNet16, same box: not kept)
         self._cuts[nback] = cuts
 
+    def cut_host(self, table, lo, on_side, group=None):
+        """Host work at a cut of the backward: the partial unpack (group: of that cut, now; else table.run(), the same launches
+        in a replayed step), on the weight-gradient stream when on_side, then the data-parallel hook.  -> (table, lo, on_side)"""
+        side = self.rt.side_stream() if on_side else None
+        with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
+            if group is not None:
+                table = self.run_unpack(group=group)
+            elif table is not None:
+                table.run()
+        hook = self._ready_hook()
+        if hook is not None:
+            hook(self.flat, lo, (side,) if side is not None else ())
+        return table, lo, on_side
+
     def run_closures(self, around_cut=None, join=True):
-        """around_cut(do): wraps the partial unpack + hook of a cut -- do() performs them and returns (unpack table or None,
-        flat offset, weight-gradient stream in use) -- so that HipNet can cut its recorded launch list there.
+        """around_cut(do): wraps the partial unpack + hook of a cut -- do() performs them and returns what cut_host returns
+        -- so that HipNet can cut its recorded launch list there.
         join=False: the caller joins the weight-gradient stream itself (Tape.finish)."""
         hook = self._ready_hook()
         back = list(reversed(self.back))
@@ -362,15 +369,8 @@ class Tape(object):
                 flat.touch_log = None
             elif cuts and i in cuts and i + 1 < nback:
                 def do(i=i):
-                    side = self.rt.side_stream() if getattr(self.rt, '_side_busy', False) else None
-                    if side is not None:
-                        with torch.cuda.stream(side):
-                            table = self.run_unpack(group=i)
-                    else:
-                        table = self.run_unpack(group=i)
-                    if hook is not None:
-                        hook(self.flat, cuts[i], (side,) if side is not None else ())
-                    return table, cuts[i], side is not None
+                    on_side = getattr(self.rt, '_side_busy', False) and self.rt.side_stream() is not None
+                    return self.cut_host(None, cuts[i], on_side, group=i)
                 if around_cut is not None:
                     around_cut(do)
                 else:
@@ -1167,7 +1167,7 @@ class HipNet(nn.Module):
     # ---- recorded launch lists (segnb_plan_*: include/segnb_hip.h) --------------------------------------------------------
     # The graphs are static: the SECOND step of a (geometry, mode) runs the Python build once more while the library records
     # every ABI call it makes (the first one allocated buffers and packed weights with calls that are not replayable); from
-    # the third step on the forward and the backward are one segnb_plan_run each -- 3-4 us of host time per launch instead
+    # the third step on the forward and the backward are one replayed list each -- 3-4 us of host time per launch instead
     # of the 10-14 us of a ctypes call, which is what bounds FCDenseNet103's ~2250 launches of ~10 us.  Whatever varies
     # between steps enters through persistent buffers: the input batch and the logits gradient are copied into them, the
     # dropout pools are redrawn in Tape.begin, BatchNorm statistics are cleared by the kernels that consume them.
@@ -1191,10 +1191,23 @@ class HipNet(nn.Module):
 
     @staticmethod
     def _plan_drop(ent):
-        for h in [ent.get('fwd')] + [h for h, _ in (ent.get('bwd') or [])]:
-            if h:
-                nv.call('segnb_plan_destroy', h)
-        ent['fwd'] = ent['bwd'] = None
+        for k in ('fwd', 'bwd'):
+            lst = ent.pop(k, None)
+            if lst is not None:
+                lst.destroy()
+
+    @staticmethod
+    @contextlib.contextmanager
+    def _recording(ent, kind):
+        """Record the launches of the body (yields the Recorder), which stores its list as ent[kind].  A step that raises, or
+        whose list cannot be replayed, stores none: the entry is then 'eager' for good and its lists are freed."""
+        with Recorder() as rec:
+            try:
+                yield rec
+            finally:
+                if ent.get(kind) is None:
+                    HipNet._plan_drop(ent)
+                    ent['state'] = 'eager'
 
     def _guards(self):
         g = getattr(self, '_replay_guards', None)
@@ -1224,7 +1237,7 @@ class HipNet(nn.Module):
         else:
             N, C, H, W = x.shape
         key = self._plan_key(x, need_grad, self._grads_alias)
-        ent, recording = None, False
+        ent, recording = None, contextlib.nullcontext()
         self._plan_live = None
         # the batch enters through ONE launch outside the recorded list (it reads the caller's tensor, whatever its address):
         # NCHW fp32 / NHWC uint8 -> the padded NHWC buffer the list's first convolution reads
@@ -1239,7 +1252,7 @@ class HipNet(nn.Module):
             else:
                 if ent['state'] == 'ready':
                     self._guard_mode = (key, 'replay')
-                    nv.call('segnb_plan_run', ent['fwd'])
+                    ent['fwd'].replay()
                     tape.back = []
                     tape.fused_stats = ent['fused_stats']
                     tape.stats_pending = bool(tape.fused_stats)
@@ -1247,24 +1260,15 @@ class HipNet(nn.Module):
                     return ent['logits'].clone()
                 if ent['state'] == 'seen' or (ent['state'] == 'fwd' and need_grad):
                     self._plan_drop(ent)                                    # (a recorded forward whose backward never ran)
-                    nv.plan_record_begin()
-                    recording = True
+                    recording = self._recording(ent, 'fwd')
         self._dlogits = [None]
         tape.unplannable = False
-        try:
+        with recording as rec:
             logits = self._build(tape, Act(xin, needs_grad=False), self._dlogits)
-        except BaseException:
-            if recording:                      # close the abandoned recording: this key stays eager
-                nv.plan_record_abort()
-                ent['state'] = 'eager'
-            raise
-        tape.stats_pending = bool(tape.fused_stats)
-        if recording:
-            handle, nops = nv.plan_record_end()
-            if handle is None:
-                ent['state'] = 'eager'                                     # not replayable: remembered
-            else:
-                ent.update(fwd=handle, logits=logits, nfwd=nops, state='fwd' if need_grad else 'ready',
+            tape.stats_pending = bool(tape.fused_stats)
+            lst = rec.finish() if rec is not None else None
+            if lst:
+                ent.update(fwd=lst, logits=logits, nfwd=lst.launches, state='fwd' if need_grad else 'ready',
                            fused_stats=list(tape.fused_stats))
                 self._guard_mode = (key, 'record')
                 self._plan_live = ent if need_grad else None
@@ -1305,65 +1309,27 @@ class HipNet(nn.Module):
         self._guard_active = self._guards()[1].begin() if ent is not None else False
         if ent is not None and ent['state'] == 'ready':
             self._guard_mode = (id(ent), 'replay')
-            for handle, cut in ent['bwd']:
-                nv.call('segnb_plan_run', handle)
-                if cut is not None:          # host work between two segments: partial unpack + the data-parallel hook
-                    table, lo, on_side = cut
-                    side = tape.rt.side_stream() if on_side else None
-                    if table is not None:
-                        if side is not None:
-                            with torch.cuda.stream(side):
-                                table.run()
-                        else:
-                            table.run()
-                    hook = tape._ready_hook()
-                    if hook is not None:
-                        hook(tape.flat, lo, (side,) if side is not None else ())
+            ent['bwd'].replay(lambda cut: tape.cut_host(*cut))      # host work between two segments, as recorded
             tape.rt._side_busy = False
             tape.stats_pending = False
             if ent['unpack'] is not None:
                 ent['unpack'].run()
         else:
             self._dlogits[0] = dlogits
-            recording = ent is not None and ent['state'] == 'fwd'
-            segs, around = [], None
-            paused = [False]          # True while a cut's hook runs OUTSIDE the recording (nothing is open to abort then)
-            if recording:
-                nv.plan_record_begin()
-
-                def around(do):
-                    handle, nops = nv.plan_record_end()
-                    paused[0] = True
-                    segs.append([handle, nops, None])          # the ended segment is owned by `segs` before the hook can raise
-                    segs[-1][2] = do()
-                    nv.plan_record_begin()
-                    paused[0] = False
-            try:
-                tape.run_closures(around, join=False)
-            except BaseException:
-                # (KeyboardInterrupt / SystemExit too: an open recording would swallow every later ABI call of this thread and
-                # make segnb_plan_run / segnb_tune refuse -- a validation pass in a Ctrl-C handler would hit that)
-                if recording:
-                    if not paused[0]:
-                        nv.plan_record_abort()
-                    for h, _, _ in segs:
-                        if h is not None:
-                            nv.call('segnb_plan_destroy', h)
-                    self._plan_drop(ent)
-                    ent['state'] = 'eager'
-                raise
-            if recording:
-                handle, nops = nv.plan_record_end()
-                segs.append((handle, nops, None))
-                if any(h is None for h, _, _ in segs) or getattr(tape, 'unplannable', False):
-                    for h, _, _ in segs:
-                        if h is not None:
-                            nv.call('segnb_plan_destroy', h)
-                    self._plan_drop(ent)
-                    ent['state'] = 'eager'
-                else:
-                    ent.update(bwd=[(h, c) for h, _, c in segs], nbwd=sum(n for _, n, _ in segs), state='ready')
-                    self._guard_mode = (id(ent), 'record')
+            if ent is not None and ent['state'] == 'fwd':
+                with self._recording(ent, 'bwd') as rec:
+                    def cut(do):             # the partial unpack and the hook run OUTSIDE the recording; the replay repeats them
+                        with rec.pause() as seg:
+                            seg.mark = do()
+                    tape.run_closures(cut, join=False)
+                    lst = rec.finish()
+                    if lst and getattr(tape, 'unplannable', False):
+                        lst.destroy()
+                    elif lst:
+                        ent.update(bwd=lst, nbwd=lst.launches, state='ready')
+                        self._guard_mode = (id(ent), 'record')
+            else:
+                tape.run_closures(join=False)
             table = tape.finish()                                           # (7x7 / strided jobs take host tap arrays: eager)
-            if recording and ent['state'] == 'ready':
+            if ent is not None and ent['state'] == 'ready':
                 ent['unpack'] = table
