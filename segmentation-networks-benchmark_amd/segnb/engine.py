@@ -338,6 +338,39 @@ class ConvOp(object):
                           all(m < 0 for m in imap[self.Ci:]))
         self._ci_offset = ci_offset
 
+    # ---- the two packed matrices --------------------------------------------------------------------
+    masked = False          # True: a packed tap sums several kernel positions (PackJob.masked; UpConvOp)
+    _FORM_KEYS = {'f': ('fwd', 'wp_fwd', 'tapoff_fwd'), 'd': ('dg', 'wp_dg', 'tapoff_dg')}     # plan keys: launches, matrices, tap words
+
+    def _form(self, f):
+        """(row map, column map, row stride, column stride, padded rows, padded columns) of a packed matrix: 'f' the forward matrix
+        [Cop][taps x Cip], 'd' the data-gradient matrix [Cip][taps x Cop].  The strides are those of one row / column channel in
+        the parameter tensor.  Buffer shapes, pack / unpack calls and job records are all derived from this."""
+        if f == 'f':
+            return self.out_map, self.in_map, self.s_out, self.s_in, self.Cop, self.Cip
+        return self.in_map, self.out_map, self.s_in, self.s_out, self.Cip, self.Cop
+
+    @property
+    def _wform(self):
+        """the form of the weight-gradient workspace, and of the launches that fill it"""
+        return 'd' if self.transposed else 'f'
+
+    def _taps(self, l):
+        """one word per tap of launch l: the kernel position of the parameter that the packed tap holds"""
+        return [a * self.KW + b for (_, _, a, b) in l.taps]
+
+    def _matrix(self, f, l, lead=(), dtype=None):
+        Mp, Cp = self._form(f)[4:]
+        return self.rt.zeros(tuple(lead) + (Mp, len(l.taps) * Cp), dtype)
+
+    def _job(self, f, l, w, packed, dtype, **extra):
+        """PackTable job record of the form-f matrix of launch l: parameter (or its gradient) w <-> packed buffer"""
+        mmap, cmap, s_m, s_c, Mp, Cp = self._form(f)
+        if self.masked:
+            extra['masked'] = True
+        return dict(w=w, packed=packed, mmap=mmap, cmap=cmap, s_m=s_m, s_c=s_c, Mp=Mp, Cp=Cp, ntaps=len(l.taps), dtype=dtype,
+                    tap_off=self._taps(l), **extra)
+
     # ---- per-input-size plan: launches, packed buffers -----------------------------------------
     def plan(self, Hi, Wi):
         key = (Hi, Wi)
@@ -361,31 +394,25 @@ class ConvOp(object):
         p['out_hw'] = (Ho, Wo)
         p['fwd'], p['fwd_full'] = fwd, full
         p['dg'], p['dg_full'] = dg, dg_full
-        p['wp_fwd'] = [rt.zeros((self.Cop, len(l.taps) * self.Cip)) for l in fwd]
+        for f in ('f', 'd') if self.need_dgrad else ('f',):
+            launches, wp, tapoff = self._FORM_KEYS[f]
+            p[wp] = [self._matrix(f, l) for l in p[launches]]
+            p[tapoff] = [nv.int_array(self._taps(l)) for l in p[launches]]
         if self.transposed and (self.KH, self.KW, self.stride, self.pad) == (4, 4, 2, 1) and len(fwd) == 4 and full and \
                 self.out_hw_override is None:
             # ConvTranspose2d(4, 2, 1): the four phase matrices in ONE buffer [4][Cop][4 * Cip] -- segnb_upconv_fprop runs the
             # phases as one launch where it serves the shape
             p['wp_fwd_all'] = rt.zeros((4, self.Cop, 4 * self.Cip))
             p['wp_fwd'] = [p['wp_fwd_all'][i] for i in range(4)]
-        p['tapoff_fwd'] = [nv.int_array([a * self.KW + b for (_, _, a, b) in l.taps]) for l in fwd]
-        if self.need_dgrad:
-            p['wp_dg'] = [rt.zeros((self.Cip, len(l.taps) * self.Cop)) for l in dg]
-            p['tapoff_dg'] = [nv.int_array([a * self.KW + b for (_, _, a, b) in l.taps]) for l in dg]
-        # weight-gradient workspace (fp32, packed like the forward matrix): nslab partial slabs per launch, as
-        # many as segnb_conv_wgrad_slabs asks for (a property of the channel counts, taps and width -- not of the
-        # batch).  The result is always slab 0 (zeroed here once, re-zeroed by segnb_unpack_wgrad when consumed);
-        # slabs 1.. are scratch for the partial sums of the pixel ranges.
-        if self.transposed:
-            geoms = [self._make_geom(l, 1, Ho, Wo, self.Cop, self.Cop, Hi, Wi, self.Cip, self.Cip) for l in dg]
-            p['nslab'] = self._under_wg_share(lambda: [nv.query('segnb_conv_wgrad_slabs', g, rt.code) for g in geoms])
-            p['dwp'] = [rt.zeros((n, self.Cip, len(l.taps) * self.Cop), torch.float32)
-                        for n, l in zip(p['nslab'], dg)]
-        else:
-            geoms = [self._make_geom(l, 1, Hi, Wi, self.Cip, self.Cip, Ho, Wo, self.Cop, self.Cop) for l in fwd]
-            p['nslab'] = self._under_wg_share(lambda: [nv.query('segnb_conv_wgrad_slabs', g, rt.code) for g in geoms])
-            p['dwp'] = [rt.zeros((n, self.Cop, len(l.taps) * self.Cip), torch.float32)
-                        for n, l in zip(p['nslab'], fwd)]
+        # weight-gradient workspace (fp32, packed like the forward matrix; a transposed convolution's like its data-gradient
+        # matrix): nslab partial slabs per launch, as many as segnb_conv_wgrad_slabs asks for (a property of the channel
+        # counts, taps and width -- not of the batch).  The result is always slab 0 (zeroed here once, re-zeroed by
+        # segnb_unpack_wgrad when consumed); slabs 1.. are scratch for the partial sums of the pixel ranges.
+        f = self._wform
+        launches = p[self._FORM_KEYS[f][0]]
+        geoms = [self._make_geom(l, 1, *self._dims(f, Hi, Wi, Ho, Wo)) for l in launches]
+        p['nslab'] = self._under_wg_share(lambda: [nv.query('segnb_conv_wgrad_slabs', g, rt.code) for g in geoms])
+        p['dwp'] = [self._matrix(f, l, (n,), torch.float32) for n, l in zip(p['nslab'], launches)]
         p['geoms'] = {}
         self._plans[key] = p
         return p
@@ -393,12 +420,52 @@ class ConvOp(object):
     def out_hw(self, Hi, Wi):
         return self.plan(Hi, Wi)['out_hw']
 
+    def _dims(self, side, Hi, Wi, Ho, Wo, ld_in=None, ld_out=None):
+        """(H, W, C, ld) of the tensor a launch gathers from, then of the one it writes: side 'f' runs x -> y, side 'd' (the data
+        gradient, and a transposed convolution's weight gradient) dy -> dx.  Hi x Wi: the convolution's input size; a pixel stride
+        left out is the dense one."""
+        x, y = (Hi, Wi, self.Cip), (Ho, Wo, self.Cop)
+        a, b = (x, y) if side == 'f' else (y, x)
+        return a + (a[2] if ld_in is None else ld_in,) + b + (b[2] if ld_out is None else ld_out,)
+
     def _geom(self, p, tag, li, launch, N, Hi, Wi, Ci, ld_in, Ho, Wo, Co, ld_out):
         key = (tag, li, N, ld_in, ld_out)
         g = p['geoms'].get(key)
         if g is None:
             g = p['geoms'][key] = self._make_geom(launch, N, Hi, Wi, Ci, ld_in, Ho, Wo, Co, ld_out)
         return g
+
+    def _launch_geom(self, p, side, li, N, H, W, ld_in=None, ld_out=None, tag=None):
+        """the cached geometry of launch li of a side at input size H x W (tag: the cache tag where it is not the side)"""
+        l = p[self._FORM_KEYS[side][0]][li]
+        return self._geom(p, tag or side, li, l, N, *self._dims(side, H, W, *p['out_hw'], ld_in=ld_in, ld_out=ld_out))
+
+    def _single(self, side, src=None, dst=None, N=None, H=None, W=None, ld_in=None, ld_out=None, tag=None):
+        """(launch, geometry) when ONE launch does the whole of a side -- what every fused variant needs -- else None.  Side 'f':
+        the forward is one launch that covers the whole output of a convolution that is not transposed; side 'd': the same of the
+        data gradient, where the op has one.  src / dst: the views the launch gathers from / writes to; a caller without one of
+        them gives N, the input size H x W and the pixel strides (default: dense) itself."""
+        if H is None:
+            own = src if side == 'f' else dst
+            H, W = own.H, own.W
+        p = self.plan(H, W)
+        if side == 'f':
+            ok = not self.transposed and len(p['fwd']) == 1 and p['fwd_full']
+        else:
+            ok = self.need_dgrad and len(p['dg']) == 1 and p['dg_full']
+        if not ok:
+            return None
+        if ld_in is None and src is not None:
+            ld_in = src.ld
+        if ld_out is None and dst is not None:
+            ld_out = dst.ld
+        return p[self._FORM_KEYS[side][0]][0], self._launch_geom(p, side, 0, src.N if N is None else N, H, W, ld_in, ld_out, tag)
+
+    def _single_ok(self, query, side, *a, **kw):
+        """does the library's `query` accept the single launch of a side (arguments as _single; extra: trailing query arguments)?"""
+        extra = kw.pop('extra', ())
+        s = self._single(side, *a, **kw)
+        return s is not None and bool(nv.query(query, s[1], self.rt.code, *extra))
 
     @staticmethod
     def _make_geom(launch, N, Hi, Wi, Ci, ld_in, Ho, Wo, Co, ld_out):
@@ -416,53 +483,49 @@ class ConvOp(object):
             g.dh[i], g.dw[i] = dh, dw
         return g
 
+    def _flops(self, N, l):
+        """multiply-adds x 2 that launch l executes at batch size N"""
+        return 2.0 * N * l.QH * l.QW * len(l.taps) * self.Ci * self.Co
+
+    def _bias_args(self):
+        """(bias pointer, its length) as the forward entry points take them; (NULL, 0) without a bias"""
+        b = self.bias.detach() if self.bias is not None else None
+        return nv.ptr(b), self.Co if b is not None else 0
+
+    @staticmethod
+    def _bn_reduce_ep(bn_reduce):
+        """bn_reduce (y View, coef, sums, act, slope) of dgrad() -> the launch's epilogue struct (None -> None)"""
+        if bn_reduce is None:
+            return None
+        yv, coef, sums, act, slope = bn_reduce
+        return nv.BnReduceEpilogue(yv.ptr, yv.ld, nv.ptr(coef), nv.ptr(sums), act, slope)
+
     # ---- weight packing (every time the parameters changed) ---------------------------------------
     def pack(self, Hi, Wi):
         p, rt = self.plan(Hi, Wi), self.rt
         w = self.weight.detach()
-        for li, l in enumerate(p['fwd']):
-            nv.call('segnb_pack_weight', nv.ptr(w), nv.ptr(p['wp_fwd'][li]), rt.code, self.Cop, self.Cip,
-                    len(l.taps), self.s_out, self.s_in, p['tapoff_fwd'][li], nv.ptr(self.out_map),
-                    nv.ptr(self.in_map), rt.stream)
-        if self.need_dgrad:
-            for li, l in enumerate(p['dg']):
-                nv.call('segnb_pack_weight', nv.ptr(w), nv.ptr(p['wp_dg'][li]), rt.code, self.Cip, self.Cop,
-                        len(l.taps), self.s_in, self.s_out, p['tapoff_dg'][li], nv.ptr(self.in_map),
-                        nv.ptr(self.out_map), rt.stream)
+        for f in ('f', 'd') if self.need_dgrad else ('f',):
+            launches, wp, tapoff = self._FORM_KEYS[f]
+            mmap, cmap, s_m, s_c, Mp, Cp = self._form(f)
+            for li, l in enumerate(p[launches]):
+                nv.call('segnb_pack_weight', nv.ptr(w), nv.ptr(p[wp][li]), rt.code, Mp, Cp, len(l.taps), s_m, s_c, p[tapoff][li],
+                        nv.ptr(mmap), nv.ptr(cmap), rt.stream)
 
     def pack_jobs(self, Hi, Wi):
         """Job records (PackTable) equivalent to pack(Hi, Wi)."""
         p, rt = self.plan(Hi, Wi), self.rt
         w = self.weight.detach()
-        jobs = []
-        for li, l in enumerate(p['fwd'] if self.pack_fwd else ()):
-            jobs.append(dict(w=w, packed=p['wp_fwd'][li], mmap=self.out_map, cmap=self.in_map, s_m=self.s_out,
-                             s_c=self.s_in, Mp=self.Cop, Cp=self.Cip, ntaps=len(l.taps), dtype=rt.code, form='f',
-                             tap_off=[a * self.KW + b for (_, _, a, b) in l.taps]))
-        if self.need_dgrad:
-            for li, l in enumerate(p['dg']):
-                jobs.append(dict(w=w, packed=p['wp_dg'][li], mmap=self.in_map, cmap=self.out_map, s_m=self.s_in,
-                                 s_c=self.s_out, Mp=self.Cip, Cp=self.Cop, ntaps=len(l.taps), dtype=rt.code, form='d',
-                                 tap_off=[a * self.KW + b for (_, _, a, b) in l.taps]))
-        return jobs
+        forms = (('f',) if self.pack_fwd else ()) + (('d',) if self.need_dgrad else ())
+        return [self._job(f, l, w, p[self._FORM_KEYS[f][1]][li], rt.code, form=f)
+                for f in forms for li, l in enumerate(p[self._FORM_KEYS[f][0]])]
 
     def unpack_jobs(self, Hi, Wi, grad_w):
         """Job records equivalent to the segnb_unpack_wgrad calls of wgrad(); use with wgrad(..., unpack=False)."""
         p = self.plan(Hi, Wi)
-        jobs = []
         if self.direct_ok():
-            return jobs          # (delivered by the weight-gradient launches themselves: segnb_wgrad_target)
-        if self.transposed:
-            for li, l in enumerate(p['dg']):
-                jobs.append(dict(w=grad_w, packed=p['dwp'][li], mmap=self.in_map, cmap=self.out_map, s_m=self.s_in,
-                                 s_c=self.s_out, Mp=self.Cip, Cp=self.Cop, ntaps=len(l.taps), dtype=nv.F32,
-                                 nslab=1, tap_off=[a * self.KW + b for (_, _, a, b) in l.taps]))
-        else:
-            for li, l in enumerate(p['fwd']):
-                jobs.append(dict(w=grad_w, packed=p['dwp'][li], mmap=self.out_map, cmap=self.in_map, s_m=self.s_out,
-                                 s_c=self.s_in, Mp=self.Cop, Cp=self.Cip, ntaps=len(l.taps), dtype=nv.F32,
-                                 nslab=1, tap_off=[a * self.KW + b for (_, _, a, b) in l.taps]))
-        return jobs
+            return []            # (delivered by the weight-gradient launches themselves: segnb_wgrad_target)
+        f = self._wform
+        return [self._job(f, l, grad_w, p['dwp'][li], nv.F32, nslab=1) for li, l in enumerate(p[self._FORM_KEYS[f][0]])]
 
     # ---- kernels ------------------------------------------------------------------------------------
     # activation (and eval-mode BatchNorm) in the convolution's epilogue instead of a pass of its own (A/B: class attribute fuse_act)
@@ -476,7 +539,7 @@ class ConvOp(object):
         assert (yv.H, yv.W) == p['out_hw']
         if not p['fwd_full']:
             rt.clear_view(yv)
-        b = self.bias.detach() if self.bias is not None else None
+        bias = self._bias_args()
         if epilogue is not None:
             # (the phase launches of a transposed convolution write disjoint output parities: each applies the epilogue to its own)
             assert stats is None and p['fwd_full'], 'full coverage, no statistics'
@@ -486,29 +549,28 @@ class ConvOp(object):
                 assert epilogue[0] is None and self.upconv_act_ok(xv.N, xv.H, xv.W, yv.ld)
                 _timed('conv_fprop', 2.0 * xv.N * xv.H * xv.W * 16 * self.Ci * self.Co,
                        lambda: nv.call('segnb_upconv_fprop_act', rt.code, xv.N, xv.H, xv.W, self.Cip, xv.ld, xv.ptr,
-                                       nv.ptr(p['wp_fwd_all']), self.Cop, self.Cop, nv.ptr(b), self.Co if b is not None else 0,
-                                       yv.ptr, yv.ld, ep, rt.stream))
+                                       nv.ptr(p['wp_fwd_all']), self.Cop, self.Cop, bias[0], bias[1], yv.ptr, yv.ld, ep, rt.stream))
                 return
             for li, l in enumerate(p['fwd']):
-                g = self._geom(p, 'f', li, l, xv.N, xv.H, xv.W, self.Cip, xv.ld, yv.H, yv.W, self.Cop, yv.ld)
-                _timed('conv_fprop', 2.0 * xv.N * l.QH * l.QW * len(l.taps) * self.Ci * self.Co,
-                       lambda: nv.call('segnb_conv_fprop_act', g, rt.code, xv.ptr, nv.ptr(p['wp_fwd'][li]), nv.ptr(b),
-                                       self.Co if b is not None else 0, yv.ptr, ep, rt.stream))
+                g = self._launch_geom(p, 'f', li, xv.N, xv.H, xv.W, xv.ld, yv.ld)
+                _timed('conv_fprop', self._flops(xv.N, l),
+                       lambda: nv.call('segnb_conv_fprop_act', g, rt.code, xv.ptr, nv.ptr(p['wp_fwd'][li]), bias[0], bias[1],
+                                       yv.ptr, ep, rt.stream))
             return
         if type(self) is ConvOp and 'wp_fwd_all' in p and \
                 nv.query('segnb_upconv_fprop_ok', xv.N, xv.H, xv.W, self.Cip, self.Cop, yv.ld, rt.code):
             ex = 2.0 * xv.N * xv.H * xv.W * 16 * self.Ci * self.Co
             _timed('conv_fprop', ex,
                    lambda: nv.call('segnb_upconv_fprop', rt.code, xv.N, xv.H, xv.W, self.Cip, xv.ld, xv.ptr,
-                                   nv.ptr(p['wp_fwd_all']), self.Cop, self.Cop, nv.ptr(b), self.Co if b is not None else 0,
-                                   yv.ptr, yv.ld, nv.ptr(stats), rt.stream))
+                                   nv.ptr(p['wp_fwd_all']), self.Cop, self.Cop, bias[0], bias[1], yv.ptr, yv.ld, nv.ptr(stats),
+                                   rt.stream))
             return
         for li, l in enumerate(p['fwd']):
-            g = self._geom(p, 'f', li, l, xv.N, xv.H, xv.W, self.Cip, xv.ld, yv.H, yv.W, self.Cop, yv.ld)
-            ex = 2.0 * xv.N * l.QH * l.QW * len(l.taps) * self.Ci * self.Co
+            g = self._launch_geom(p, 'f', li, xv.N, xv.H, xv.W, xv.ld, yv.ld)
+            ex = self._flops(xv.N, l)
             _timed('conv_fprop', ex * self.algo_scale,
-                   lambda: nv.call('segnb_conv_fprop', g, rt.code, xv.ptr, nv.ptr(p['wp_fwd'][li]), nv.ptr(b),
-                                   self.Co if b is not None else 0, yv.ptr, nv.ptr(stats), rt.stream), ex)
+                   lambda: nv.call('segnb_conv_fprop', g, rt.code, xv.ptr, nv.ptr(p['wp_fwd'][li]), bias[0], bias[1], yv.ptr,
+                                   nv.ptr(stats), rt.stream), ex)
 
     def upconv_act_ok(self, N, H, W, ld_out):
         p = self.plan(H, W)
@@ -537,93 +599,67 @@ class ConvOp(object):
     def drop_epilogue_ok(self, N, H, W, ld_out):
         """True when segnb_conv_fprop_drop serves this convolution: the Dropout2d multipliers (and the statistics of the result) in
         the launch's store pass."""
-        p = self.plan(H, W)
-        if not self.fuse_drop or self.transposed or len(p['fwd']) != 1 or not p['fwd_full'] or self.rt.code != nv.BF16:
-            return False
-        Ho, Wo = p['out_hw']
-        g = self._geom(p, 'f', 0, p['fwd'][0], N, H, W, self.Cip, self.Cip, Ho, Wo, self.Cop, ld_out)
-        return bool(nv.query('segnb_conv_fprop_drop_ok', g, self.rt.code))
+        s = self._single('f', N=N, H=H, W=W, ld_out=ld_out)
+        return bool(s is not None and self.fuse_drop and self.rt.code == nv.BF16
+                    and nv.query('segnb_conv_fprop_drop_ok', s[1], self.rt.code))
 
     def fprop_drop(self, xv, yv, dropmul, out_stats=None):
         """yv = Dropout2d multipliers x (conv + bias); out_stats: (fp64 table, element offset, row stride) -- the statistics of yv are
         accumulated into that channel range -- or None.  Check drop_epilogue_ok first."""
         p, rt = self.plan(xv.H, xv.W), self.rt
         assert xv.Cp == self.Cip and yv.Cp == self.Cop and (yv.H, yv.W) == p['out_hw'] and dropmul.shape[1] >= self.Cop
-        l = p['fwd'][0]
-        g = self._geom(p, 'f', 0, l, xv.N, xv.H, xv.W, self.Cip, xv.ld, yv.H, yv.W, self.Cop, yv.ld)
-        b = self.bias.detach() if self.bias is not None else None
+        l, g = self._single('f', xv, yv)
         st = nv.ptr(out_stats[0], out_stats[1]) if out_stats is not None else None
-        _timed('conv_fprop', 2.0 * xv.N * l.QH * l.QW * len(l.taps) * self.Ci * self.Co,
-               lambda: nv.call('segnb_conv_fprop_drop', g, rt.code, xv.ptr, nv.ptr(p['wp_fwd'][0]), nv.ptr(b),
-                               self.Co if b is not None else 0, yv.ptr, nv.ptr(dropmul), int(dropmul.shape[1]), st,
-                               out_stats[2] if out_stats is not None else 0, rt.stream))
+        _timed('conv_fprop', self._flops(xv.N, l),
+               lambda: nv.call('segnb_conv_fprop_drop', g, rt.code, xv.ptr, nv.ptr(p['wp_fwd'][0]), *self._bias_args(), yv.ptr,
+                               nv.ptr(dropmul), int(dropmul.shape[1]), st, out_stats[2] if out_stats is not None else 0,
+                               rt.stream))
 
     def u8_direct_ok(self, N, H, W, ld_out):
         """True when segnb_conv_fprop_u8 serves this convolution as the network's first layer."""
-        p = self.plan(H, W)
-        if len(p['fwd']) != 1 or self.Cip != 8 or p['out_hw'] != (H, W):
-            return False
-        g = self._geom(p, 'f', 0, p['fwd'][0], N, H, W, self.Cip, self.Cip, H, W, self.Cop, ld_out)
-        return bool(nv.query('segnb_conv_fprop_u8_ok', g, self.rt.code))
+        return (self.plan(H, W)['out_hw'] == (H, W) and self.Cip == 8
+                and self._single_ok('segnb_conv_fprop_u8_ok', 'f', N=N, H=H, W=W, ld_out=ld_out))
 
     def fprop_u8(self, img, norm, yv, stats=None, packed=None):
         """First layer straight from the uint8 HWC batch `img` [N,H,W,C]; packed: optional View that receives the
         normalised bf16 pixels (the x operand of this layer's weight gradient)."""
         N, H, W, C = img.shape
         p, rt = self.plan(H, W), self.rt
-        l = p['fwd'][0]
-        g = self._geom(p, 'f', 0, l, N, H, W, self.Cip, self.Cip, yv.H, yv.W, self.Cop, yv.ld)
+        l, g = self._single('f', None, yv, N=N, H=H, W=W)
         mean, std = norm.arrays(C)
-        b = self.bias.detach() if self.bias is not None else None
-        _timed('conv_fprop', 2.0 * N * l.QH * l.QW * len(l.taps) * self.Ci * self.Co,
+        _timed('conv_fprop', self._flops(N, l),
                lambda: nv.call('segnb_conv_fprop_u8', g, nv.ptr(img), C, norm.scale, mean, std, nv.ptr(p['wp_fwd'][0]),
-                               nv.ptr(b), self.Co if b is not None else 0, yv.ptr, nv.ptr(stats), vptr(packed),
-                               vld(packed), rt.stream))
+                               *self._bias_args(), yv.ptr, nv.ptr(stats), vptr(packed), vld(packed), rt.stream))
 
     def dgrad_bnreduce_ok(self, dyv, dxv):
         """True when this data gradient can also do the BatchNorm-backward reduction of the layer that produced its
         input (segnb_conv_fprop_bnreduce): one launch geometry, served by a fused kernel."""
-        p = self.plan(dxv.H, dxv.W)
-        if not self.need_dgrad or len(p['dg']) != 1 or not p['dg_full']:
-            return False
-        g = self._geom(p, 'd', 0, p['dg'][0], dyv.N, dyv.H, dyv.W, self.Cop, dyv.ld, dxv.H, dxv.W, self.Cip, dxv.ld)
-        return bool(nv.query('segnb_conv_fprop_bnreduce_ok', g, self.rt.code))
+        return self._single_ok('segnb_conv_fprop_bnreduce_ok', 'd', dyv, dxv)
 
     def dgrad_bnapply_ok(self, dyv, N, H, W, ld):
         """True when this data gradient can run as the two launches that never store it (segnb_conv_fprop_bnsums / _bnapply: a dense
         layer's 16 -> prefix gradient); N, H, W, ld: the input tensor's geometry (the gradient itself gets no buffer)."""
-        p = self.plan(H, W)
-        if not self.need_dgrad or len(p['dg']) != 1 or not p['dg_full']:
-            return False
-        g = self._geom(p, 'd', 0, p['dg'][0], dyv.N, dyv.H, dyv.W, self.Cop, dyv.ld, H, W, self.Cip, ld)
-        return bool(nv.query('segnb_conv_fprop_bnapply_ok', g, self.rt.code))
+        return self._single_ok('segnb_conv_fprop_bnapply_ok', 'd', dyv, H=H, W=W, ld_out=ld)
 
     def dgrad_bnsums(self, dyv, H, W, bn_reduce):
         """first launch: the BatchNorm-backward sums of the layer whose activation gradient this data gradient is; nothing stored"""
         p, rt = self.plan(H, W), self.rt
-        l = p['dg'][0]
-        yv, coef, sums, act, slope = bn_reduce
-        g = self._geom(p, 'd', 0, l, dyv.N, dyv.H, dyv.W, self.Cop, dyv.ld, H, W, self.Cip, yv.ld)
-        ep = nv.BnReduceEpilogue(yv.ptr, yv.ld, nv.ptr(coef), nv.ptr(sums), act, slope)
-        _timed('conv_fprop', 2.0 * dyv.N * l.QH * l.QW * len(l.taps) * self.Ci * self.Co,
+        l, g = self._single('d', dyv, H=H, W=W, ld_out=bn_reduce[0].ld)
+        ep = self._bn_reduce_ep(bn_reduce)
+        _timed('conv_fprop', self._flops(dyv.N, l),
                lambda: nv.call('segnb_conv_fprop_bnsums', g, rt.code, dyv.ptr, nv.ptr(p['wp_dg'][0]), ep, rt.stream))
 
     def dgrad_bnapply(self, dyv, H, W, ep):
         """second launch (ep: nv.BnApplyEpilogue): the gradient recomputed, BatchNorm backward applied, written / added to ep.dx"""
         p, rt = self.plan(H, W), self.rt
-        l = p['dg'][0]
-        g = self._geom(p, 'd', 0, l, dyv.N, dyv.H, dyv.W, self.Cop, dyv.ld, H, W, self.Cip, ep.ld_dx)
-        _timed('conv_fprop', 2.0 * dyv.N * l.QH * l.QW * len(l.taps) * self.Ci * self.Co,
+        l, g = self._single('d', dyv, H=H, W=W, ld_out=ep.ld_dx)
+        _timed('conv_fprop', self._flops(dyv.N, l),
                lambda: nv.call('segnb_conv_fprop_bnapply', g, rt.code, dyv.ptr, nv.ptr(p['wp_dg'][0]), ep, rt.stream))
 
     def dgrad_actmask_ok(self, dyv, dxv):
         """True when this data gradient can apply the activation mask of the conv + activation (no BatchNorm) that produced its
         input and store dz (segnb_conv_fprop_bnreduce with coef None)."""
-        p = self.plan(dxv.H, dxv.W)
-        if not self.need_dgrad or len(p['dg']) != 1 or not p['dg_full']:
-            return False
-        g = self._geom(p, 'd', 0, p['dg'][0], dyv.N, dyv.H, dyv.W, self.Cop, dyv.ld, dxv.H, dxv.W, self.Cip, dxv.ld)
-        return bool(nv.query('segnb_conv_fprop_actmask_ok', g, self.rt.code))
+        return self._single_ok('segnb_conv_fprop_actmask_ok', 'd', dyv, dxv)
 
     def dgrad(self, dyv, dxv, bn_reduce=None):
         """bn_reduce: (y View, coef, sums, act, slope) of the layer whose activation gradient dxv is -- its reduction
@@ -634,15 +670,14 @@ class ConvOp(object):
         if not p['dg_full']:
             rt.clear_view(dxv)
         for li, l in enumerate(p['dg']):
-            g = self._geom(p, 'd', li, l, dyv.N, dyv.H, dyv.W, self.Cop, dyv.ld, dxv.H, dxv.W, self.Cip, dxv.ld)
+            g = self._launch_geom(p, 'd', li, dyv.N, dxv.H, dxv.W, dyv.ld, dxv.ld)
             if bn_reduce is not None:
-                yv, coef, sums, act, slope = bn_reduce
-                ep = nv.BnReduceEpilogue(yv.ptr, yv.ld, nv.ptr(coef), nv.ptr(sums), act, slope)
-                _timed('conv_fprop', 2.0 * dyv.N * l.QH * l.QW * len(l.taps) * self.Ci * self.Co,
+                ep = self._bn_reduce_ep(bn_reduce)
+                _timed('conv_fprop', self._flops(dyv.N, l),
                        lambda: nv.call('segnb_conv_fprop_bnreduce', g, rt.code, dyv.ptr, nv.ptr(p['wp_dg'][li]), dxv.ptr,
                                        ep, rt.stream))
                 continue
-            ex = 2.0 * dyv.N * l.QH * l.QW * len(l.taps) * self.Ci * self.Co
+            ex = self._flops(dyv.N, l)
             _timed('conv_fprop', ex * self.algo_scale,
                    lambda: nv.call('segnb_conv_fprop', g, rt.code, dyv.ptr, nv.ptr(p['wp_dg'][li]), None, 0,
                                    dxv.ptr, None, rt.stream), ex)
@@ -659,62 +694,39 @@ class ConvOp(object):
         return nv.OperandTf(nv.TF_BNBWD, yv.ptr, yv.ld, nv.ptr(coef), nv.ptr(bcoef), None, yv.Cp, act, slope)
 
     def fprop_tf_ok(self, xv, yv):
-        p = self.plan(xv.H, xv.W)
-        if self.transposed or len(p['fwd']) != 1 or not p['fwd_full']:
-            return False
-        g = self._geom(p, 'f', 0, p['fwd'][0], xv.N, xv.H, xv.W, self.Cip, xv.ld, yv.H, yv.W, self.Cop, yv.ld)
-        return bool(nv.query('segnb_conv_fprop_tf_ok', g, self.rt.code, nv.TF_ACT))
+        return self._single_ok('segnb_conv_fprop_tf_ok', 'f', xv, yv, extra=(nv.TF_ACT,))
 
     def fprop_tf(self, xv, tf, yv, stats=None):
         """forward whose input operand is tf(xv) (xv: the producing layer's pre-BatchNorm output)"""
         p, rt = self.plan(xv.H, xv.W), self.rt
-        l = p['fwd'][0]
-        g = self._geom(p, 'f', 0, l, xv.N, xv.H, xv.W, self.Cip, xv.ld, yv.H, yv.W, self.Cop, yv.ld)
-        b = self.bias.detach() if self.bias is not None else None
-        _timed('conv_fprop', 2.0 * xv.N * l.QH * l.QW * len(l.taps) * self.Ci * self.Co,
-               lambda: nv.call('segnb_conv_fprop_tf', g, rt.code, xv.ptr, tf, nv.ptr(p['wp_fwd'][0]), nv.ptr(b),
-                               self.Co if b is not None else 0, yv.ptr, nv.ptr(stats), None, rt.stream))
+        l, g = self._single('f', xv, yv)
+        _timed('conv_fprop', self._flops(xv.N, l),
+               lambda: nv.call('segnb_conv_fprop_tf', g, rt.code, xv.ptr, tf, nv.ptr(p['wp_fwd'][0]), *self._bias_args(), yv.ptr,
+                               nv.ptr(stats), None, rt.stream))
 
     def dgrad_tf_ok(self, dyv, dxv):
-        p = self.plan(dxv.H, dxv.W)
-        if not self.need_dgrad or len(p['dg']) != 1 or not p['dg_full']:
-            return False
-        g = self._geom(p, 'd', 0, p['dg'][0], dyv.N, dyv.H, dyv.W, self.Cop, dyv.ld, dxv.H, dxv.W, self.Cip, dxv.ld)
-        return bool(nv.query('segnb_conv_fprop_tf_ok', g, self.rt.code, nv.TF_BNBWD))
+        return self._single_ok('segnb_conv_fprop_tf_ok', 'd', dyv, dxv, extra=(nv.TF_BNBWD,))
 
     def dgrad_tf(self, gv, tf, dxv, bn_reduce=None):
         """data gradient whose dy operand is tf(gv) (gv: the gradient of this layer's activation, or dz); bn_reduce as dgrad()"""
         p, rt = self.plan(dxv.H, dxv.W), self.rt
-        l = p['dg'][0]
-        g = self._geom(p, 'd', 0, l, gv.N, gv.H, gv.W, self.Cop, gv.ld, dxv.H, dxv.W, self.Cip, dxv.ld)
-        ep = None
-        if bn_reduce is not None:
-            yv, coef, sums, act, slope = bn_reduce
-            ep = nv.BnReduceEpilogue(yv.ptr, yv.ld, nv.ptr(coef), nv.ptr(sums), act, slope)
-        _timed('conv_fprop', 2.0 * gv.N * l.QH * l.QW * len(l.taps) * self.Ci * self.Co,
+        l, g = self._single('d', gv, dxv)
+        ep = self._bn_reduce_ep(bn_reduce)
+        _timed('conv_fprop', self._flops(gv.N, l),
                lambda: nv.call('segnb_conv_fprop_tf', g, rt.code, gv.ptr, tf, nv.ptr(p['wp_dg'][0]), None, 0, dxv.ptr, None, ep,
                                rt.stream))
 
     def wgrad_tf_ok(self, xv, dyv):
-        p = self.plan(xv.H, xv.W)
-        if self.transposed or len(p['fwd']) != 1:
-            return False
-        g = self._geom(p, 'f', 0, p['fwd'][0], xv.N, xv.H, xv.W, self.Cip, xv.ld, dyv.H, dyv.W, self.Cop, dyv.ld)
-        return bool(nv.query('segnb_conv_wgrad_tf_ok', g, self.rt.code))
+        return self._single_ok('segnb_conv_wgrad_tf_ok', 'f', xv, dyv)
 
     def wgrad_tf(self, xv, tfx, dv, tfd, grad_w=None):
         """weight gradient with x = tfx(xv) and dy = tfd(dv) (either transform may be None); the result is left in the
         packed workspace (slab 0), or delivered into grad_w (direct_ok).  grad_w None on a direct_ok op also leaves it in the
         workspace -- for a caller that reads it there: unpack_jobs() has no job for such an op, so a backward passes grad_w"""
         p, rt = self.plan(xv.H, xv.W), self.rt
-        l = p['fwd'][0]
-        g = self._geom(p, 'f', 0, l, xv.N, xv.H, xv.W, self.Cip, xv.ld, dv.H, dv.W, self.Cop, dv.ld)
-
-        def launch():
-            if self.direct_ok() and grad_w is not None:
-                self._arm_target(p, 0, grad_w)
-            nv.call('segnb_conv_wgrad_tf', g, rt.code, xv.ptr, tfx, dv.ptr, tfd, nv.ptr(p['dwp'][0]), p['nslab'][0], rt.stream)
-        _timed('conv_wgrad', 2.0 * xv.N * l.QH * l.QW * len(l.taps) * self.Ci * self.Co, lambda: self._under_wg_share(launch))
+        l, g = self._single('f', xv, dv)
+        self._wgrad_launch(p, 0, l, xv.N, grad_w, lambda: nv.call(
+            'segnb_conv_wgrad_tf', g, rt.code, xv.ptr, tfx, dv.ptr, tfd, nv.ptr(p['dwp'][0]), p['nslab'][0], rt.stream))
 
     # share (%) of the CUs this convolution's weight gradient splits its pixels for; None = the library default.  Set before
     # the first plan (the workspace is sized under it); every launch is bracketed by segnb_wg_cu_share (recordable)
@@ -729,32 +741,36 @@ class ConvOp(object):
         finally:
             nv.call('segnb_wg_cu_share', 0)
 
+    def _wgrad_launch(self, p, li, l, N, grad_w, call, scaled=False):
+        """One weight-gradient launch `call` for launch l (index li) of the workspace's form: the delivery target armed first where
+        the op delivers into grad_w itself (direct_ok, and a grad_w given), under the op's CU share, timed as conv_wgrad."""
+        def launch():
+            if grad_w is not None and self.direct_ok():
+                self._arm_target(p, li, grad_w)
+            call()
+        ex = self._flops(N, l)
+        if scaled:
+            _timed('conv_wgrad', ex * self.algo_scale, lambda: self._under_wg_share(launch), ex)
+        else:
+            _timed('conv_wgrad', ex, lambda: self._under_wg_share(launch))
+
     def wgrad_bnapply_ok(self, xv, yv):
         """True when this convolution's weight gradient can recompute its dy operand -- the BatchNorm-backward apply of the
         layer -- from (g, y) itself (segnb_conv_wgrad_bnapply): the apply pass then disappears for a layer without a data
         gradient.  By default only the first layer's rolling kernel (8 padded input channels) takes it: 52.6 us against
         52.5 us (apply pass) + 58.8 us (weight gradient on the stored dz) stand-alone, -0.85 % of the timed step;
         SEGNB_WGRAD_BNAPPLY=1 adds the thin tile kernel's variant (measured neutral), =0 disables both."""
-        p = self.plan(xv.H, xv.W)
-        if self.transposed or len(p['fwd']) != 1:
-            return False
-        g = self._geom(p, 'f', 0, p['fwd'][0], xv.N, xv.H, xv.W, self.Cip, xv.ld, yv.H, yv.W, self.Cop, yv.ld)
-        return bool(nv.query('segnb_conv_wgrad_bnapply_ok', g, self.rt.code))
+        return self._single_ok('segnb_conv_wgrad_bnapply_ok', 'f', xv, yv)
 
     def wgrad_bnapply(self, xv, gv, yv, coef, bcoef, act, slope, grad_w=None):
         """the weight gradient with dy = BatchNorm-backward apply of (gv, yv); result left in the packed workspace, or delivered
         into grad_w (direct_ok: required, as for wgrad_tf)"""
         assert grad_w is not None or not self.direct_ok(), 'a directly delivering op needs grad_w'
         p, rt = self.plan(xv.H, xv.W), self.rt
-        l = p['fwd'][0]
-        g = self._geom(p, 'f', 0, l, xv.N, xv.H, xv.W, self.Cip, xv.ld, yv.H, yv.W, self.Cop, yv.ld)
-
-        def launch():
-            if self.direct_ok():
-                self._arm_target(p, 0, grad_w)
-            nv.call('segnb_conv_wgrad_bnapply', g, rt.code, xv.ptr, gv.ptr, gv.ld, yv.ptr, yv.ld, nv.ptr(coef), nv.ptr(bcoef),
-                    self.Cop, act, slope, nv.ptr(p['dwp'][0]), p['nslab'][0], rt.stream)
-        _timed('conv_wgrad', 2.0 * xv.N * l.QH * l.QW * len(l.taps) * self.Ci * self.Co, lambda: self._under_wg_share(launch))
+        l, g = self._single('f', xv, yv)
+        self._wgrad_launch(p, 0, l, xv.N, grad_w, lambda: nv.call(
+            'segnb_conv_wgrad_bnapply', g, rt.code, xv.ptr, gv.ptr, gv.ld, yv.ptr, yv.ld, nv.ptr(coef), nv.ptr(bcoef), self.Cop, act,
+            slope, nv.ptr(p['dwp'][0]), p['nslab'][0], rt.stream))
 
     # direct_dw = False (class attribute / SEGNB_DIRECT_DW=0): weight gradients through the packed workspace + batched unpack (A/B)
     direct_dw = os.environ.get('SEGNB_DIRECT_DW', '1') != '0'
@@ -788,8 +804,8 @@ class ConvOp(object):
             t.gw = grad_w.data_ptr()
             t.s_out, t.s_in, t.ci_off = self.s_out, self.s_in, self._ci_offset
             t.Ci, t.Co, t.accumulate, t.ntaps = self.Ci, self.Co, 0 if over else 1, len(l.taps)
-            for i, (_, _, a, b) in enumerate(l.taps):
-                t.kpos[i] = a * self.KW + b
+            for i, k in enumerate(self._taps(l)):
+                t.kpos[i] = k
             p[key] = t
         nv.call('segnb_wgrad_target_arm', t)
 
@@ -798,41 +814,22 @@ class ConvOp(object):
         workspace (slab 0) for a later batched segnb_unpack_wgrad_multi (unpack_jobs) -- unless the launches deliver into
         grad_w themselves (direct_ok: no unpack job exists for them)."""
         p, rt = self.plan(xv.H, xv.W), self.rt
-        gw = grad_w
-        entry = 'segnb_conv_wgrad'
-        if self.direct_ok():
-            for li, l in enumerate(p['fwd']):
-                g = self._geom(p, 'f', li, l, xv.N, xv.H, xv.W, self.Cip, xv.ld, dyv.H, dyv.W, self.Cop, dyv.ld)
-
-                def launch():
-                    self._arm_target(p, li, gw)
-                    nv.call(entry, g, rt.code, xv.ptr, dyv.ptr, nv.ptr(p['dwp'][li]), p['nslab'][li], rt.stream)
-                _timed('conv_wgrad', 2.0 * xv.N * l.QH * l.QW * len(l.taps) * self.Ci * self.Co,
-                       lambda: self._under_wg_share(launch))
-            return
-        if self.transposed:
-            # dW[ci][co][k] = sum_hi x[hi][ci] * dy[hi*s - pad + k][co]: "dout" := x, gathered "in" := dy
-            for li, l in enumerate(p['dg']):
-                g = self._geom(p, 'wt', li, l, xv.N, dyv.H, dyv.W, self.Cop, dyv.ld, xv.H, xv.W, self.Cip, xv.ld)
-                ex = 2.0 * xv.N * l.QH * l.QW * len(l.taps) * self.Ci * self.Co
-                _timed('conv_wgrad', ex * self.algo_scale,
-                       lambda: self._under_wg_share(lambda: nv.call(entry, g, rt.code, dyv.ptr, xv.ptr, nv.ptr(p['dwp'][li]),
-                                                                    p['nslab'][li], rt.stream)),
-                       ex)
-                if unpack:
-                    nv.call('segnb_unpack_wgrad', nv.ptr(p['dwp'][li]), nv.ptr(gw), self.Cip, self.Cop, len(l.taps),
-                            self.s_in, self.s_out, p['tapoff_dg'][li], nv.ptr(self.in_map), nv.ptr(self.out_map), 1,
-                            rt.stream)
-            return
-        for li, l in enumerate(p['fwd']):
-            g = self._geom(p, 'f', li, l, xv.N, xv.H, xv.W, self.Cip, xv.ld, dyv.H, dyv.W, self.Cop, dyv.ld)
-            _timed('conv_wgrad', 2.0 * xv.N * l.QH * l.QW * len(l.taps) * self.Ci * self.Co,
-                   lambda: self._under_wg_share(lambda: nv.call(entry, g, rt.code, xv.ptr, dyv.ptr, nv.ptr(p['dwp'][li]),
-                                                                p['nslab'][li], rt.stream)))
+        # the workspace's form decides the launches, the geometry tag and the operand order.  Transposed:
+        # dW[ci][co][k] = sum_hi x[hi][ci] * dy[hi*s - pad + k][co], i.e. "dout" := x, gathered "in" := dy
+        f = self._wform
+        launches, _, tapoff = self._FORM_KEYS[f]
+        src, dst, tag = (dyv, xv, 'wt') if self.transposed else (xv, dyv, 'f')
+        mmap, cmap, s_m, s_c, Mp, Cp = self._form(f)
+        unpack = unpack and not self.direct_ok()
+        assert not (unpack and self.masked), 'masked jobs exist in the batched form only'
+        for li, l in enumerate(p[launches]):
+            g = self._launch_geom(p, f, li, xv.N, xv.H, xv.W, src.ld, dst.ld, tag)
+            self._wgrad_launch(p, li, l, xv.N, grad_w, lambda: nv.call(
+                'segnb_conv_wgrad', g, rt.code, src.ptr, dst.ptr, nv.ptr(p['dwp'][li]), p['nslab'][li], rt.stream),
+                scaled=self.transposed)
             if unpack:
-                nv.call('segnb_unpack_wgrad', nv.ptr(p['dwp'][li]), nv.ptr(gw), self.Cop, self.Cip, len(l.taps),
-                        self.s_out, self.s_in, p['tapoff_fwd'][li], nv.ptr(self.out_map), nv.ptr(self.in_map), 1,
-                        rt.stream)
+                nv.call('segnb_unpack_wgrad', nv.ptr(p['dwp'][li]), nv.ptr(grad_w), Mp, Cp, len(l.taps), s_m, s_c, p[tapoff][li],
+                        nv.ptr(mmap), nv.ptr(cmap), 1, rt.stream)
 
 
 class UpConvOp(ConvOp):
@@ -849,6 +846,7 @@ class UpConvOp(ConvOp):
     """
     T = ((2,), (1, 2), (0, 1), (0,))
     algo_scale = 9.0 / 4.0
+    masked = True           # (ConvOp's job records in its transposed naming; a tap word = mask(a, b) over the 3x3 parameter)
 
     def __init__(self, rt, weight, ci_real, ci_pad, need_dgrad=True, pack_fwd=True):
         co, ci_total, kh, kw = weight.shape
@@ -895,28 +893,8 @@ class UpConvOp(ConvOp):
     def pack(self, Hi, Wi):
         raise NotImplementedError('UpConvOp packs through the batched job table only (masked jobs)')
 
-    def pack_jobs(self, Hi, Wi):
-        p, rt = self.plan(Hi, Wi), self.rt
-        w = self.weight.detach()
-        jobs = []
-        for li, l in enumerate(p['fwd'] if self.pack_fwd else ()):
-            # ConvOp's transposed naming: the forward matrix is [Co][taps][Ci]
-            jobs.append(dict(w=w, packed=p['wp_fwd'][li], mmap=self.out_map, cmap=self.in_map, s_m=self.s_out,
-                             s_c=self.s_in, Mp=self.Cop, Cp=self.Cip, ntaps=len(l.taps), dtype=rt.code, masked=True, form='f',
-                             tap_off=[self.mask(a, b) for (_, _, a, b) in l.taps]))
-        if self.need_dgrad:
-            for li, l in enumerate(p['dg']):
-                jobs.append(dict(w=w, packed=p['wp_dg'][li], mmap=self.in_map, cmap=self.out_map, s_m=self.s_in,
-                                 s_c=self.s_out, Mp=self.Cip, Cp=self.Cop, ntaps=len(l.taps), dtype=rt.code, masked=True, form='d',
-                                 tap_off=[self.mask(a, b) for (_, _, a, b) in l.taps]))
-        return jobs
-
-    def unpack_jobs(self, Hi, Wi, grad_w):
-        p = self.plan(Hi, Wi)
-        return [dict(w=grad_w, packed=p['dwp'][li], mmap=self.in_map, cmap=self.out_map, s_m=self.s_in, s_c=self.s_out,
-                     Mp=self.Cip, Cp=self.Cop, ntaps=len(l.taps), dtype=nv.F32, masked=True,
-                     nslab=1,
-                     tap_off=[self.mask(a, b) for (_, _, a, b) in l.taps]) for li, l in enumerate(p['dg'])]
+    def _taps(self, l):
+        return [self.mask(a, b) for (_, _, a, b) in l.taps]
 
 
 class UpCatConvOp(object):
@@ -969,8 +947,7 @@ class UpCatConvOp(object):
         key = (N, H, W)
         v = self._seg.get(key)
         if v is None:
-            p = self.up.plan(H // 2, W // 2)
-            g = self.up._geom(p, 'd', 0, p['dg'][0], N, H, W, self.up.Cop, self.up.Cop, H // 2, W // 2, self.up.Cip, self.up.Cip)
+            _, g = self.up._single('d', N=N, H=H // 2, W=W // 2)        # (plans the up segment at this size, whatever the answer)
             v = self._seg[key] = (self.force_segmented or (self.force_thin and self.Cop <= 32 and W >= 64) or
                                   bool(nv.query('segnb_conv_fprop_upd_ok', g, self.rt.code)))
         return v
@@ -987,12 +964,7 @@ class UpCatConvOp(object):
         key = ('s', N, H, W)
         v = self._seg.get(key)
         if v is None:
-            p = self.full.plan(H, W)
-            v = False
-            if len(p['dg']) == 1 and p['dg_full']:
-                g = self.full._geom(p, 'd', 0, p['dg'][0], N, H, W, self.Cop, self.Cop, H, W, self.Cip, self.Cip)
-                v = bool(nv.query('segnb_conv_fprop_upsum_ok', g, self.rt.code, self.up_pad))
-            self._seg[key] = v
+            v = self._seg[key] = self.full._single_ok('segnb_conv_fprop_upsum_ok', 'd', N=N, H=H, W=W, extra=(self.up_pad,))
         return v
 
     def writes_du(self, N, H, W):
@@ -1025,9 +997,7 @@ class UpCatConvOp(object):
         key = ('v', N, H, W)
         v = self._seg.get(key)
         if v is None:
-            p = self.full.plan(H, W)
-            g = self.full._geom(p, 'f', 0, p['fwd'][0], N, H, W, self.full.Cip, self.full.Cip, H, W, self.full.Cop, self.full.Cop)
-            v = self._seg[key] = bool(nv.query('segnb_conv_upcat_ok', g, self.rt.code, self.up_pad))
+            v = self._seg[key] = self.full._single_ok('segnb_conv_upcat_ok', 'f', N=N, H=H, W=W, extra=(self.up_pad,))
         return v
 
     def reads_upsampled(self, N, H, W):
@@ -1041,13 +1011,11 @@ class UpCatConvOp(object):
         """Does anything read the low-resolution tensor itself?  (virtual concat, segmented forward or weight gradient)"""
         return self.virtual(N, H, W) or self.fwd_segmented(N, H, W) or self.segment_wgrad
 
-    def _upcat_args(self, xv):
-        """(geometry of the whole 9-tap convolution over the logical concat, skip view, segnb_upcat_src)"""
-        p = self.full.plan(xv.H, xv.W)
-        l = p['fwd'][0]
+    def _upcat_args(self, xv, yv):
+        """(plan, launch and geometry of the whole 9-tap convolution over the logical concat -> yv, skip view, segnb_upcat_src)"""
         sk = xv.slice(self.up_pad, self.sk_pad)
-        src = nv.UpcatSrc(self._u.ptr, self.up_pad, self._u.ld)
-        return p, l, sk, src
+        l, g = self.full._single('f', sk, yv, tag='fv')
+        return self.full.plan(xv.H, xv.W), l, g, sk, nv.UpcatSrc(self._u.ptr, self.up_pad, self._u.ld)
 
     _seg = None
     # thin output (<= 32 channels, the 224x224 level): the layer is HBM-bound on the 4x-sized upsampled gradient slice, and
@@ -1064,12 +1032,10 @@ class UpCatConvOp(object):
 
     def fprop(self, xv, yv, stats=None, epilogue=None):
         if epilogue is None and self._u is not None and self.virtual(xv.N, xv.H, xv.W):
-            p, l, sk, src = self._upcat_args(xv)
-            g = self.full._geom(p, 'fv', 0, l, xv.N, xv.H, xv.W, self.full.Cip, sk.ld, yv.H, yv.W, self.full.Cop, yv.ld)
-            b = self.bias.detach() if self.bias is not None else None
-            _timed('conv_fprop', 2.0 * xv.N * l.QH * l.QW * len(l.taps) * self.Ci * self.Co,
-                   lambda: nv.call('segnb_conv_fprop_upcat', g, self.rt.code, sk.ptr, src, nv.ptr(p['wp_fwd'][0]), nv.ptr(b),
-                                   self.Co if b is not None else 0, yv.ptr, nv.ptr(stats), self.rt.stream))
+            p, l, g, sk, src = self._upcat_args(xv, yv)
+            _timed('conv_fprop', self.full._flops(xv.N, l),
+                   lambda: nv.call('segnb_conv_fprop_upcat', g, self.rt.code, sk.ptr, src, nv.ptr(p['wp_fwd'][0]),
+                                   *self.full._bias_args(), yv.ptr, nv.ptr(stats), self.rt.stream))
             return
         if epilogue is None and self._u is not None and self.fwd_segmented(xv.N, xv.H, xv.W, yv.ld):
             # skip segment (with the bias) -> yv, then the upsampled segment added on the low-resolution tensor; the
@@ -1101,10 +1067,9 @@ class UpCatConvOp(object):
             assert self._du is not None
             f, rt = self.full, self.rt
             p = f.plan(dxv.H, dxv.W)
-            l = p['dg'][0]
-            g = f._geom(p, 'd', 0, l, dyv.N, dyv.H, dyv.W, self.Cop, dyv.ld, dxv.H, dxv.W, self.Cip, dxv.ld)
+            l, g = f._single('d', dyv, dxv)
             dst = nv.UpcatSrc(self._du.ptr, self.up_pad, self._du.ld)
-            _timed('conv_fprop', 2.0 * dyv.N * l.QH * l.QW * len(l.taps) * self.Ci * self.Co,
+            _timed('conv_fprop', f._flops(dyv.N, l),
                    lambda: nv.call('segnb_conv_fprop_upsum', g, rt.code, dyv.ptr, nv.ptr(p['wp_dg'][0]), dxv.ptr, dst, rt.stream))
             return
         if not self.segmented(dxv.N, dxv.H, dxv.W):
@@ -1116,16 +1081,9 @@ class UpCatConvOp(object):
     def wgrad(self, xv, dyv, grad_w, unpack=True):
         if not self.segment_wgrad and self._u is not None and self.virtual(xv.N, xv.H, xv.W):
             assert not unpack
-            p, l, sk, src = self._upcat_args(xv)
-            g = self.full._geom(p, 'fv', 0, l, xv.N, xv.H, xv.W, self.full.Cip, sk.ld, dyv.H, dyv.W, self.full.Cop, dyv.ld)
-
-            def launch():
-                if self.full.direct_ok():
-                    self.full._arm_target(p, 0, grad_w)
-                nv.call('segnb_conv_wgrad_upcat', g, self.rt.code, sk.ptr, src, dyv.ptr, nv.ptr(p['dwp'][0]), p['nslab'][0],
-                        self.rt.stream)
-            _timed('conv_wgrad', 2.0 * xv.N * l.QH * l.QW * len(l.taps) * self.Ci * self.Co,
-                   lambda: self.full._under_wg_share(launch))
+            p, l, g, sk, src = self._upcat_args(xv, dyv)
+            self.full._wgrad_launch(p, 0, l, xv.N, grad_w, lambda: nv.call(
+                'segnb_conv_wgrad_upcat', g, self.rt.code, sk.ptr, src, dyv.ptr, nv.ptr(p['dwp'][0]), p['nslab'][0], self.rt.stream))
             return
         if not self.segment_wgrad:
             return self.full.wgrad(xv, dyv, grad_w, unpack)
@@ -1140,11 +1098,11 @@ class UpCatConvOp(object):
         fseg = (self.fwd_segmented(N, H, W) and not self.virtual(N, H, W)) if N is not None else self.segment_fwd
         full, skip, up = self.full.pack_jobs(H, W), self.skip.pack_jobs(H, W), self.up.pack_jobs(H // 2, W // 2)
 
-        def pick(jobs, op, fwd):
-            return [j for j in jobs if (j['mmap'] is op.out_map) == fwd]
-        jobs = (pick(skip, self.skip, True) + pick(up, self.up, True)) if fseg else pick(full, self.full, True)
+        def pick(jobs, form):
+            return [j for j in jobs if j['form'] == form]
+        jobs = (pick(skip, 'f') + pick(up, 'f')) if fseg else pick(full, 'f')
         if self.need_dgrad:
-            jobs += (pick(skip, self.skip, False) + pick(up, self.up, False)) if dseg else pick(full, self.full, False)
+            jobs += (pick(skip, 'd') + pick(up, 'd')) if dseg else pick(full, 'd')
         return jobs
 
     def unpack_jobs(self, H, W, grad_w):
@@ -1202,30 +1160,11 @@ class PackTable(object):
                 if enb < 0 or j.get('masked') or j.get('nslab', 1) > 1:
                     self.singles.append(j)
                     continue
-                row = np.zeros((), dtype=PACK_JOB_DTYPE)
-                for f in ('w', 'packed', 'mmap', 'cmap'):
-                    row[f] = j[f].data_ptr()
-                    self._keep.append(j[f])
-                for f in ('s_m', 's_c', 'Mp', 'Cp', 'ntaps', 'dtype'):
-                    row[f] = j[f]
-                row['nslab'] = 1
-                row['tap_off'][:len(j['tap_off'])] = j['tap_off']
-                row['block_start'] = eblocks
+                erows.append(self._row(j, eblocks))          # (neither masked nor slabbed: checked above)
                 eblocks += enb
-                erows.append(row)
                 continue
-            row = np.zeros((), dtype=PACK_JOB_DTYPE)
-            for f in ('w', 'packed', 'mmap', 'cmap'):
-                row[f] = j[f].data_ptr()
-                self._keep.append(j[f])
-            for f in ('s_m', 's_c', 'Mp', 'Cp', 'ntaps', 'dtype'):
-                row[f] = j[f]
-            row['nslab'] = j.get('nslab', 1)
-            row['masked'] = 1 if j.get('masked') else 0
-            row['tap_off'][:len(j['tap_off'])] = j['tap_off']
-            row['block_start'] = blocks
+            rows.append(self._row(j, blocks))
             blocks += nb
-            rows.append(row)
         self.rt, self.entry, self.single_entry, self.n, self.blocks = rt, entry, single_entry, len(rows), blocks
         self.table = None
         if rows:
@@ -1236,6 +1175,20 @@ class PackTable(object):
         if erows:
             tab = np.array(erows, dtype=PACK_JOB_DTYPE)
             self.etable = torch.from_numpy(tab.view(np.uint8).reshape(-1).copy()).to(rt.device)
+
+    def _row(self, j, block_start):
+        """one PACK_JOB_DTYPE row of a table whose earlier rows take `block_start` blocks; the job's tensors are kept alive"""
+        row = np.zeros((), dtype=PACK_JOB_DTYPE)
+        for f in ('w', 'packed', 'mmap', 'cmap'):
+            row[f] = j[f].data_ptr()
+            self._keep.append(j[f])
+        for f in ('s_m', 's_c', 'Mp', 'Cp', 'ntaps', 'dtype'):
+            row[f] = j[f]
+        row['nslab'] = j.get('nslab', 1)
+        row['masked'] = 1 if j.get('masked') else 0
+        row['tap_off'][:len(j['tap_off'])] = j['tap_off']
+        row['block_start'] = block_start
+        return row
 
     # pair_pack = False (class attribute): every matrix by its own job (A/B)
     pair_pack = True
