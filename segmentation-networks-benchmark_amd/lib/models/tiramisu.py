@@ -26,7 +26,7 @@ from torch import nn
 
 from segnb import _native as nv
 from segnb import convplan as cp
-from segnb.engine import STAT_REPLICAS
+from segnb.bnpass import STAT_REPLICAS
 from segnb.net import Act, HipNet, bn_act, conv_unit, head_1x1, head_from_act
 
 

@@ -462,13 +462,13 @@ class _ZFUnetPlan(object):
         self._restore_stage_state(plan[1])
 
     def _stage_state(self):
-        return [(st, st._stats_stale, st._fused_fwd, getattr(st, '_saved', None))
+        return [(st, st.bnl.stats_left, st.bnl.fused_fwd, getattr(st, '_saved', None))
                 for n in ENCODER + DECODER for st in self.stages[n]]
 
     @staticmethod
     def _restore_stage_state(state):
         for st, stale, fused, saved in state:
-            st._stats_stale, st._fused_fwd, st._saved = stale, fused, saved
+            st.bnl.stats_left, st.bnl.fused_fwd, st._saved = stale, fused, saved
 
     # ---- forward ---------------------------------------------------------------------------------------
     def forward(self, x, train, need_grad):
@@ -510,9 +510,9 @@ class _ZFUnetPlan(object):
             # statistics a fused training forward left unconsumed are cleared here, outside the recorded list
             for n in ENCODER + DECODER:
                 for st in self.stages[n]:
-                    if st.bn is not None and train and st._stats_stale:
-                        st.stats.zero_()
-                        st._stats_stale = False
+                    if st.bn is not None and train and st.bnl.stats_left:
+                        st.bnl.stats.zero_()
+                        st.bnl.stats_left = False
             plan = self._cplans.get(ckey)
             self._guard_active = self._guard_f.begin()
             if plan is not None and plan[0] is not None:

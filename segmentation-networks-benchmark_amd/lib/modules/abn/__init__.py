@@ -3,7 +3,7 @@
 
 The reference delegates to the un-vendored ``inplace_abn`` CUDA extension (functions.py:1: mean_var / forward /
 edz_eydz / backward).  Here the same four phases are segnb_bn_stats + segnb_bn_finalize / segnb_bn_act_fwd /
-segnb_bn_act_bwd_reduce / segnb_bn_bwd_apply.  Inside LinkNet34 the module is only a parameter holder (the
+segnb_bn_act_bwd_reduce / segnb_bn_bwd_apply (launched through segnb.bnpass.BnLayer).  Inside LinkNet34 the module is only a parameter holder (the
 executor fuses BN + LeakyReLU behind each convolution); called on its own it runs the same kernels, with the NCHW <->
 NHWC moves as launches of the library too, and writes its result into the input's storage like the reference.
 
@@ -30,6 +30,8 @@ import torch.nn as nn
 
 from segnb import _native as nv
 from segnb import convplan as cp
+from segnb.bnpass import BnLayer
+from segnb.engine import View
 
 ACT_LEAKY_RELU, ACT_ELU, ACT_NONE = 'leaky_relu', 'elu', 'none'
 
@@ -58,18 +60,14 @@ class _ABNFn(torch.autograd.Function):
         dev, st = x.device, (torch.cuda.current_stream(x.device).cuda_stream if x.is_cuda else 0)
         y = torch.empty((N, H, W, Cp), dtype=torch.float32, device=dev)
         nv.call('segnb_pack_input_nchw', nv.ptr(x), N, C, H, W, nv.ptr(y), nv.F32, Cp, Cp, st)
-        stats = torch.zeros((16, 2, Cp), dtype=torch.float64, device=dev)
-        coef = torch.zeros((4, Cp), dtype=torch.float32, device=dev)
+        bnl = ctx.bnl = BnLayer(C, Cp, lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev), act, slope,
+                                lambda: (weight, bias, running_mean, running_var, None, eps, momentum), accumulate=0)
+        coef = bnl.coef
+        yv = View(y, N, H, W, Cp)
         if training:
-            nv.call('segnb_bn_stats', nv.F32, nv.ptr(y), Cp, N, H, W, Cp, nv.ptr(stats), st)
-        nv.call('segnb_bn_finalize', nv.ptr(stats), C, Cp, float(N * H * W),
-                nv.ptr(weight.detach() if weight is not None else None),
-                nv.ptr(bias.detach() if bias is not None else None), eps, momentum, nv.ptr(running_mean),
-                nv.ptr(running_var), None,
-                1 if training else 0, nv.ptr(coef), st)
+            bnl.stats_of(nv.F32, st, yv)
         out = torch.empty_like(y)
-        nv.call('segnb_bn_act_fwd', nv.F32, nv.ptr(y), Cp, N, H, W, Cp, nv.ptr(coef), act, slope, None, nv.ptr(out), Cp,
-                None, 0, None, 0, None, 0, st)
+        bnl.forward(nv.F32, st, yv, False, training, out=View(out, N, H, W, Cp))
         ctx.training = bool(training)
         ctx.save_for_backward(y, coef, weight if weight is not None else coef.new_empty(0),
                               w_param if (abs_form and w_param is not None) else coef.new_empty(0))
@@ -91,31 +89,24 @@ class _ABNFn(torch.autograd.Function):
         g = torch.empty((N, H, W, Cp), dtype=torch.float32, device=dev)
         nv.call('segnb_pack_input_nchw', nv.ptr(gout), N, C, H, W, nv.ptr(g), nv.F32, Cp, Cp, st)
         dz = torch.empty_like(g)
-        sums = torch.zeros((16, 2, Cp), dtype=torch.float64, device=dev)
-        bcoef = torch.zeros((3, Cp), dtype=torch.float32, device=dev)
         dgamma = torch.zeros(C, dtype=torch.float32, device=dev)
         dbeta = torch.zeros(C, dtype=torch.float32, device=dev)
         dx = torch.empty((N, C, H, W), dtype=torch.float32, device=dev)
-        nv.call('segnb_bn_act_bwd_reduce', nv.F32, nv.ptr(y), Cp, N, H, W, Cp, nv.ptr(coef), act, slope, None, nv.ptr(g),
-                Cp, None, 0, None, 0, nv.ptr(dz), Cp, nv.ptr(sums), None, 0, st)
+        bnl = ctx.bnl
+        bnl.params, bnl.grads = (lambda: (weight if affine else None,)), (lambda: (dgamma, dbeta))
+        yv, dzv = View(y, N, H, W, Cp), View(dz, N, H, W, Cp)
+        bnl.reduce(nv.F32, st, yv, View(g, N, H, W, Cp), dz=dzv)
         if not ctx.training:
             # inference-mode backward of the reference (functions.py:113-116: edz = eydz = 0): a plain affine map,
             # dx = dz * gamma * rstd; dgamma / dbeta are still the sums (the training formula is wrong here).
             # As launches: sums -> dgamma / dbeta, then dz scaled per channel by coef row 0 = gamma * rstd of the running
             # statistics (segnb_bn_act_fwd with a coefficient table whose shift row is zero, no activation)
-            nv.call('segnb_bn_bwd_finalize', nv.ptr(sums), C, Cp, float(N * H * W),
-                    nv.ptr(weight.detach() if affine else None), nv.ptr(coef), nv.ptr(bcoef), nv.ptr(dgamma),
-                    nv.ptr(dbeta), 0, st)
+            bnl.bwd_finalize(st, N * H * W)
             scale_only = torch.zeros_like(coef)
             scale_only[0].copy_(coef[0])
-            nv.call('segnb_bn_act_fwd', nv.F32, nv.ptr(dz), Cp, N, H, W, Cp, nv.ptr(scale_only), nv.ACT_NONE, 0.0, None,
-                    nv.ptr(dz), Cp, None, 0, None, 0, None, 0, st)
+            bnl.act_fwd(nv.F32, st, dzv, dzv, scale_only, nv.ACT_NONE, 0.0)
         else:
-            nv.call('segnb_bn_bwd_finalize', nv.ptr(sums), C, Cp, float(N * H * W),
-                    nv.ptr(weight.detach() if affine else None), nv.ptr(coef), nv.ptr(bcoef), nv.ptr(dgamma),
-                    nv.ptr(dbeta), 0, st)
-            nv.call('segnb_bn_bwd_apply', nv.F32, nv.ptr(y), Cp, N, H, W, Cp, nv.ptr(coef), nv.ptr(bcoef), nv.ptr(dz), Cp,
-                    nv.ptr(dz), Cp, None, C, st)
+            bnl.apply(nv.F32, st, yv, dzv, False, dz=dzv)
         nv.call('segnb_nhwc_to_nchw_f32', nv.F32, nv.ptr(dz), Cp, N, H, W, C, nv.ptr(dx), st)
         if ctx.abs_form:
             # d(|w| + eps)/dw as the backend signs it: +1 for w > 0, -1 otherwise

@@ -14,10 +14,8 @@ import torch
 
 from . import _native as nv
 from . import convplan as cp
+from .bnpass import BN_EPS, BN_MOMENTUM, FUSE_FINALIZE, BnLayer, module_params
 
-BN_EPS = 1e-5
-STAT_REPLICAS = 16     # SEGNB_STAT_REPLICAS
-BN_MOMENTUM = 0.1
 
 
 class KernelTimer(object):
@@ -1280,23 +1278,13 @@ class Stage(object):
     # of the source pass runs at 3 TB/s where the plain apply pass it replaces runs at 6.4 (profiles/r04_ab.txt).
     recompute_dz_min_mb = 0.0
 
+    fuse_finalize = FUSE_FINALIZE      # (bnpass.FUSE_FINALIZE: finalize folded into the activation / apply passes)
+
     def __init__(self, rt, conv, bn=None, act=nv.ACT_RELU, slope=0.01, name=''):
         self.rt, self.conv, self.bn, self.act, self.slope, self.name = rt, conv, bn, act, slope, name
         self.defer_unpack = False     # True: the model plan runs one batched unpack at the end of backward
-        # BatchNorm finalize folded into the activation / apply passes (segnb_bn_fwd_fused / _bwd_apply_fused): saves
-        # two 5 us launches per layer, but every block of the big kernel then starts with the same dependent
-        # statistics loads -- measured neutral on MI355X (7.47 vs 7.39 ms/step), so off by default
-        # finalize folded into the activation / apply passes: 44 launches of ~5 us less on the dependent chain
-        # (re-measured after the convolutions got faster: 5.71 -> 5.58 ms/step; neutral when first tried)
-        self.fuse_finalize = os.environ.get('SEGNB_FUSE_FINALIZE', '1') != '0'
-        self._stats_stale = False
-        self._fused_fwd = False
-        Cp = conv.Cop
-        self.C, self.Cp = conv.Co, Cp
-        self.stats = rt.zeros((STAT_REPLICAS, 2, Cp), torch.float64)   # consumed + re-zeroed by segnb_bn_finalize
-        self.sums = rt.zeros((STAT_REPLICAS, 2, Cp), torch.float64)    # consumed + re-zeroed by segnb_bn_bwd_finalize
-        self.coef = rt.zeros((4, Cp), torch.float32)
-        self.bcoef = rt.zeros((3, Cp), torch.float32)
+        self.C, self.Cp = conv.Co, conv.Cop
+        self.bnl = BnLayer(conv.Co, conv.Cop, rt.zeros, act, slope, module_params(bn, BN_EPS, BN_MOMENTUM) if bn is not None else None)
         self._bufs = {}
 
     def buffers(self, N, Ho, Wo):
@@ -1331,102 +1319,59 @@ class Stage(object):
         Ho, Wo = self.conv.out_hw(xv.H, xv.W)
         b = self.buffers(xv.N, Ho, Wo)
         yv = b['y']
+        bnl = self.bnl
         use_batch_stats = self.bn is not None and train
-        if use_batch_stats and self._stats_stale:
+        if use_batch_stats and bnl.stats_left:
             # the previous training-mode forward was fused (statistics left unconsumed) and no backward cleared them
-            self.stats.zero_()
-            self._stats_stale = False
+            bnl.stats.zero_()
+            bnl.stats_left = False
         if (not need_grad and not use_batch_stats and u8 is None and out is not None and pool_out is None and up_out is None
                 and dropmul is None and self.conv.act_epilogue_ok(xv.H, xv.W)):
             # inference (validate(), tiled prediction): eval-mode BatchNorm and the activation in the convolution's epilogue --
             # the activated output goes straight to `out`, no BatchNorm pass at all
             coef = None
             if self.bn is not None:
-                bn = self.bn
-                nv.call('segnb_bn_finalize', nv.ptr(self.stats), self.C, self.Cp, float(xv.N * Ho * Wo),
-                        nv.ptr(bn.weight.detach()), nv.ptr(bn.bias.detach()), BN_EPS, BN_MOMENTUM,
-                        nv.ptr(bn.running_mean), nv.ptr(bn.running_var), nv.ptr(bn.num_batches_tracked), 0,
-                        nv.ptr(self.coef), rt.stream)
-                coef = self.coef
+                bnl.finalize(rt.stream, xv.N * Ho * Wo, False)
+                coef = bnl.coef
             self.conv.fprop(xv, out, None, epilogue=(coef, self.act, self.slope))
             self._saved = None
             return out
         self._x_tf = x_tf
         if u8 is not None:
-            self.conv.fprop_u8(u8[0], u8[1], yv, self.stats if use_batch_stats else None, xv if need_grad else None)
+            self.conv.fprop_u8(u8[0], u8[1], yv, bnl.stats if use_batch_stats else None, xv if need_grad else None)
         elif x_tf is not None:
-            self.conv.fprop_tf(xv, x_tf, yv, self.stats if use_batch_stats else None)
+            self.conv.fprop_tf(xv, x_tf, yv, bnl.stats if use_batch_stats else None)
         else:
-            self.conv.fprop(xv, yv, self.stats if use_batch_stats else None)
-        coef = None
+            self.conv.fprop(xv, yv, bnl.stats if use_batch_stats else None)
         fused = use_batch_stats and self.fuse_finalize and need_grad
+        self._saved = (xv, yv, dropmul, self.bn is not None)
         if defer_act == 'head':
             # the network's last layer: its activation pass is launched by the plan together with the classifier behind it
             # (head_forward: segnb_bn_fwd_fused_head), outside any recorded list -- the logits go to a fresh tensor
             assert fused and pool_out is None and up_out is None
-            self._stats_stale = True
-            self._saved = (xv, yv, dropmul, True)
-            self._fused_fwd = True
-            return yv
-        if defer_act:
+            bnl.stats_left = bnl.fused_fwd = True
+        elif defer_act:
             assert fused and dropmul is None and pool_out is None and up_out is None
-            bn = self.bn
-            nv.call('segnb_bn_finalize_keep', nv.ptr(self.stats), self.C, self.Cp, float(xv.N * Ho * Wo),
-                    nv.ptr(bn.weight.detach()), nv.ptr(bn.bias.detach()), BN_EPS, BN_MOMENTUM, nv.ptr(bn.running_mean),
-                    nv.ptr(bn.running_var), nv.ptr(bn.num_batches_tracked), nv.ptr(self.coef), nv.ptr(self.sums), rt.stream)
-            self._stats_stale = True
-            self._saved = (xv, yv, None, True)
-            self._fused_fwd = True
-            return yv
-        if fused:
-            # finalize folded into the activation pass (one launch less per layer and direction); the statistics are
-            # cleared by this layer's backward (segnb_bn_bwd_apply_fused), the backward sums here
-            bn = self.bn
-            nv.call('segnb_bn_fwd_fused', rt.code, yv.ptr, yv.ld, xv.N, Ho, Wo, self.C, self.Cp, nv.ptr(self.stats),
-                    nv.ptr(bn.weight.detach()), nv.ptr(bn.bias.detach()), BN_EPS, BN_MOMENTUM,
-                    nv.ptr(bn.running_mean), nv.ptr(bn.running_var), nv.ptr(bn.num_batches_tracked),
-                    nv.ptr(self.coef), nv.ptr(self.sums), self.act, self.slope, nv.ptr(dropmul), vptr(out), vld(out),
-                    vptr(pool_out), vld(pool_out), vptr(up_out), vld(up_out), None, 0, rt.stream)
-            self._stats_stale = True
-            self._saved = (xv, yv, dropmul, True)
-            self._fused_fwd = True
-            return yv
-        self._fused_fwd = False
-        if self.bn is not None:
-            bn = self.bn
-            nv.call('segnb_bn_finalize', nv.ptr(self.stats), self.C, self.Cp, float(xv.N * Ho * Wo),
-                    nv.ptr(bn.weight.detach()), nv.ptr(bn.bias.detach()), BN_EPS, BN_MOMENTUM,
-                    nv.ptr(bn.running_mean), nv.ptr(bn.running_var), nv.ptr(bn.num_batches_tracked),
-                    1 if train else 0, nv.ptr(self.coef), rt.stream)
-            coef = self.coef
-        nv.call('segnb_bn_act_fwd', rt.code, yv.ptr, yv.ld, xv.N, Ho, Wo, self.Cp, nv.ptr(coef), self.act,
-                self.slope, nv.ptr(dropmul), vptr(out), vld(out), vptr(pool_out), vld(pool_out), vptr(up_out),
-                vld(up_out), None, 0, rt.stream)
-        self._saved = (xv, yv, dropmul, coef is not None)
+            bnl.finalize_keep(rt.stream, xv.N * Ho * Wo)
+        else:
+            bnl.forward(rt.code, rt.stream, yv, fused, train, dropmul, out, pool_out, up_out)
         return yv
 
     def head_forward(self, head_w, head_b, K, logits, out=None):
         """BatchNorm (finalize folded in) + activation (+ Dropout2d) of this stage's convolution output AND the 1x1 classifier on
         the activated values, one launch (after forward(..., defer_act='head')); out: optional View for the activated tensor."""
-        rt, bn = self.rt, self.bn
         xv, yv, dropmul, _ = self._saved
-        nv.call('segnb_bn_fwd_fused_head', rt.code, yv.ptr, yv.ld, yv.N, yv.H, yv.W, self.C, self.Cp, nv.ptr(self.stats),
-                nv.ptr(bn.weight.detach()), nv.ptr(bn.bias.detach()), BN_EPS, BN_MOMENTUM, nv.ptr(bn.running_mean),
-                nv.ptr(bn.running_var), nv.ptr(bn.num_batches_tracked), nv.ptr(self.coef), nv.ptr(self.sums), self.act,
-                self.slope, nv.ptr(dropmul), vptr(out), vld(out), nv.ptr(head_w), nv.ptr(head_b), K, nv.ptr(logits), rt.stream)
+        self.bnl.forward(self.rt.code, self.rt.stream, yv, True, True, dropmul, out, head=(head_w, head_b, K, logits))
 
     def head_backward(self, head_w, K, dlogits, dw, db):
         """d(logits) through the classifier, this stage's activation / Dropout2d and its BatchNorm-backward reduction in one pass
         over y (segnb_head_bn_bwd): leaves dz in the stage's buffer and the sums complete -- backward(..., dz_ready=True) next."""
-        rt = self.rt
         xv, yv, dropmul, _ = self._saved
         dz = self.buffers(yv.N, yv.H, yv.W)['dz']
         # head_dz_recompute: dz is NOT stored -- backward(dz_ready=True) recomputes it from d(logits) and y inside the apply pass
         # (segnb_head_bn_bwd_apply): one tensor write and one tensor read less at the network's full resolution
         self._head_src = (head_w, K, dlogits) if (self.head_dz_recompute and self.bn is not None and self.fuse_finalize) else None
-        nv.call('segnb_head_bn_bwd', rt.code, yv.ptr, yv.ld, yv.N, yv.H, yv.W, self.C, self.Cp, nv.ptr(self.coef), self.act,
-                self.slope, nv.ptr(dropmul), nv.ptr(head_w), K, nv.ptr(dlogits), None if self._head_src is not None else dz.ptr,
-                dz.ld, nv.ptr(self.sums), nv.ptr(dw), nv.ptr(db), rt.stream)
+        self.bnl.head_reduce(self.rt.code, self.rt.stream, yv, dropmul, head_w, K, dlogits, dz, self._head_src is None, dw, db)
 
     # head_dz_recompute = False (class attribute / SEGNB_HEAD_DZ=0): the last layer's dz is stored by segnb_head_bn_bwd and read back (A/B)
     head_dz_recompute = os.environ.get('SEGNB_HEAD_DZ', '1') != '0'
@@ -1434,16 +1379,16 @@ class Stage(object):
 
     def tf_out(self):
         """the operand transform a consumer applies to this stage's pre-BatchNorm output (after forward(..., defer_act=True))"""
-        return ConvOp.tf_act(self.coef, self.Cp, self.act, self.slope)
+        return ConvOp.tf_act(self.bnl.coef, self.Cp, self.act, self.slope)
 
     def reduce_in_producer(self):
         """-> the (y, coef, sums, act, slope) a data-gradient launch needs to do THIS layer's BatchNorm-backward
         reduction in its epilogue, or None when the layer does not qualify (it must be a 'direct' layer: BatchNorm,
         one direct gradient source, no dropout; the caller guarantees the single direct source)."""
         xv, yv, dropmul, has_bn = self._saved
-        if not (self.direct_apply and has_bn and dropmul is None and self._fused_fwd):
+        if not (self.direct_apply and has_bn and dropmul is None and self.bnl.fused_fwd):
             return None
-        return (yv, self.coef, self.sums, self.act, self.slope)
+        return self.bnl.producer(yv)
 
     def backward(self, grads, g_direct=None, g_pool=None, g_up=None, dx=None, reduced=False, fuse_reduce_of=None,
                  dz_ready=False):
@@ -1451,10 +1396,12 @@ class Stage(object):
         input gradient, or None (first layer).  reduced: the reduction pass of this layer was already done by the
         data-gradient launch that produced g_direct.  fuse_reduce_of: the Stage whose activation gradient dx is -- if
         it qualifies, this layer's data gradient does that stage's reduction too; returns True when it did."""
-        rt = self.rt
+        rt, bnl = self.rt, self.bnl
         xv, yv, dropmul, has_bn = self._saved
         dz = self.buffers(yv.N, yv.H, yv.W)['dz']
-        coef = self.coef if has_bn else None
+        fused = has_bn and bnl.fused_fwd
+        if has_bn:
+            bnl.grads = lambda: (grads.grad_of(self.bn.weight), grads.grad_of(self.bn.bias))
         # A single direct gradient source, no dropout: dz never goes to memory -- the reduce pass only sums, the apply
         # pass recomputes dz from g (segnb_bn_bwd_apply_direct): one tensor write less per such layer.
         # dz_ready: head_backward() already left dz in the buffer and completed the sums (no gradient source tensor at all)
@@ -1462,74 +1409,33 @@ class Stage(object):
                   and dropmul is None and not dz_ready)
         assert not reduced or direct, 'only a direct layer can be reduced by its producer'
         mb = yv.N * yv.H * yv.W * self.Cp * (2 if rt.code == nv.BF16 else 4) / 1e6
-        recompute = (not direct and not dz_ready and has_bn and self._fused_fwd and self.recompute_dz_min_mb > 0
-                     and mb >= self.recompute_dz_min_mb)
+        recompute = (not direct and not dz_ready and fused and self.recompute_dz_min_mb > 0 and mb >= self.recompute_dz_min_mb)
         if not reduced and not dz_ready:
-            nv.call('segnb_bn_act_bwd_reduce', rt.code, yv.ptr, yv.ld, yv.N, yv.H, yv.W, self.Cp, nv.ptr(coef),
-                    self.act, self.slope, nv.ptr(dropmul), vptr(g_direct), vld(g_direct), vptr(g_pool), vld(g_pool),
-                    vptr(g_up), vld(g_up), None if (direct or recompute) else dz.ptr, dz.ld, nv.ptr(self.sums), None, 0,
-                    rt.stream)
-        count = float(yv.N * yv.H * yv.W)
-        gbias = grads.grad_of(self.conv.bias) if self.conv.bias is not None else None
-        if (dx is None and direct and self._fused_fwd and self.defer_unpack
+            bnl.reduce(rt.code, rt.stream, yv, g_direct, None, g_pool, g_up, dropmul, dz, store=not (direct or recompute))
+        count = yv.N * yv.H * yv.W
+        if (dx is None and direct and fused and self.defer_unpack
                 and isinstance(self.conv, ConvOp) and self.conv.wgrad_bnapply_ok(xv, yv)):
             # FIRST layer of the network: no data gradient, so the only reader of dy is this layer's weight gradient -- it
             # recomputes dy from (g, y) while staging its tiles (segnb_conv_wgrad_bnapply): the apply pass and its tensor are
             # gone from the serial tail of backward (a 5 us finalize instead of a full pass over the largest activation)
-            nv.call('segnb_bn_bwd_finalize_clear', nv.ptr(self.sums), self.C, self.Cp, count, nv.ptr(self.bn.weight.detach()),
-                    nv.ptr(self.coef), nv.ptr(self.bcoef), nv.ptr(grads.grad_of(self.bn.weight)),
-                    nv.ptr(grads.grad_of(self.bn.bias)), 1, nv.ptr(self.stats), rt.stream)
-            self._stats_stale = False
-            self.conv.wgrad_bnapply(xv, g_direct, yv, self.coef, self.bcoef, self.act, self.slope,
+            bnl.bwd_finalize(rt.stream, count, clear_stats=True)
+            self.conv.wgrad_bnapply(xv, g_direct, yv, bnl.coef, bnl.bcoef, self.act, self.slope,
                                     grad_w=grads.grad_of(self.conv.weight))
             return False
         # the weight gradient is forked to the side stream right behind the apply pass: its event rides on that launch
         if self.defer_unpack and dx is not None and rt.side_stream() is not None:
             rt.arm_fork()
-        if dz_ready and self._head_src is not None and has_bn and self._fused_fwd:
-            head_w, K, dlogits = self._head_src
-            nv.call('segnb_head_bn_bwd_apply', rt.code, yv.ptr, yv.ld, yv.N, yv.H, yv.W, self.C, self.Cp, nv.ptr(self.coef),
-                    nv.ptr(self.sums), nv.ptr(self.bn.weight.detach()), nv.ptr(self.bcoef), nv.ptr(grads.grad_of(self.bn.weight)),
-                    nv.ptr(grads.grad_of(self.bn.bias)), 1, nv.ptr(self.stats), self.act, self.slope, nv.ptr(dropmul),
-                    nv.ptr(head_w), K, nv.ptr(dlogits), dz.ptr, dz.ld, rt.stream)
-            self._stats_stale = False
-        elif has_bn and self._fused_fwd and direct:
-            nv.call('segnb_bn_bwd_apply_fused_direct', rt.code, yv.ptr, yv.ld, yv.N, yv.H, yv.W, self.C, self.Cp,
-                    nv.ptr(self.coef), nv.ptr(self.sums), nv.ptr(self.bn.weight.detach()), nv.ptr(self.bcoef),
-                    nv.ptr(grads.grad_of(self.bn.weight)), nv.ptr(grads.grad_of(self.bn.bias)), 1,
-                    nv.ptr(self.stats), self.act, self.slope, g_direct.ptr, g_direct.ld, dz.ptr, dz.ld, rt.stream)
-            self._stats_stale = False
+        if not has_bn:
+            # no BatchNorm: dy = dz, d(bias) = sum dz
+            bnl.bwd_finalize(rt.stream, count, gbias=grads.grad_of(self.conv.bias) if self.conv.bias is not None else None)
+        elif dz_ready and self._head_src is not None and fused:
+            bnl.apply(rt.code, rt.stream, yv, dz, True, head=(dropmul,) + self._head_src)
+        elif direct:
+            bnl.apply(rt.code, rt.stream, yv, dz, fused, g=g_direct)
         elif recompute:
-            nv.call('segnb_bn_bwd_apply_fused_src', rt.code, yv.ptr, yv.ld, yv.N, yv.H, yv.W, self.C, self.Cp,
-                    nv.ptr(self.coef), nv.ptr(self.sums), nv.ptr(self.bn.weight.detach()), nv.ptr(self.bcoef),
-                    nv.ptr(grads.grad_of(self.bn.weight)), nv.ptr(grads.grad_of(self.bn.bias)), 1, nv.ptr(self.stats),
-                    self.act, self.slope, nv.ptr(dropmul), vptr(g_direct), vld(g_direct), vptr(g_pool), vld(g_pool),
-                    vptr(g_up), vld(g_up), dz.ptr, dz.ld, rt.stream)
-            self._stats_stale = False
-        elif has_bn and self._fused_fwd:
-            nv.call('segnb_bn_bwd_apply_fused', rt.code, yv.ptr, yv.ld, yv.N, yv.H, yv.W, self.C, self.Cp,
-                    nv.ptr(self.coef), nv.ptr(self.sums), nv.ptr(self.bn.weight.detach()), nv.ptr(self.bcoef),
-                    nv.ptr(grads.grad_of(self.bn.weight)), nv.ptr(grads.grad_of(self.bn.bias)), 1,
-                    nv.ptr(self.stats), dz.ptr, dz.ld, dz.ptr, dz.ld, rt.stream)
-            self._stats_stale = False
-        elif has_bn:
-            nv.call('segnb_bn_bwd_finalize', nv.ptr(self.sums), self.C, self.Cp, count,
-                    nv.ptr(self.bn.weight.detach()), nv.ptr(self.coef), nv.ptr(self.bcoef),
-                    nv.ptr(grads.grad_of(self.bn.weight)), nv.ptr(grads.grad_of(self.bn.bias)), 1, rt.stream)
-            # d(loss)/d(conv bias) under training-mode BatchNorm is identically zero (BN subtracts the batch mean):
-            # sum(dy) = A*(sum dz - n*mean(dz) - mean(dz*yhat)*sum(yhat)) = 0.  The reference's fp32 value is pure
-            # summation noise (~1e-7 of the weight-gradient scale); the flat gradient buffer already holds 0.
-            if direct:
-                nv.call('segnb_bn_bwd_apply_direct', rt.code, yv.ptr, yv.ld, yv.N, yv.H, yv.W, self.Cp,
-                        nv.ptr(self.coef), nv.ptr(self.bcoef), self.act, self.slope, g_direct.ptr, g_direct.ld,
-                        dz.ptr, dz.ld, None, self.C, rt.stream)
-            else:
-                nv.call('segnb_bn_bwd_apply', rt.code, yv.ptr, yv.ld, yv.N, yv.H, yv.W, self.Cp, nv.ptr(self.coef),
-                        nv.ptr(self.bcoef), dz.ptr, dz.ld, dz.ptr, dz.ld, None, self.C, rt.stream)
+            bnl.apply(rt.code, rt.stream, yv, dz, True, src=(dropmul, g_direct, g_pool, g_up))
         else:
-            # no BatchNorm: dy = dz, d(bias) = sum dz (accumulated through the dbeta slot)
-            nv.call('segnb_bn_bwd_finalize', nv.ptr(self.sums), self.C, self.Cp, count, None, nv.ptr(self.coef),
-                    nv.ptr(self.bcoef), None, nv.ptr(gbias), 1, rt.stream)
+            bnl.apply(rt.code, rt.stream, yv, dz, fused, dz=dz)
         x_tf = getattr(self, '_x_tf', None)
 
         def wgrad(unpack):

@@ -21,8 +21,8 @@ from torch import nn
 
 from . import _native as nv
 from . import convplan as cp
-from .engine import (BN_EPS, BN_MOMENTUM, STAT_REPLICAS, ConvOp, FlatParams, InputNorm, PackTable, Runtime, View,
-                     pack_input, vld, vptr)
+from .bnpass import FUSE_FINALIZE, BnLayer, module_params, stats_into
+from .engine import ConvOp, FlatParams, InputNorm, PackTable, Runtime, View, pack_input, vld, vptr
 from .launchlist import Recorder
 
 
@@ -123,9 +123,7 @@ class Tape(object):
             self.wg_cu_pct = int(os.environ['SEGNB_WG_CU_PCT'])
         self.lazy_add = bool(getattr(module, 'lazy_add', False))
 
-    # BatchNorm finalize folded into the activation / apply launches of a differentiated training forward (one launch less
-    # per layer and direction; A/B: SEGNB_FUSE_FINALIZE=0)
-    fuse_finalize = os.environ.get('SEGNB_FUSE_FINALIZE', '1') != '0'
+    fuse_finalize = FUSE_FINALIZE      # (bnpass.FUSE_FINALIZE; here only in a differentiated training forward)
 
     def fuses_finalize(self):
         return self.fuse_finalize and self.train and self.need_grad
@@ -396,14 +394,13 @@ class Tape(object):
     # batch_bias = False (class attribute): one segnb_bn_bwd_finalize launch per bias gradient (A/B)
     batch_bias = True
 
-    def defer_bias_grad(self, sums, C, Cp, gb, count, coef_buf, bcoef):
-        """The bias gradient of a convolution without BatchNorm (sum of dz, accumulated in `sums` by the reduction pass): joined to
-        the ONE segnb_bias_grad_multi launch that goes with the next batched unpack (nothing reads a bias gradient earlier)."""
+    def defer_bias_grad(self, bnl, gb, count):
+        """The bias gradient of a convolution without BatchNorm (sum of dz, accumulated in the layer's sums by the reduction pass):
+        joined to the ONE segnb_bias_grad_multi launch that goes with the next batched unpack (nothing reads a bias gradient earlier)."""
         if not self.batch_bias:
-            nv.call('segnb_bn_bwd_finalize', nv.ptr(sums), C, Cp, count, None, nv.ptr(coef_buf), nv.ptr(bcoef), None, nv.ptr(gb), 1,
-                    self.rt.stream)
+            bnl.bwd_finalize(self.rt.stream, count, gbias=gb)
             return
-        self._bias_pending.append((sums, C, Cp, gb))
+        self._bias_pending.append((bnl.sums, bnl.C, bnl.Cp, gb))
 
     def _run_bias_grads(self, group):
         """-> the (job table, job count) launched, or None.  The caller keeps it: a replayed backward launches the same table
@@ -477,11 +474,6 @@ class Tape(object):
 # ------------------------------------------------------------------------------------------------------------
 # layer helpers
 # ------------------------------------------------------------------------------------------------------------
-def _bn_fields(bn):
-    return (bn.weight, bn.bias, bn.running_mean, bn.running_var, getattr(bn, 'num_batches_tracked', None),
-            float(getattr(bn, 'eps', BN_EPS)), float(getattr(bn, 'momentum', BN_MOMENTUM) or BN_MOMENTUM))
-
-
 def _data_gradient(tape, conv, x, dy, site):
     """dx of a convolution handed to its input.  When the input is the activated BatchNorm output of ONE convolution and this
     is its only consumer (Act.producer / .consumers), the launch's epilogue also does that layer's BatchNorm-backward reduction
@@ -514,12 +506,6 @@ def _data_gradient(tape, conv, x, dy, site):
     else:
         conv.dgrad(dy, dx)
     tape.contribute(x, dx)
-
-
-def _sum_into(tape, v, out_stats):
-    """statistics of View v into the channel range out_stats = (table, element offset, row stride) (segnb_bn_stats_ld)"""
-    table, off, ld = out_stats
-    nv.call('segnb_bn_stats_ld', tape.rt.code, v.ptr, v.ld, v.N, v.H, v.W, v.Cp, nv.ptr(table, off), ld, tape.rt.stream)
 
 
 def conv_unit(tape, x, weight, bias, in_segments, stride=1, pad=1, transposed=False, bn=None, act=nv.ACT_RELU,
@@ -555,28 +541,25 @@ def conv_unit(tape, x, weight, bias, in_segments, stride=1, pad=1, transposed=Fa
     Ho, Wo = conv.out_hw(xv.H, xv.W)
     N, Cp, C = xv.N, conv.Cop, conv.Co
     y = tape.view(site + '/y', N, Ho, Wo, Cp)
-    stats = tape.small(site + '/stats', (STAT_REPLICAS, 2, Cp), torch.float64)
-    coef_buf = tape.small(site + '/coef', (4, Cp), torch.float32)
     has_bn = bn is not None
     use_batch_stats = has_bn and tape.train
     # InPlaceABN with the backend's affine form (lib/modules/abn: affine_form='abs_eps'): the kernels take |w| + eps as gamma
     # and hand dgamma to a scratch vector that segnb_abn_dscale signs into the parameter's gradient
     abs_form = has_bn and getattr(bn, 'affine_form', 'gamma') == 'abs_eps' and bn.weight is not None
 
-    def eff_gamma():
-        if not abs_form:
-            return bn.weight.detach()
-        geff = tape.small(site + '/geff', (C,), torch.float32)
-        nv.call('segnb_abn_scale', nv.ptr(bn.weight.detach()), float(bn.eps), nv.ptr(geff), C, rt.stream)
-        return geff
-
-    def dgamma_target():
-        return tape.small(site + '/dgeff', (C,), torch.float32) if abs_form else tape.flat.grad_of(bn.weight)
-
-    def dgamma_done():
-        if abs_form:
-            nv.call('segnb_abn_dscale', nv.ptr(bn.weight.detach()), nv.ptr(tape.small(site + '/dgeff', (C,), torch.float32)),
-                    nv.ptr(tape.flat.grad_of(bn.weight)), C, rt.stream)
+    def make_bnl():
+        params = grads = None
+        if has_bn:
+            params = module_params(bn)
+            grads = lambda: (tape.flat.grad_of(bn.weight), tape.flat.grad_of(bn.bias))
+            if abs_form:      # gamma: the effective scale (written by eff_gamma() in the forward); dgamma: its scratch vector
+                geff, dgeff = (tape.small(site + k, (C,), torch.float32) for k in ('/geff', '/dgeff'))
+                params = lambda: (geff,) + module_params(bn)()[1:]
+                grads = lambda: (dgeff, tape.flat.grad_of(bn.bias))
+        return BnLayer(C, Cp, rt.zeros, act, slope, params, grads)
+    bnl = tape.cached(site + '/bn', make_bnl)
+    stats = bnl.stats
+    eff_gamma = lambda: abs_form and nv.call('segnb_abn_scale', nv.ptr(bn.weight.detach()), float(bn.eps), nv.ptr(bnl.params()[0]), C, rt.stream)
     # activation in the convolution's epilogue (segnb_conv_fprop_act): no BatchNorm (unet16.py:12-21, the linknet head), or
     # BatchNorm in inference -- with no residual, dropout or fused pooling in the way.  The backward of the no-BatchNorm
     # form reads the ACTIVATED tensor where it read the raw one: act'(z) has the sign of act(z).
@@ -590,10 +573,9 @@ def conv_unit(tape, x, weight, bias, in_segments, stride=1, pad=1, transposed=Fa
     if fuse:
         coef = None
         if has_bn:
-            gamma, beta, rm, rv, nbt, eps, mom = _bn_fields(bn)
-            nv.call('segnb_bn_finalize', nv.ptr(stats), C, Cp, float(N * Ho * Wo), nv.ptr(eff_gamma()),
-                    nv.ptr(beta.detach()), eps, mom, nv.ptr(rm), nv.ptr(rv), nv.ptr(nbt), 0, nv.ptr(coef_buf), rt.stream)
-            coef = coef_buf
+            eff_gamma()
+            bnl.finalize(rt.stream, N * Ho * Wo, False)
+            coef = bnl.coef
         ov = ov_direct if ov_direct is not None else tape.view(site + '/a', N, Ho, Wo, Cp)
         conv.fprop(xv, ov, None, epilogue=(coef, act, slope))
         pv = None
@@ -601,20 +583,18 @@ def conv_unit(tape, x, weight, bias, in_segments, stride=1, pad=1, transposed=Fa
             pv = pool_out if pool_out is not None else tape.view(site + '/p', N, Ho // 2, Wo // 2, Cp)
             nv.call('segnb_maxpool_fwd', rt.code, ov.ptr, ov.ld, N, Ho, Wo, Cp, 2, 2, 0, pv.ptr, pv.ld, None, rt.stream)
         if out_stats is not None:
-            _sum_into(tape, pv if pool else ov, out_stats)
+            stats_into(rt.code, rt.stream, pv if pool else ov, out_stats)
         oa = Act(ov)
         pa = Act(pv) if pool else None
         if not has_bn and tape.need_grad and not pool:
             # (sums: zero between steps -- segnb_bias_grad_multi clears what it reads)
-            oa.producer = (ov, None, tape.small(site + '/sums', (STAT_REPLICAS, 2, Cp), torch.float64), act, slope)
+            oa.producer = bnl.producer(ov)
 
         def backward_fused():
             gp = pa.g if pa is not None else None
             if oa._g is None and gp is None:
                 return
             flat = tape.flat
-            sums = tape.small(site + '/sums', (STAT_REPLICAS, 2, Cp), torch.float64)
-            bcoef = tape.small(site + '/bcoef', (3, Cp), torch.float32)
             if oa.g_is_dz:
                 # the one consumer wrote dz = g * act'(a) and summed it (head_conv: segnb_head_conv_bwd)
                 oa.g_is_dz = False
@@ -626,14 +606,8 @@ def conv_unit(tape, x, weight, bias, in_segments, stride=1, pad=1, transposed=Fa
                 # the weight gradient's fork: its event rides on this dispatch, engine.Runtime.arm_fork); the pooled gradient is
                 # routed to the window's first maximum of a, as the forward's pooling pass chose it
                 (rt.arm_fork() if forks else None)
-                if g2 is not None:
-                    nv.call('segnb_bn_act_bwd_reduce_add', rt.code, ov.ptr, ov.ld, N, Ho, Wo, Cp, None, act, slope, None,
-                            g1.ptr, g1.ld, g2.ptr, g2.ld, dz.ptr, dz.ld, nv.ptr(sums), None, 0, rt.stream)
-                else:
-                    nv.call('segnb_bn_act_bwd_reduce', rt.code, ov.ptr, ov.ld, N, Ho, Wo, Cp, None, act, slope, None,
-                            vptr(g1), vld(g1), vptr(gp), vld(gp), None, 0, dz.ptr, dz.ld, nv.ptr(sums), None, 0, rt.stream)
-            gb = flat.grad_of(bias) if bias is not None else None
-            tape.defer_bias_grad(sums, C, Cp, gb, float(N * Ho * Wo), coef_buf, bcoef)
+                bnl.reduce(rt.code, rt.stream, ov, g1, g2, gp, dz=dz)
+            tape.defer_bias_grad(bnl, flat.grad_of(bias) if bias is not None else None, N * Ho * Wo)
             side = rt.fork_side() if forks else None
             if side is not None:
                 with torch.cuda.stream(side):
@@ -656,47 +630,27 @@ def conv_unit(tape, x, weight, bias, in_segments, stride=1, pad=1, transposed=Fa
         conv.fprop_drop(xv, ov, dropmul, out_stats)
         out_stats = None
         y = ov                  # (the reduction pass of the backward takes y for act'(z) only: ACT_NONE never reads it)
-        coef, pv, fused_bn = None, None, False
+        pv, fused_bn = None, False
     else:
         conv.fprop(xv, y, stats if use_batch_stats else None)
-        coef = None
         ov = out if out is not None else tape.view(site + '/a', N, Ho, Wo, Cp)
         pv = (pool_out if pool_out is not None else tape.view(site + '/p', N, Ho // 2, Wo // 2, Cp)) if pool else None
         fused_bn = has_bn and tape.fuses_finalize()
+        # fused_bn: finalize + activation pass in one launch (the statistics stay for this layer's backward to clear); otherwise
+        # the pass that writes the slice also sums it where it can (out_stats)
+        eff_gamma()
+        if bnl.forward(rt.code, rt.stream, y, fused_bn, tape.train, dropmul, ov, pv, res=None if res is None else res.v,
+                       out_stats=out_stats):
+            out_stats = None
         if fused_bn:
-            # finalize + activation pass in one launch; the statistics stay for this layer's backward to clear, the
-            # backward sums are cleared here (segnb_bn_fwd_fused / segnb_bn_bwd_apply_fused, include/segnb_hip.h)
-            gamma, beta, rm, rv, nbt, eps, mom = _bn_fields(bn)
-            sums_f = tape.small(site + '/sums', (STAT_REPLICAS, 2, Cp), torch.float64)
-            nv.call('segnb_bn_fwd_fused', rt.code, y.ptr, y.ld, N, Ho, Wo, C, Cp, nv.ptr(stats), nv.ptr(eff_gamma()),
-                    nv.ptr(beta.detach()), eps, mom, nv.ptr(rm), nv.ptr(rv), nv.ptr(nbt), nv.ptr(coef_buf), nv.ptr(sums_f),
-                    act, slope, nv.ptr(dropmul), ov.ptr, ov.ld, vptr(pv), vld(pv), None, 0,
-                    None if res is None else res.v.ptr, 0 if res is None else res.v.ld, rt.stream)
             tape.note_fused_stats(stats)
-            coef = coef_buf
-        else:
-            if has_bn:
-                gamma, beta, rm, rv, nbt, eps, mom = _bn_fields(bn)
-                nv.call('segnb_bn_finalize', nv.ptr(stats), C, Cp, float(N * Ho * Wo), nv.ptr(eff_gamma()),
-                        nv.ptr(beta.detach()), eps, mom, nv.ptr(rm), nv.ptr(rv), nv.ptr(nbt), 1 if tape.train else 0,
-                        nv.ptr(coef_buf), rt.stream)
-                coef = coef_buf
-            if out_stats is not None and pv is None and res is None:
-                # the pass that writes the slice also sums it
-                nv.call('segnb_bn_act_fwd_stats', rt.code, y.ptr, y.ld, N, Ho, Wo, Cp, nv.ptr(coef), act, slope, nv.ptr(dropmul),
-                        ov.ptr, ov.ld, nv.ptr(out_stats[0], out_stats[1]), out_stats[2], rt.stream)
-                out_stats = None
-            else:
-                nv.call('segnb_bn_act_fwd', rt.code, y.ptr, y.ld, N, Ho, Wo, Cp, nv.ptr(coef), act, slope, nv.ptr(dropmul),
-                        ov.ptr, ov.ld, vptr(pv), vld(pv), None, 0, None if res is None else res.v.ptr,
-                        0 if res is None else res.v.ld, rt.stream)
     if out_stats is not None:
-        _sum_into(tape, pv if pool else ov, out_stats)
+        stats_into(rt.code, rt.stream, pv if pool else ov, out_stats)
     oa = Act(ov)
     pa = Act(pv) if pool else None
     if fused_bn and not pool and res is None and dropmul is None and tape.need_grad:
         # (the sums buffer is the one this layer's backward reads; cleared by segnb_bn_fwd_fused above)
-        oa.producer = (y, coef_buf, tape.small(site + '/sums', (STAT_REPLICAS, 2, Cp), torch.float64), act, slope)
+        oa.producer = bnl.producer(y)
 
     def backward():
         if oa._g is None and (pa is None or pa.g is None):
@@ -706,8 +660,6 @@ def conv_unit(tape, x, weight, bias, in_segments, stride=1, pad=1, transposed=Fa
             return
         flat = tape.flat
         dz = tape.view(site + '/dz', N, Ho, Wo, Cp)
-        sums = tape.small(site + '/sums', (STAT_REPLICAS, 2, Cp), torch.float64)
-        bcoef = tape.small(site + '/bcoef', (3, Cp), torch.float32)
         gp = pa.g if pa is not None else None
         # (two gradient sources -- a tensor with two consumers, linknet.py:41-62's identity branches: both go to the reduction pass,
         # segnb_bn_act_bwd_reduce_add, instead of an add pass first; not beside a pooled gradient)
@@ -723,19 +675,9 @@ def conv_unit(tape, x, weight, bias, in_segments, stride=1, pad=1, transposed=Fa
         else:
             if not has_bn and res is None:
                 (rt.arm_fork() if forks else None)                # (no BatchNorm: this pass is the last launch before the weight gradient's fork)
-            if og2 is not None:
-                nv.call('segnb_bn_act_bwd_reduce_add', rt.code, y.ptr, y.ld, N, Ho, Wo, Cp, nv.ptr(coef), act, slope,
-                        nv.ptr(dropmul), og.ptr, og.ld, og2.ptr, og2.ld, dz.ptr, dz.ld, nv.ptr(sums),
-                        None if res is None else res.v.ptr, 0 if res is None else res.v.ld, rt.stream)
-            else:
-                nv.call('segnb_bn_act_bwd_reduce', rt.code, y.ptr, y.ld, N, Ho, Wo, Cp, nv.ptr(coef), act, slope,
-                        nv.ptr(dropmul), vptr(og), vld(og), vptr(gp), vld(gp), None, 0, None if direct else dz.ptr,
-                        0 if direct else dz.ld, nv.ptr(sums), None if res is None else res.v.ptr, 0 if res is None else res.v.ld,
-                        rt.stream)
-        count = float(N * Ho * Wo)
+            bnl.reduce(rt.code, rt.stream, y, og, og2, gp, None, dropmul, None if direct else dz, res=None if res is None else res.v)
         dy = dz
         if has_bn:
-            gamma = tape.small(site + '/geff', (C,), torch.float32) if abs_form else bn.weight      # (geff: written by the forward)
             if res is not None:             # dz is also the residual branch's gradient: keep it intact
                 dy = tape.view(site + '/dy', N, Ho, Wo, Cp)
             if res is None and not abs_form:
@@ -743,23 +685,13 @@ def conv_unit(tape, x, weight, bias, in_segments, stride=1, pad=1, transposed=Fa
                 # (engine.Runtime.arm_fork: no marker packet between the pass and the data gradient on this queue)
                 (rt.arm_fork() if forks else None)
             if direct:
-                nv.call('segnb_bn_bwd_apply_fused_direct', rt.code, y.ptr, y.ld, N, Ho, Wo, C, Cp, nv.ptr(coef_buf),
-                        nv.ptr(sums), nv.ptr(gamma.detach()), nv.ptr(bcoef), nv.ptr(dgamma_target()),
-                        nv.ptr(flat.grad_of(bn.bias)), 1, nv.ptr(stats), act, slope, oa.g.ptr, oa.g.ld, dy.ptr, dy.ld,
-                        rt.stream)
-            elif fused_bn:
-                nv.call('segnb_bn_bwd_apply_fused', rt.code, y.ptr, y.ld, N, Ho, Wo, C, Cp, nv.ptr(coef_buf), nv.ptr(sums),
-                        nv.ptr(gamma.detach()), nv.ptr(bcoef), nv.ptr(dgamma_target()),
-                        nv.ptr(flat.grad_of(bn.bias)), 1, nv.ptr(stats), dz.ptr, dz.ld, dy.ptr, dy.ld, rt.stream)
+                bnl.apply(rt.code, rt.stream, y, dy, True, g=oa.g)
             else:
-                nv.call('segnb_bn_bwd_finalize', nv.ptr(sums), C, Cp, count, nv.ptr(gamma.detach()), nv.ptr(coef_buf),
-                        nv.ptr(bcoef), nv.ptr(dgamma_target()), nv.ptr(flat.grad_of(bn.bias)), 1, rt.stream)
-                nv.call('segnb_bn_bwd_apply', rt.code, y.ptr, y.ld, N, Ho, Wo, Cp, nv.ptr(coef_buf), nv.ptr(bcoef),
-                        dz.ptr, dz.ld, dy.ptr, dy.ld, None, C, rt.stream)
-            dgamma_done()
+                bnl.apply(rt.code, rt.stream, y, dy, fused_bn, dz=dz)
+            if abs_form:
+                nv.call('segnb_abn_dscale', nv.ptr(bn.weight.detach()), nv.ptr(bnl.grads()[0]), nv.ptr(flat.grad_of(bn.weight)), C, rt.stream)
         else:
-            gb = flat.grad_of(bias) if bias is not None else None
-            tape.defer_bias_grad(sums, C, Cp, gb, count, coef_buf, bcoef)
+            tape.defer_bias_grad(bnl, flat.grad_of(bias) if bias is not None else None, N * Ho * Wo)
         if res is not None:
             tape.contribute(res, dz)
         # the weight gradient (and its unpack) only READ x and dy, and nothing reads dW before the end of backward: side
@@ -788,36 +720,22 @@ def _bn_act_core(tape, x, fields, grads_of, act, slope, tag, out=None, stats_src
     site = tape.site(tag)
     tape.consume(x)
     N, H, W, Cp = xv.N, xv.H, xv.W, xv.Cp
-    gamma, beta, rm, rv, nbt, eps, mom = fields
-    C = gamma.numel()
-    stats = tape.small(site + '/stats', (STAT_REPLICAS, 2, Cp), torch.float64)
-    coef = tape.small(site + '/coef', (4, Cp), torch.float32)
+    C = fields[0].numel()
+    bnl = tape.cached(site + '/bn', lambda: BnLayer(C, Cp, rt.zeros, act, slope))
+    bnl.params, bnl.grads = (lambda: fields), grads_of          # (this call's views of the parameters)
     fused = tape.fuses_finalize()
     cached = stats_src is not None and fused
     if tape.train and not cached:
-        nv.call('segnb_bn_stats', rt.code, xv.ptr, xv.ld, N, H, W, Cp, nv.ptr(stats), rt.stream)
+        bnl.stats_of(rt.code, rt.stream, xv)
     ov = out if out is not None else tape.view(site + '/a', N, H, W, Cp)
-    if cached:
-        sums_f = tape.small(site + '/sums', (STAT_REPLICAS, 2, Cp), torch.float64)
-        nv.call('segnb_bn_fwd_fused_ld', rt.code, xv.ptr, xv.ld, N, H, W, C, Cp, nv.ptr(stats_src[0], stats_src[1]), stats_src[2],
-                nv.ptr(gamma.detach()), nv.ptr(beta.detach()), eps, mom, nv.ptr(rm), nv.ptr(rv), nv.ptr(nbt), nv.ptr(coef),
-                nv.ptr(sums_f), act, slope, None, ov.ptr, ov.ld, rt.stream)
-    elif fused:
-        sums_f = tape.small(site + '/sums', (STAT_REPLICAS, 2, Cp), torch.float64)
-        nv.call('segnb_bn_fwd_fused', rt.code, xv.ptr, xv.ld, N, H, W, C, Cp, nv.ptr(stats), nv.ptr(gamma.detach()),
-                nv.ptr(beta.detach()), eps, mom, nv.ptr(rm), nv.ptr(rv), nv.ptr(nbt), nv.ptr(coef), nv.ptr(sums_f), act,
-                slope, None, ov.ptr, ov.ld, None, 0, None, 0, None, 0, rt.stream)
-        tape.note_fused_stats(stats)
-    else:
-        nv.call('segnb_bn_finalize', nv.ptr(stats), C, Cp, float(N * H * W), nv.ptr(gamma.detach()), nv.ptr(beta.detach()),
-                eps, mom, nv.ptr(rm), nv.ptr(rv), nv.ptr(nbt), 1 if tape.train else 0, nv.ptr(coef), rt.stream)
-        nv.call('segnb_bn_act_fwd', rt.code, xv.ptr, xv.ld, N, H, W, Cp, nv.ptr(coef), act, slope, None, ov.ptr, ov.ld,
-                None, 0, None, 0, None, 0, rt.stream)
+    bnl.forward(rt.code, rt.stream, xv, fused, tape.train, out=ov, stats_src=stats_src if cached else None)
+    if fused and not cached:
+        tape.note_fused_stats(bnl.stats)
     oa = Act(ov)
     if fused and tape.need_grad and tape.train:
         # the ONE consumer's data gradient may do this layer's BatchNorm-backward reduction in its store pass (_data_gradient:
         # a dense layer's 16 -> prefix data gradient, tiramisu.py:9-20); the sums buffer was cleared by the fused forward above
-        oa.producer = (xv, coef, tape.small(site + '/sums', (STAT_REPLICAS, 2, Cp), torch.float64), act, slope)
+        oa.producer = bnl.producer(xv)
         # ... or never store that gradient at all: sums launch now, recompute + apply in this layer's backward (nothing else to
         # clear there: the statistics are the concat buffer's cached ones)
         oa.lazy_ok = cached
@@ -825,52 +743,36 @@ def _bn_act_core(tape, x, fields, grads_of, act, slope, tag, out=None, stats_src
     def backward():
         if oa.lazy_dgrad is None and oa.g is None:
             if fused and not cached:
-                stats.zero_()
+                bnl.stats.zero_()
                 tape.unplannable = True
             return
-        flat = tape.flat
-        sums = tape.small(site + '/sums', (STAT_REPLICAS, 2, Cp), torch.float64)
-        bcoef = tape.small(site + '/bcoef', (3, Cp), torch.float32)
         if oa.lazy_dgrad is not None:
             conv2, dyv = oa.lazy_dgrad
             oa.lazy_dgrad, oa.g_is_dz = None, False
             acc = x.needs_grad and x.g is not None
             dst = x.g if acc else tape.view(site + '/dz', N, H, W, Cp)
-            ep = nv.BnApplyEpilogue(xv.ptr, xv.ld, nv.ptr(coef), nv.ptr(sums), nv.ptr(gamma.detach()), C, float(N * H * W),
-                                    nv.ptr(bcoef), nv.ptr(grads_of()[0]), nv.ptr(grads_of()[1]), act, slope, dst.ptr, dst.ld,
+            ep = nv.BnApplyEpilogue(xv.ptr, xv.ld, nv.ptr(bnl.coef), nv.ptr(bnl.sums), nv.ptr(fields[0].detach()), C, float(N * H * W),
+                                    nv.ptr(bnl.bcoef), nv.ptr(grads_of()[0]), nv.ptr(grads_of()[1]), act, slope, dst.ptr, dst.ld,
                                     1 if acc else 0)
             conv2.dgrad_bnapply(dyv, H, W, ep)
             if not acc:
                 tape.contribute(x, dst)
             return
+        # fused: ONE gradient source, no dropout, no residual: dz never goes to memory -- a sums-only reduction (done by the
+        # consumer's data gradient where a fused kernel serves it: oa.g_is_dz), then the apply launch recomputes
+        # dz = act'(z) * g from the incoming gradient (the *_direct forms, as ZF_UNET's first convolutions) and, when the
+        # input has other consumers whose gradients are already in x.g, adds its result there (no segnb_add pass)
+        dz = None if fused else tape.view(site + '/dz', N, H, W, Cp)
+        if oa.g_is_dz:
+            oa.g_is_dz = False
+        else:
+            bnl.reduce(rt.code, rt.stream, xv, oa.g, dz=dz)
+        acc = fused and x.needs_grad and x.g is not None
         if fused:
-            # ONE gradient source, no dropout, no residual: dz never goes to memory -- a sums-only reduction (done by the
-            # consumer's data gradient where a fused kernel serves it: oa.g_is_dz), then the apply launch recomputes
-            # dz = act'(z) * g from the incoming gradient (the *_direct forms, as ZF_UNET's first convolutions) and, when the
-            # input has other consumers whose gradients are already in x.g, adds its result there (no segnb_add pass)
-            if oa.g_is_dz:
-                oa.g_is_dz = False
-            else:
-                nv.call('segnb_bn_act_bwd_reduce', rt.code, xv.ptr, xv.ld, N, H, W, Cp, nv.ptr(coef), act, slope, None,
-                        oa.g.ptr, oa.g.ld, None, 0, None, 0, None, 0, nv.ptr(sums), None, 0, rt.stream)
-            fargs = (rt.code, xv.ptr, xv.ld, N, H, W, C, Cp, nv.ptr(coef), nv.ptr(sums), nv.ptr(gamma.detach()),
-                     nv.ptr(bcoef), nv.ptr(grads_of()[0]), nv.ptr(grads_of()[1]), 1, None if cached else nv.ptr(stats),
-                     act, slope, oa.g.ptr, oa.g.ld)
-            if x.needs_grad and x.g is not None:
-                nv.call('segnb_bn_bwd_apply_fused_direct_acc', *(fargs + (x.g.ptr, x.g.ld, rt.stream)))
-            else:
-                dz = tape.view(site + '/dz', N, H, W, Cp)
-                nv.call('segnb_bn_bwd_apply_fused_direct', *(fargs + (dz.ptr, dz.ld, rt.stream)))
-                tape.contribute(x, dz)
-            return
-        dz = tape.view(site + '/dz', N, H, W, Cp)
-        nv.call('segnb_bn_act_bwd_reduce', rt.code, xv.ptr, xv.ld, N, H, W, Cp, nv.ptr(coef), act, slope, None,
-                oa.g.ptr, oa.g.ld, None, 0, None, 0, dz.ptr, dz.ld, nv.ptr(sums), None, 0, rt.stream)
-        nv.call('segnb_bn_bwd_finalize', nv.ptr(sums), C, Cp, float(N * H * W), nv.ptr(gamma.detach()), nv.ptr(coef),
-                nv.ptr(bcoef), nv.ptr(grads_of()[0]), nv.ptr(grads_of()[1]), 1, rt.stream)
-        nv.call('segnb_bn_bwd_apply', rt.code, xv.ptr, xv.ld, N, H, W, Cp, nv.ptr(coef), nv.ptr(bcoef), dz.ptr, dz.ld,
-                dz.ptr, dz.ld, None, C, rt.stream)
-        tape.contribute(x, dz)
+            dz = x.g if acc else tape.view(site + '/dz', N, H, W, Cp)
+        bnl.apply(rt.code, rt.stream, xv, dz, fused, g=oa.g if fused else None, dz=dz, acc=acc, clear_stats=not cached)
+        if not acc:
+            tape.contribute(x, dz)
 
     tape.record(backward)
     return oa
@@ -885,9 +787,9 @@ def bn_act(tape, x, bn, act=nv.ACT_RELU, slope=0.01, tag='bnact', segs=None, sta
     advanced by the first slice only."""
     if segs is None or len(segs) == 1:
         flat = tape.flat
-        return _bn_act_core(tape, x, _bn_fields(bn), lambda: (flat.grad_of(bn.weight), flat.grad_of(bn.bias)), act, slope, tag,
+        return _bn_act_core(tape, x, module_params(bn)(), lambda: (flat.grad_of(bn.weight), flat.grad_of(bn.bias)), act, slope, tag,
                             stats_src=stats_src)
-    gamma, beta, rm, rv, nbt, eps, mom = _bn_fields(bn)
+    gamma, beta, rm, rv, nbt, eps, mom = module_params(bn)()
     xv = x.v
     assert sum(p for _, p in segs) == xv.Cp and sum(r for r, _ in segs) == gamma.numel(), (segs, xv.Cp, gamma.numel())
     ov = tape.view(tape.site(tag) + '/a', xv.N, xv.H, xv.W, xv.Cp)

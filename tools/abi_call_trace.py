@@ -2,6 +2,10 @@
 
     python tools/abi_call_trace.py CASE [CHECKOUT]      CASE: zf_f32 zf_f32_segw zf_bf16 zf_bf16_segw zf_bf16_segf
                                                               linknet tiramisu unet16 gcn34 (bf16), or all
+    further cases (the BatchNorm branches a default training step never takes): zf_bf16_drop (Dropout2d 0.2), zf_bf16_src
+    (Stage.recompute_dz_min_mb tiny), zf_bf16_headdz (Stage.head_dz_recompute off), tiramisu_nocache (cache_prefix_stats off),
+    every case above + _nofuse (BatchNorm finalize not fused), zf_bf16_eval / linknet_eval (eval-mode forward under no_grad),
+    abn (InPlaceABN on its own: forward + backward, training and eval mode, both affine forms)
 
 CHECKOUT is the repository root whose segnb.engine is traced (default: this one), so the same file traces a parent's
 checkout.  Every nv.call / nv.query is printed in order; a tensor address becomes (ordinal of its storage by first
@@ -13,7 +17,9 @@ import gc
 import os
 import sys
 
-CASES = ('zf_f32', 'zf_f32_segw', 'zf_bf16', 'zf_bf16_segw', 'zf_bf16_segf', 'linknet', 'tiramisu', 'unet16', 'gcn34')
+BASE = ('zf_f32', 'zf_f32_segw', 'zf_bf16', 'zf_bf16_segw', 'zf_bf16_segf', 'linknet', 'tiramisu', 'unet16', 'gcn34')
+CASES = (BASE + ('zf_bf16_drop', 'zf_bf16_src', 'zf_bf16_headdz', 'tiramisu_nocache') + tuple(c + '_nofuse' for c in BASE)
+         + ('zf_bf16_eval', 'linknet_eval', 'abn'))
 root = os.path.abspath(sys.argv[2]) if len(sys.argv) > 2 else os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [root, os.path.join(root, 'segmentation-networks-benchmark_amd'), os.path.join(root, 'tests')]
 os.environ['SEGNB_TEST_HARNESS'] = '1'       # a tool, not the product: allowed to install the emulator
@@ -21,6 +27,7 @@ import numpy as np
 import torch
 from segnb import _native as nv
 import segnb.engine as E
+import segnb.net as NET
 
 starts, spans, ordinals, keep = [], {}, {}, []      # storage bases (sorted), base -> bytes, base -> ordinal, references
 
@@ -99,7 +106,7 @@ def install(out):
     E.View.ptr = property(lambda self: (reg(self.t), orig_vptr(self))[1])
 
 
-def make(case):
+def make(case, nocache=False):
     """-> (model, x, y, dtype)"""
     import model_checks as mc
     golden = os.path.join(root, 'tests', 'golden')
@@ -107,30 +114,62 @@ def make(case):
         from lib.models.zf_unet import ZF_UNET
         g = np.load(os.path.join(golden, 'zf_unet_tiny.npz'))
         torch.manual_seed(3)
-        return ZF_UNET(dropout_val=0.0, filters=4), torch.from_numpy(g['x']), torch.from_numpy(g['y']), case.split('_')[1]
+        return (ZF_UNET(dropout_val=0.2 if case.endswith('_drop') else 0.0, filters=4), torch.from_numpy(g['x']),
+                torch.from_numpy(g['y']), case.split('_')[1])
     if case == 'gcn34':
         import test_gcn_cpu as tg
         g = tg.load_case('k1')
         return tg.make_gcn('k1', g), torch.from_numpy(g['x']), torch.from_numpy(g['y']), 'bf16'
     if case == 'tiramisu':
+        from lib.models.tiramisu import FCDenseNet
+        FCDenseNet.cache_prefix_stats = not nocache
         m, _, x, y = mc.make_tiramisu(np.load(os.path.join(golden, 'tiramisu_small.npz')))
     else:
         m, _, x, y = {'linknet': mc.make_linknet, 'unet16': mc.make_unet16}[case]()
     return m, x, y, 'bf16'
 
 
+def trace_abn():
+    """InPlaceABN called on its own (not through an executor): forward + backward in training and eval mode, both affine forms"""
+    from lib.modules.abn import InPlaceABN
+    for training in (True, False):
+        for form in ('gamma', 'abs_eps'):
+            torch.manual_seed(7)
+            m = InPlaceABN(5, affine_form=form).train(training)
+            x = torch.randn(1, 5, 4, 4, requires_grad=True)
+            m(x).sum().backward()
+
+
 def trace(case):
     from lib.losses import BCEWithLogitsLossAndSmoothJaccard
-    if case == 'gcn34':
+    base = case
+    for suffix in ('_nofuse', '_eval', '_drop', '_src', '_headdz', '_nocache'):
+        base = base[:-len(suffix)] if base.endswith(suffix) else base
+    if base == 'gcn34':
         import gcn_ref
         nv.set_backend_for_testing(gcn_ref.GcnAbiEmulator())
     else:
         from oracle import abi_emulator
         nv.set_backend_for_testing(abi_emulator.AbiEmulator())
-    E.UpCatConvOp.segment_wgrad, E.UpCatConvOp.segment_fwd = case.endswith('_segw'), case.endswith('_segf')
-    model, x, y, dtype = make(case)
+    # finalize fused or not: the environment for a checkout whose Stage reads it per instance, the class attributes otherwise
+    fuse = not case.endswith('_nofuse')
+    os.environ['SEGNB_FUSE_FINALIZE'] = '1' if fuse else '0'
+    E.Stage.fuse_finalize = NET.Tape.fuse_finalize = fuse
+    E.Stage.recompute_dz_min_mb = 1e-6 if case.endswith('_src') else 0.0
+    E.Stage.head_dz_recompute = not case.endswith('_headdz')
+    E.UpCatConvOp.segment_wgrad, E.UpCatConvOp.segment_fwd = base.endswith('_segw'), base.endswith('_segf')
+    if case == 'abn':
+        return trace_abn()
+    torch.manual_seed(11)
+    model, x, y, dtype = make(base + ('_drop' if case.endswith('_drop') else ''), case.endswith('_nocache'))
     model.set_compute_dtype(dtype)
+    if case.endswith('_eval'):
+        model.eval()
+        with torch.no_grad():
+            model(x)
+        return
     model.train()
+    torch.manual_seed(13)            # (the Dropout2d multipliers: only the call text is compared, but keep it repeatable)
     loss = BCEWithLogitsLossAndSmoothJaccard()(model(x), y)
     (x.shape[0] * loss).backward()
 

@@ -28,7 +28,7 @@ for run in range(4):
         for k, st in enumerate(plan.stages[name]):
             b = list(st._bufs.values())[0]
             snap['%s.l%d.y' % (name, k + 1)] = b['y'].t.clone()
-            snap['%s.l%d.coef' % (name, k + 1)] = st.coef.clone()
+            snap['%s.l%d.coef' % (name, k + 1)] = st.bnl.coef.clone()
     snap['logits'] = out.clone()
     snaps.append(snap)
 for run in range(1, 4):
