@@ -3,12 +3,17 @@ copies of the same inputs and (b) where one exists, the torch-CPU fp32 operator 
 called.  Calls go through segnb._native (ctypes -> libsegnb_hip.so): no torch operator computes anything
 on the GPU side.
 
-Tolerances (written per check):
-  f32  path : exact-fp32 MFMA (v_mfma_f32_32x32x2_f32) vs CPU fp32 -> summation-order noise, rtol 1e-4 on
-              the tensor scale
-  bf16 path : identical bf16 storage rounding on both sides, fp32 accumulation -> at most 1-2 bf16 ulps
-              (2^-8 relative) on individual elements after re-rounding
+Tolerances (written per check; check() below):
+  f32  path : exact-fp32 MFMA (v_mfma_f32_32x32x2_f32) vs CPU fp32 -> summation-order noise: 2e-4 of the tensor's largest
+              magnitude + 2e-4 of the element
+  bf16 path : identical bf16 storage rounding on both sides, fp32 accumulation.  The arithmetic differs by 1-2 bf16 ulps
+              (2^-8 relative) of an ELEMENT, but check() allows 2e-2 of the tensor's largest magnitude + 2e-2 of the element:
+              10 to 35 times that on a typical element, enough to pass a kernel that drops one product per output.  The
+              tight check of the convolutions -- a derived per-element bound against float64, and exact impulse probes -- is
+              tests/test_conv_errbound_gpu.py (tests/errbound.py).
 """
+import zlib
+
 import numpy as np
 import pytest
 import torch
@@ -190,7 +195,7 @@ def _run_conv(device, dtype, case, w, b, x_nchw, dy_nchw):
 def test_conv_fprop_dgrad_wgrad(case, dtype):
     name, N, H, W, segs, Co, k, s, p, transposed = case
     Ci = sum(r for r, _ in segs)
-    gen = torch.Generator().manual_seed(hash(name) % 1000)
+    gen = torch.Generator().manual_seed(zlib.crc32(name.encode()) % 1000)
     wshape = (Ci, Co, k, k) if transposed else (Co, Ci, k, k)
     w = torch.randn(wshape, generator=gen) * (2.0 / (Ci * k * k)) ** 0.5
     b = torch.randn(Co, generator=gen) * 0.1
@@ -227,7 +232,7 @@ def test_conv_fprop_dgrad_wgrad(case, dtype):
         parts.append(dx_g[..., off:off + real])
         off += padded
     check(name + ' dx vs torch', torch.cat(parts, -1).permute(0, 3, 1, 2), xr.grad, dtype)
-    check(name + ' dW vs torch', gw_g, wr.grad, 'f32' if dtype == 'f32' else 'bf16', scale=float(wr.grad.abs().max()))
+    check(name + ' dW vs torch', gw_g, wr.grad, 'f32', scale=float(wr.grad.abs().max()))     # (fp32 on both dtypes' paths)
 
 
 SX_CASES = [c for c in CONV_CASES if ' tile' in c[0] or 'stem ragged' in c[0] or c[0] == '2x2 head co1']
@@ -255,7 +260,7 @@ def test_conv_fprop_deepk(case):
     layers, tiramisu.py:14) against the general kernel it replaces, the emulator and F.conv2d; reproducible run to run."""
     name, N, H, W, segs, Co, k, s, p, transposed = case
     Ci = sum(r for r, _ in segs)
-    gen = torch.Generator().manual_seed(hash(name) % 1000)
+    gen = torch.Generator().manual_seed(zlib.crc32(name.encode()) % 1000)
     w = (torch.randn((Co, Ci, k, k), generator=gen) * (2.0 / (Ci * k * k)) ** 0.5).bfloat16().float()
     b = torch.randn(Co, generator=gen) * 0.1
     x = torch.randn(N, Ci, H, W, generator=gen).bfloat16().float()
