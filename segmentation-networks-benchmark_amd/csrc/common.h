@@ -139,6 +139,12 @@ inline int segnb_try_launched(segnb_try_outcome* did, int rc) {
     if (rc == 0) *did = SEGNB_TRY_LAUNCHED;
     return rc;
 }
+// after a try of the plain forward / weight-gradient cascades (segnb_conv_fprop, _act, segnb_conv_wgrad): remember the first
+// selector that launched.  With the call census on, the cascade counts it -- or "kernel:fprop_general" / "kernel:wgrad_general"
+// when every selector declined -- beside the entry points, so a test can tell which kernel served a geometry (tests/test_dilation_gpu.py)
+inline void segnb_kernel_took(segnb_try_outcome did, const char** served, const char* name) {
+    if (did != SEGNB_TRY_DECLINED && *served == nullptr) *served = name;
+}
 // fprop_thin.hip; bn: the BatchNorm-backward reduction epilogue of segnb_conv_fprop_bnreduce or NULL
 int segnb_fprop_thin_try(segnb_try_outcome* did, const segnb_conv_geom* g, const void* in, const void* wpacked, void* out,
                          hipStream_t stream, const segnb_bn_reduce_epilogue* bn);
@@ -315,3 +321,18 @@ __device__ __forceinline__ double wave_sum(double v) {
 }
 
 static inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
+
+// a dense 3 x 3 window: 9 taps whose row and column offsets both span exactly 2 (pad 0 or 1, forward or flipped).  Every kernel
+// that assumes +-1 neighbours gates on this; a dilated 3 x 3 (segnb.convplan, dilation > 1) has 9 taps over a wider span and goes
+// to the general gather kernel
+static inline bool segnb_taps_3x3(const segnb_conv_geom* g) {
+    if (g->ntaps != 9) return false;
+    int dhmin = g->dh[0], dhmax = g->dh[0], dwmin = g->dw[0], dwmax = g->dw[0];
+    for (int t = 1; t < 9; ++t) {
+        dhmin = g->dh[t] < dhmin ? g->dh[t] : dhmin;
+        dhmax = g->dh[t] > dhmax ? g->dh[t] : dhmax;
+        dwmin = g->dw[t] < dwmin ? g->dw[t] : dwmin;
+        dwmax = g->dw[t] > dwmax ? g->dw[t] : dwmax;
+    }
+    return dhmax - dhmin == 2 && dwmax - dwmin == 2;
+}

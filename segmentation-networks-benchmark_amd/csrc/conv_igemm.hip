@@ -1724,35 +1724,47 @@ static int conv_fprop_impl(const segnb_conv_geom* g, int dtype, const void* in, 
         const bool general_only = general_env || bn != nullptr || ap != nullptr;
         const hipStream_t st = (hipStream_t)stream;
         segnb_try_outcome did = SEGNB_TRY_DECLINED;       // (until a kernel below takes the launch)
+        const char* served = nullptr;                     // the selector that took it, for the census (segnb_kernel_took)
         // (the affine + activation epilogue lives in the c8, rw, ws and general kernels: s1 is skipped for it)
         if (!general_only)
             rc = segnb_fprop_c8_try(&did, g, in, wpacked, bias, bias_n, out, stats, st, ep);
+        segnb_kernel_took(did, &served, "kernel:fprop_c8");
         if (!rc && !did && !general_env && ap == nullptr && bn_mode == 0 && out != nullptr && ep == nullptr && stats == nullptr &&
             bias == nullptr)
             rc = segnb_fprop_thin_try(&did, g, in, wpacked, out, st, bn);      // (thin input, wide output; bn or plain)
+        segnb_kernel_took(did, &served, "kernel:fprop_thin");
         if (!rc && !did && !general_only && ep == nullptr)
             rc = segnb_fprop_roll_try(&did, g, in, a.in_bytes, wpacked, a.w_bytes, bias, bias_n, out, stats, st);
+        segnb_kernel_took(did, &served, "kernel:fprop_roll");
         if (!rc && !did && !general_only)
             rc = segnb_fprop_rw_try(&did, g, in, a.in_bytes, wpacked, a.w_bytes, bias, bias_n, out, stats, st, nullptr, ep);
+        segnb_kernel_took(did, &served, "kernel:fprop_rw");
         if (!rc && !did && !general_only)
             rc = segnb_fprop_dma_try(&did, g, in, a.in_bytes, wpacked, a.w_bytes, bias, bias_n, out, stats, st, ep);
+        segnb_kernel_took(did, &served, "kernel:fprop_dma");
         if (!rc && !did && !general_only && fprop_deepk_applies(a)) {
             // few pixels x few channels x deep K (before the halo-tile kernel below, whose blocks also walk K serially)
             hipLaunchKernelGGL(conv_fprop_deepk_kernel, dim3(ceil_div(a.M, 32), ceil_div(g->Co, 32)), dim3(DK_WAVES * 64), 0, st, a);
             did = SEGNB_TRY_LAUNCHED;
         }
+        segnb_kernel_took(did, &served, "kernel:fprop_deepk");
         if (!rc && !did && !general_only && ep == nullptr)
             rc = segnb_fprop_s1_try(&did, g, in, wpacked, bias, bias_n, out, stats, st);
+        segnb_kernel_took(did, &served, "kernel:fprop_s1");
         if (!rc && !did && !general_only && ep == nullptr)
             rc = segnb_fprop_sx_try(&did, g, in, wpacked, bias, bias_n, out, stats, st);
+        segnb_kernel_took(did, &served, "kernel:fprop_sx");
         if (rc) return rc;
         if (did) {
+            if (g_segnb_census_on) segnb_census(served);
             SEGNB_LAUNCH_CHECK();
             return 0;
         }
+        if (g_segnb_census_on) segnb_census("kernel:fprop_general");
         a.ksteps = ceil_div(a.Ktot, 64);
         rc = dispatch_fprop<bf16_t>(a, (hipStream_t)stream);
     } else if (dtype == SEGNB_F32) {
+        if (g_segnb_census_on) segnb_census("kernel:fprop_general");
         a.ksteps = ceil_div(a.Ktot, 32);
         rc = dispatch_fprop<float>(a, (hipStream_t)stream);
     } else {
@@ -1768,21 +1780,14 @@ static int conv_fprop_impl(const segnb_conv_geom* g, int dtype, const void* in, 
 // served where the plain cascade above ends in conv_fprop_deepk_kernel or conv_fprop_s1x9_kernel: <= 32 output channels behind more
 // than 96 input channels (below that the rolling / LDS-DMA kernels take the launch), a stride-1 3 x 3 window
 static bool drop_s1_shape(const segnb_conv_geom* g) {
-    if (g->ntaps != 9 || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return false;
-    if (g->QH != g->Ho || g->QW != g->Wo || g->Wo <= 8) return false;
-    int dhmin = g->dh[0], dhmax = g->dh[0], dwmin = g->dw[0], dwmax = g->dw[0];
-    for (int t = 1; t < 9; ++t) {
-        dhmin = g->dh[t] < dhmin ? g->dh[t] : dhmin;
-        dhmax = g->dh[t] > dhmax ? g->dh[t] : dhmax;
-        dwmin = g->dw[t] < dwmin ? g->dw[t] : dwmin;
-        dwmax = g->dw[t] > dwmax ? g->dw[t] : dwmax;
-    }
-    return dhmax - dhmin == 2 && dwmax - dwmin == 2;
+    if (!segnb_taps_3x3(g) || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return false;
+    return g->QH == g->Ho && g->QW == g->Wo && g->Wo > 8;
 }
 
 extern "C" int segnb_conv_fprop_drop_ok(const segnb_conv_geom* g, int dtype) {
     if (g == nullptr || dtype != SEGNB_BF16 || check_geom(g) || getenv("SEGNB_FPROP_GENERAL") != nullptr || !segnb_knob_fprop_drop()) return 0;
     if (g->Co > 32 || g->Co % 8 != 0 || g->Ci <= 96 || g->Ci % 8 != 0) return 0;
+    if (g->ntaps == 9 && !segnb_taps_3x3(g)) return 0;      // (a dilated 3 x 3: the plain launch, whichever kernel it ends on)
     const long long inb = (((long long)g->N * g->Hi * g->Wi - 1) * g->ld_in + g->Ci) * 2;
     const long long wb = (long long)g->Co * g->ntaps * g->Ci * 2;
     if (inb >= (1ll << 31) || wb >= (1ll << 31)) return 0;
@@ -1923,7 +1928,7 @@ extern "C" int segnb_upconv_fprop_act(int dtype, int N, int H, int W, int Ci, in
 static bool wgrad_general_only();
 static bool upcat_geom_ok(const segnb_conv_geom* g, int dtype, int Cu) {
     if (g == nullptr || dtype != SEGNB_BF16 || check_geom(g) || getenv("SEGNB_FPROP_GENERAL") != nullptr || wgrad_general_only()) return false;
-    if (!segnb_knob_fprop_dma() || g->ntaps != 9 || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return false;
+    if (!segnb_knob_fprop_dma() || !segnb_taps_3x3(g) || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return false;
     if (g->QH != g->Ho || g->QW != g->Wo || (g->Hi & 1) || (g->Wi & 1) || g->Hi != g->Ho || g->Wi != g->Wo || g->Wo < 12) return false;
     if (Cu <= 0 || Cu >= g->Ci) return false;
     const bool thin = g->Ci % 32 == 0 && g->Ci <= 96 && g->Co <= 64 && Cu % 32 == 0 && segnb_knob_fprop_rw();      // fprop_rw.hip
@@ -1963,7 +1968,7 @@ extern "C" int segnb_conv_fprop_upcat(const segnb_conv_geom* g, int dtype, const
 
 static bool upsum_geom_ok(const segnb_conv_geom* g, int dtype, int Cu) {
     if (g == nullptr || dtype != SEGNB_BF16 || check_geom(g) || getenv("SEGNB_FPROP_GENERAL") != nullptr) return false;
-    if (!segnb_knob_fprop_dma() || !segnb_knob_fprop_rw() || g->ntaps != 9 || g->in_step != 1 || g->out_step != 1) return false;
+    if (!segnb_knob_fprop_dma() || !segnb_knob_fprop_rw() || !segnb_taps_3x3(g) || g->in_step != 1 || g->out_step != 1) return false;
     if (g->oh0 != 0 || g->ow0 != 0 || g->QH != g->Ho || g->QW != g->Wo || (g->Ho & 1) || (g->Wo & 1) || g->Wo < 12) return false;
     return g->Ci % 32 == 0 && g->Ci <= 96 && g->Co <= 96 && g->Co % 8 == 0 && Cu % 8 == 0 && Cu > 0 && Cu < g->Co;
 }
@@ -2040,9 +2045,9 @@ static bool bnreduce_general(const segnb_conv_geom* g) { return g->Ci <= 24 && g
 
 extern "C" int segnb_conv_fprop_bnreduce_ok(const segnb_conv_geom* g, int dtype) {
     if (g == nullptr || dtype != SEGNB_BF16 || check_geom(g) || !segnb_knob_bnreduce_fused()) return 0;
-    if (g->ntaps != 9 || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return 0;
+    if (!segnb_taps_3x3(g) || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return 0;
     if (g->QH != g->Ho || g->QW != g->Wo || g->Co % 8 != 0) return 0;
-    if (bnreduce_general(g)) return 1;      // (the general gather kernel: any width, any tap offsets)
+    if (bnreduce_general(g)) return 1;      // (the general gather kernel: any width)
     if (getenv("SEGNB_FPROP_GENERAL") != nullptr || !segnb_knob_fprop_dma() || !segnb_knob_fprop_rw() || g->Wo < 12) return 0;
     for (int t = 0; t < 9; ++t)
         if (g->dh[t] < -1 || g->dh[t] > 1 || g->dw[t] < -1 || g->dw[t] > 1) return 0;
@@ -2098,7 +2103,7 @@ extern "C" int segnb_conv_fprop_bnreduce(const segnb_conv_geom* g, int dtype, co
 // ---- a dense layer's data gradient that is never stored (include/segnb_hip.h): two launches of the general kernel
 extern "C" int segnb_conv_fprop_bnapply_ok(const segnb_conv_geom* g, int dtype) {
     if (g == nullptr || dtype != SEGNB_BF16 || check_geom(g) || !segnb_knob_bnreduce_fused()) return 0;
-    if (g->ntaps != 9 || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return 0;
+    if (!segnb_taps_3x3(g) || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return 0;
     if (g->QH != g->Ho || g->QW != g->Wo || g->Co % 8 != 0 || g->Co <= 32) return 0;      // (64-channel tiles)
     return bnreduce_general(g) ? 1 : 0;
 }
@@ -2166,16 +2171,25 @@ extern "C" int segnb_conv_wgrad(const segnb_conv_geom* g, int dtype, const void*
         // (with a target the fast kernels leave their slabs unreduced: segnb_wgrad_to_param sums them into the parameter's gradient)
         const bool part = tgt != nullptr, general = wgrad_general_only();
         segnb_try_outcome did = SEGNB_TRY_DECLINED;       // (until a kernel below takes the launch)
+        const char* served = nullptr;                     // the selector that took it, for the census (segnb_kernel_took)
         if (!general && segnb_knob_wgrad_roll())
             rc = segnb_wgrad_roll_try(&did, g, in, dout, dwp, nslab, st, part);
+        segnb_kernel_took(did, &served, "kernel:wgrad_roll");
         if (!rc && !did && !general && segnb_knob_wgrad_c8roll() && segnb_wgrad_s1_slabs(g) > 0)
             rc = segnb_wgrad_c8roll_try(&did, g, in, dout, dwp, nslab, st, part);
+        segnb_kernel_took(did, &served, "kernel:wgrad_c8roll");
         if (!rc && !did && !general)
             rc = segnb_wgrad_s1_try(&did, g, in, dout, dwp, nslab, st, false, nullptr, nullptr, tgt);
+        segnb_kernel_took(did, &served, "kernel:wgrad_s1");
         if (!rc && !did && !general)
             rc = segnb_wgrad_sx_try(&did, g, in, dout, dwp, nslab, st, part);
+        segnb_kernel_took(did, &served, "kernel:wgrad_sx");
         if (rc) return rc;
-        if (did) return finish_wgrad(__func__, did, g, dwp, nslab, tgt, false, st);
+        if (did) {
+            if (g_segnb_census_on) segnb_census(served);
+            return finish_wgrad(__func__, did, g, dwp, nslab, tgt, false, st);
+        }
+        if (g_segnb_census_on) segnb_census("kernel:wgrad_general");
         if (wgrad_co8_applies(g)) {
             const int nslot = g->ntaps * (g->Ci / 8), PL = NT / nslot;
             int grid = segnb_num_cus() * 8;
@@ -2183,9 +2197,10 @@ extern "C" int segnb_conv_wgrad(const segnb_conv_geom* g, int dtype, const void*
             hipLaunchKernelGGL(conv_wgrad_co8_kernel, dim3(grid), dim3(NT), 0, (hipStream_t)stream, a, nslot, PL);
         } else
             rc = dispatch_wgrad<bf16_t>(a, (hipStream_t)stream);
-    } else if (dtype == SEGNB_F32)
+    } else if (dtype == SEGNB_F32) {
+        if (g_segnb_census_on) segnb_census("kernel:wgrad_general");
         rc = dispatch_wgrad<float>(a, (hipStream_t)stream);
-    else {
+    } else {
         segnb_set_error("segnb_conv_wgrad: unknown dtype %d", dtype);
         return SEGNB_E_BADARG;
     }

@@ -253,7 +253,7 @@ int segnb_fprop_c8_try(segnb_try_outcome* did, const segnb_conv_geom* g, const v
 
 static bool c8_launch(const segnb_conv_geom* g, const void* in, const C8Norm* u8, const void* wpacked, const float* bias,
                       int bias_n, void* out, double* stats, hipStream_t stream, const segnb_act_epilogue* ep) {
-    if (g->ntaps != 9 || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return false;
+    if (!segnb_taps_3x3(g) || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return false;
     if (g->Co > 32 && g->Co <= 64 && g->Co % 8 == 0 && g->Ci == 8 && stats == nullptr && u8 == nullptr &&
         (ep == nullptr || ep->coef == nullptr)) {
         // 33..64 output channels (unet16.py:73: VGG's 3 -> 64 at 1024 x 1024) as two launches over channel halves: the input is
@@ -267,14 +267,11 @@ static bool c8_launch(const segnb_conv_geom* g, const void* in, const C8Norm* u8
                          bias_n > 32 ? bias_n - 32 : 0, (bf16_t*)out + 32, nullptr, stream, ep);
     }
     if (g->QH != g->Ho || g->QW != g->Wo || g->Ci != 8 || g->Co > 32 || g->Wo < 12) return false;
-    int dhmin = g->dh[0], dhmax = g->dh[0], dwmin = g->dw[0], dwmax = g->dw[0];
+    int dhmin = g->dh[0], dwmin = g->dw[0];      // (segnb_taps_3x3 above: the spans are 2)
     for (int t = 1; t < 9; ++t) {
         dhmin = g->dh[t] < dhmin ? g->dh[t] : dhmin;
-        dhmax = g->dh[t] > dhmax ? g->dh[t] : dhmax;
         dwmin = g->dw[t] < dwmin ? g->dw[t] : dwmin;
-        dwmax = g->dw[t] > dwmax ? g->dw[t] : dwmax;
     }
-    if (dhmax - dhmin != 2 || dwmax - dwmin != 2) return false;
     C8Args a;
     a.ep_act = ep != nullptr ? ep->act : -1;
     a.ep_coef = ep != nullptr ? ep->coef : nullptr;
@@ -370,7 +367,7 @@ extern "C" int segnb_pack_input_u8(const unsigned char* img, int N, int H, int W
 
 extern "C" int segnb_conv_fprop_u8_ok(const segnb_conv_geom* g, int dtype) {
     if (g == nullptr || dtype != SEGNB_BF16 || !segnb_knob_fprop_dma()) return 0;
-    if (g->ntaps != 9 || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return 0;
+    if (!segnb_taps_3x3(g) || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return 0;
     if (g->QH != g->Ho || g->QW != g->Wo || g->Ci != 8 || g->Co > 32 || g->Wo < 12 || g->Hi != g->Ho || g->Wi != g->Wo) return 0;
     for (int t = 0; t < 9; ++t)
         if (g->dh[t] < -1 || g->dh[t] > 1 || g->dw[t] < -1 || g->dw[t] > 1) return 0;

@@ -1463,7 +1463,7 @@ int segnb_fprop_dma_actmask_ok(const segnb_conv_geom* g) {
     if (!segnb_knob_fprop_dma() || !segnb_knob_fprop_mask() || !segnb_knob_fprop_mf16() || segnb_knob_fprop_dma_cfg() >= 2 ||
         getenv("SEGNB_FPROP_GENERAL") != nullptr)
         return 0;
-    if (g->ntaps != 9 || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return 0;
+    if (!segnb_taps_3x3(g) || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return 0;
     if (g->QH != g->Ho || g->QW != g->Wo || g->Ci % 64 != 0 || g->Co <= 32 || g->Co % 8 != 0 || g->Wo <= 8) return 0;
     int dhmin = g->dh[0], dwmin = g->dw[0];
     for (int t = 1; t < 9; ++t) {
@@ -1507,7 +1507,7 @@ int segnb_fprop_dma_try(segnb_try_outcome* did, const segnb_conv_geom* g, const 
     // (fused BatchNorm-backward REDUCTIONS: fprop_rw.hip / fprop_roll.hip; here only the activation mask of a layer without
     // BatchNorm -- coef NULL -- on a plain data gradient: the MASK instantiation)
     if (bn != nullptr && (bn->coef != nullptr || bn->y == nullptr || bn->sums == nullptr || ep != nullptr || uc != nullptr ||
-                          stats != nullptr || bias != nullptr || g->ntaps != 9 || !segnb_knob_fprop_mask()))
+                          stats != nullptr || bias != nullptr || !segnb_taps_3x3(g) || !segnb_knob_fprop_mask()))
         return 0;
     if (g->ntaps == 16 && ep == nullptr && stats == nullptr && bias == nullptr && segnb_knob_fprop_upd()) {
         FdArgs a;
@@ -1536,16 +1536,13 @@ int segnb_fprop_dma_try(segnb_try_outcome* did, const segnb_conv_geom* g, const 
         if (rc == NOT_HANDLED) return 0;
         return segnb_try_launched(did, rc);
     }
-    if (g->ntaps != 9 || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return 0;
+    if (!segnb_taps_3x3(g) || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return 0;
     if (g->QH != g->Ho || g->QW != g->Wo || g->Ci % 64 != 0) return 0;
-    int dhmin = g->dh[0], dhmax = g->dh[0], dwmin = g->dw[0], dwmax = g->dw[0];
+    int dhmin = g->dh[0], dwmin = g->dw[0];      // (segnb_taps_3x3 above: the spans are 2)
     for (int t = 1; t < 9; ++t) {
         dhmin = g->dh[t] < dhmin ? g->dh[t] : dhmin;
-        dhmax = g->dh[t] > dhmax ? g->dh[t] : dhmax;
         dwmin = g->dw[t] < dwmin ? g->dw[t] : dwmin;
-        dwmax = g->dw[t] > dwmax ? g->dw[t] : dwmax;
     }
-    if (dhmax - dhmin != 2 || dwmax - dwmin != 2) return 0;
     FdArgs a;
     a.x = (const bf16_t*)in;
     a.w = (const bf16_t*)wpacked;

@@ -642,17 +642,14 @@ int segnb_fprop_roll_try(segnb_try_outcome* did, const segnb_conv_geom* g, const
     *did = SEGNB_TRY_DECLINED;
     const int knob = segnb_knob_fprop_roll();
     if (!knob) return 0;
-    if (g->ntaps != 9 || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return 0;
+    if (!segnb_taps_3x3(g) || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return 0;
     if (g->QH != g->Ho || g->QW != g->Wo) return 0;
     if (g->Co % 8 != 0 || g->Wo < 32 || g->ld_in % 8 != 0 || g->ld_out % 8 != 0) return 0;
-    int dhmin = g->dh[0], dhmax = g->dh[0], dwmin = g->dw[0], dwmax = g->dw[0];
+    int dhmin = g->dh[0], dwmin = g->dw[0];      // (segnb_taps_3x3 above: the spans are 2)
     for (int t = 1; t < 9; ++t) {
         dhmin = g->dh[t] < dhmin ? g->dh[t] : dhmin;
-        dhmax = g->dh[t] > dhmax ? g->dh[t] : dhmax;
         dwmin = g->dw[t] < dwmin ? g->dw[t] : dwmin;
-        dwmax = g->dw[t] > dwmax ? g->dw[t] : dwmax;
     }
-    if (dhmax - dhmin != 2 || dwmax - dwmin != 2) return 0;
     // same-size (padding 1) everywhere; another padding (the valid 3 x 3 convolution of lib/models/linknet.py:60 and its data
     // gradient: input and output grids differ) only for the plain one-wave form
     const bool same = g->Hi == g->Ho && g->Wi == g->Wo && dhmin == -1 && dwmin == -1;
@@ -758,18 +755,15 @@ extern "C" int segnb_conv_fprop_actmask_ok(const segnb_conv_geom* g, int dtype) 
 // conv_roll_kernel, EPI = 3 (32 -> <= 32 channels)
 int segnb_fprop_roll_actmask_ok(const segnb_conv_geom* g) {
     if (!segnb_knob_fprop_roll() || getenv("SEGNB_FPROP_GENERAL") != nullptr) return 0;
-    if (g->ntaps != 9 || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return 0;
+    if (!segnb_taps_3x3(g) || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return 0;
     if (g->QH != g->Ho || g->QW != g->Wo || g->Ci != 32 || g->Co > 32 || g->Co % 8 != 0 || g->Wo < 32) return 0;
     if (g->ld_in % 8 != 0 || g->ld_out % 8 != 0) return 0;
-    int dhmin = g->dh[0], dhmax = g->dh[0], dwmin = g->dw[0], dwmax = g->dw[0];
+    int dhmin = g->dh[0], dwmin = g->dw[0];      // (segnb_taps_3x3 above: the spans are 2)
     bool seen[9] = {false, false, false, false, false, false, false, false, false};
     for (int t = 1; t < 9; ++t) {
         dhmin = g->dh[t] < dhmin ? g->dh[t] : dhmin;
-        dhmax = g->dh[t] > dhmax ? g->dh[t] : dhmax;
         dwmin = g->dw[t] < dwmin ? g->dw[t] : dwmin;
-        dwmax = g->dw[t] > dwmax ? g->dw[t] : dwmax;
     }
-    if (dhmax - dhmin != 2 || dwmax - dwmin != 2) return 0;
     for (int t = 0; t < 9; ++t) {
         const int k = (g->dh[t] - dhmin) * 3 + (g->dw[t] - dwmin);
         if (seen[k]) return 0;
@@ -780,7 +774,7 @@ int segnb_fprop_roll_actmask_ok(const segnb_conv_geom* g) {
 
 static bool roll_tf_geom_ok(const segnb_conv_geom* g, int dtype) {
     if (g == nullptr || dtype != SEGNB_BF16 || !segnb_knob_fprop_roll() || getenv("SEGNB_FPROP_GENERAL") != nullptr) return false;
-    if (g->ntaps != 9 || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return false;
+    if (!segnb_taps_3x3(g) || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return false;
     if (g->QH != g->Ho || g->QW != g->Wo || g->Hi != g->Ho || g->Wi != g->Wo) return false;
     if (g->Ci != 32 || g->Co > 32 || g->Co % 8 != 0 || g->Wo < 32 || g->ld_in % 8 != 0 || g->ld_out % 8 != 0) return false;
     for (int t = 0; t < 9; ++t)

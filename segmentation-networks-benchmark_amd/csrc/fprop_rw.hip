@@ -513,16 +513,13 @@ int segnb_fprop_rw_try(segnb_try_outcome* did, const segnb_conv_geom* g, const v
                        const segnb_upcat_src* uc, const segnb_upcat_src* upsum) {
     *did = SEGNB_TRY_DECLINED;
     if (!segnb_knob_fprop_dma() || !segnb_knob_fprop_rw()) return 0;
-    if (g->ntaps != 9 || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return 0;
+    if (!segnb_taps_3x3(g) || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return 0;
     if (g->QH != g->Ho || g->QW != g->Wo || g->Ci % 32 != 0 || g->Ci > 96 || g->Co > 96 || g->Wo < 12) return 0;
-    int dhmin = g->dh[0], dhmax = g->dh[0], dwmin = g->dw[0], dwmax = g->dw[0];
+    int dhmin = g->dh[0], dwmin = g->dw[0];      // (segnb_taps_3x3 above: the spans are 2)
     for (int t = 1; t < 9; ++t) {
         dhmin = g->dh[t] < dhmin ? g->dh[t] : dhmin;
-        dhmax = g->dh[t] > dhmax ? g->dh[t] : dhmax;
         dwmin = g->dw[t] < dwmin ? g->dw[t] : dwmin;
-        dwmax = g->dw[t] > dwmax ? g->dw[t] : dwmax;
     }
-    if (dhmax - dhmin != 2 || dwmax - dwmin != 2) return 0;
     FdArgs a;
     a.x = (const bf16_t*)in;
     a.w = (const bf16_t*)wpacked;

@@ -362,16 +362,13 @@ int dispatch_fs1(FpS1Args& a, hipStream_t stream) {
 int segnb_fprop_s1_try(segnb_try_outcome* did, const segnb_conv_geom* g, const void* in, const void* wpacked, const float* bias, int bias_n,
                        void* out, double* stats, hipStream_t stream, const float* drop, int ld_drop, int stats_ld) {
     *did = SEGNB_TRY_DECLINED;
-    if (g->ntaps != 9 || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return 0;
+    if (!segnb_taps_3x3(g) || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return 0;
     if (g->QH != g->Ho || g->QW != g->Wo || g->Ci < 32) return 0;
-    int dhmin = g->dh[0], dhmax = g->dh[0], dwmin = g->dw[0], dwmax = g->dw[0];
+    int dhmin = g->dh[0], dwmin = g->dw[0];      // (segnb_taps_3x3 above: the spans are 2)
     for (int t = 1; t < 9; ++t) {
         dhmin = g->dh[t] < dhmin ? g->dh[t] : dhmin;
-        dhmax = g->dh[t] > dhmax ? g->dh[t] : dhmax;
         dwmin = g->dw[t] < dwmin ? g->dw[t] : dwmin;
-        dwmax = g->dw[t] > dwmax ? g->dw[t] : dwmax;
     }
-    if (dhmax - dhmin != 2 || dwmax - dwmin != 2) return 0;
     FpS1Args a;
     a.x = (const bf16_t*)in;
     a.w = (const bf16_t*)wpacked;

@@ -260,7 +260,7 @@ __global__ __launch_bounds__(256, 2) void conv_thin_kernel(const ThinArgs a) {
 }
 
 bool thin_geometry(const segnb_conv_geom* g) {
-    if (g->ntaps != 9 || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return false;
+    if (!segnb_taps_3x3(g) || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return false;
     if (g->QH != g->Ho || g->QW != g->Wo || g->Hi != g->Ho || g->Wi != g->Wo) return false;
     if ((g->Ci != 8 && g->Ci != 16) || g->Co % 8 != 0 || g->Co < 48 || g->Co > TH_MAXC) return false;
     // (measured, tools/dense_dgrad_bench.py: from 8 x 32 x 32 pixels up this kernel wins -- 15.6 vs 18.4 us with the reduction at 656

@@ -657,7 +657,7 @@ int launch_c8roll(WRollArgs& a, int nslab, hipStream_t stream) {
 }  // namespace
 
 bool segnb_wgrad_roll_applies(const segnb_conv_geom* g) {
-    if (g->ntaps != 9 || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return false;
+    if (!segnb_taps_3x3(g) || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return false;
     if (g->QH != g->Ho || g->QW != g->Wo || g->Hi != g->Ho || g->Wi != g->Wo) return false;
     if (g->Ci != 32 || g->Co > 32 || g->Co % 8 != 0 || g->Wo < 32 || g->ld_in % 8 != 0 || g->ld_out % 8 != 0) return false;
     bool seen[9] = {false, false, false, false, false, false, false, false, false};
@@ -733,7 +733,7 @@ int segnb_wgrad_roll_try(segnb_try_outcome* did, const segnb_conv_geom* g, const
 }
 
 bool segnb_wgrad_c8roll_applies(const segnb_conv_geom* g) {
-    if (g->ntaps != 9 || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return false;
+    if (!segnb_taps_3x3(g) || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return false;
     if (g->QH != g->Ho || g->QW != g->Wo || g->Hi != g->Ho || g->Wi != g->Wo) return false;
     if (g->Ci != 8 || g->Co > 32 || g->Co % 8 != 0 || g->Wo < 32 || g->ld_in % 8 != 0 || g->ld_out % 8 != 0) return false;
     bool seen[9] = {false, false, false, false, false, false, false, false, false};

@@ -297,11 +297,18 @@ class ConvOp(object):
     algo_scale = 1.0        # algorithmic / executed FLOPs of a launch (UpConvOp: 9 / 4)
     _in_place, _ci_offset = False, 0      # (subclasses that build their own channel maps keep the workspace + unpack path)
     pack_fwd = True         # False: the forward matrix is never used (the owner runs the forward through another op)
+    dilation = 1
 
     def __init__(self, rt, weight, bias, in_segments, stride=1, pad=1, transposed=False, need_dgrad=True,
-                 out_hw=None, ci_offset=0):
+                 out_hw=None, ci_offset=0, dilation=1):
         """ci_offset: the op covers input channels [ci_offset, ci_offset + sum(real)) of the parameter tensor only (one
-        segment of a concatenated input handled on its own)."""
+        segment of a concatenated input handled on its own).
+        dilation > 1 (stride 1, not transposed): the tap tables spread by it (segnb.convplan); every fast path declines such a
+        table (csrc/common.h: segnb_taps_3x3) and the general gather kernel serves the three launches."""
+        if dilation < 1 or (dilation != 1 and (stride != 1 or transposed)):
+            raise ValueError('dilation %r needs stride 1 and transposed=False (got stride %r, transposed %r)'
+                             % (dilation, stride, transposed))
+        self.dilation = dilation
         self.rt = rt
         self.out_hw_override = out_hw      # transposed conv only: crop the output at the bottom/right
                                            # (center_crop of tiramisu.py:86-90 always has offset 0)
@@ -386,9 +393,9 @@ class ConvOp(object):
                 Ho, Wo = Hc, Wc
             dg, dg_full = cp.convt_dgrad(Hi, Wi, self.KH, self.KW, self.stride, self.pad), True
         else:
-            (Ho, Wo), fwd = cp.conv_fwd(Hi, Wi, self.KH, self.KW, self.stride, self.pad)
+            (Ho, Wo), fwd = cp.conv_fwd(Hi, Wi, self.KH, self.KW, self.stride, self.pad, self.dilation)
             full = True
-            dg, dg_full = cp.conv_dgrad(Hi, Wi, self.KH, self.KW, self.stride, self.pad)
+            dg, dg_full = cp.conv_dgrad(Hi, Wi, self.KH, self.KW, self.stride, self.pad, self.dilation)
         p['out_hw'] = (Ho, Wo)
         p['fwd'], p['fwd_full'] = fwd, full
         p['dg'], p['dg_full'] = dg, dg_full

@@ -510,10 +510,11 @@ def _data_gradient(tape, conv, x, dy, site):
 
 def conv_unit(tape, x, weight, bias, in_segments, stride=1, pad=1, transposed=False, bn=None, act=nv.ACT_RELU,
               slope=0.01, dropmul=None, out=None, pool=False, pool_out=None, res=None, out_hw=None, tag='conv',
-              out_stats=None):
+              out_stats=None, dilation=1):
     """conv / conv-transpose -> [BatchNorm] -> (+res) -> activation -> [Dropout2d multipliers] [-> MaxPool2d(2)].
 
     out: optional View to write the activated output into (a slice of a concat buffer).
+    dilation: of an nn.Conv2d with stride 1 (ConvOp).
     out_stats: (fp64 table, element offset, row stride) -- the per-channel statistics of the FINAL output (the pooled one when
     pool is set) are accumulated into that channel range (the slice's share of its concat buffer's statistics table: bn_act's
     stats_src), by the pass that writes it where there is one.
@@ -521,7 +522,8 @@ def conv_unit(tape, x, weight, bias, in_segments, stride=1, pad=1, transposed=Fa
     rt = tape.rt
     site = tape.site(tag)
     def make_op():
-        op = ConvOp(rt, weight, bias, in_segments, stride, pad, transposed, need_dgrad=x.needs_grad, out_hw=out_hw)
+        op = ConvOp(rt, weight, bias, in_segments, stride, pad, transposed, need_dgrad=x.needs_grad, out_hw=out_hw,
+                    dilation=dilation)
         op.wg_cu_pct = tape.wg_cu_pct          # (the model's share of the CUs for its weight gradients; None = the library default)
         return op
     conv = tape.cached(site + '/op', make_op)
