@@ -119,6 +119,7 @@ void segnb_plan_refuse(const char* why);
     if (plan_scope__.top && segnb_plan_recording()) segnb_plan_refuse(why)
 
 int segnb_num_cus();
+bool segnb_fprop_general_forced();      // conv_igemm.hip: SEGNB_FPROP_GENERAL is set (A/B testing; read once per process)
 int segnb_knob_fprop_dma();       // runtime.hip: segnb_tune() knobs
 int segnb_knob_fprop_dma_cfg();
 int segnb_knob_fprop_dma_dbg();
@@ -335,4 +336,8 @@ static inline bool segnb_taps_3x3(const segnb_conv_geom* g) {
         dwmax = g->dw[t] > dwmax ? g->dw[t] : dwmax;
     }
     return dhmax - dhmin == 2 && dwmax - dwmin == 2;
+}
+// one launch of a dense stride-1 3 x 3 that writes every output pixel: what the fused forward entry points serve
+static inline bool whole_output_3x3_s1(const segnb_conv_geom* g) {
+    return segnb_taps_3x3(g) && g->in_step == 1 && g->out_step == 1 && g->oh0 == 0 && g->ow0 == 0 && g->QH == g->Ho && g->QW == g->Wo;
 }

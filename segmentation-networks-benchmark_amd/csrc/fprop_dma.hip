@@ -1461,7 +1461,7 @@ int segnb_fprop_upf_try(segnb_try_outcome* did, int N, int H, int W, int Ci, int
 // 1 when the MASK instantiation serves the data gradient g (segnb_conv_fprop_actmask_ok): what segnb_fprop_dma_try + dispatch_fd accept
 int segnb_fprop_dma_actmask_ok(const segnb_conv_geom* g) {
     if (!segnb_knob_fprop_dma() || !segnb_knob_fprop_mask() || !segnb_knob_fprop_mf16() || segnb_knob_fprop_dma_cfg() >= 2 ||
-        getenv("SEGNB_FPROP_GENERAL") != nullptr)
+        segnb_fprop_general_forced())
         return 0;
     if (!segnb_taps_3x3(g) || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return 0;
     if (g->QH != g->Ho || g->QW != g->Wo || g->Ci % 64 != 0 || g->Co <= 32 || g->Co % 8 != 0 || g->Wo <= 8) return 0;
@@ -1487,7 +1487,7 @@ int segnb_fprop_dma_actmask_ok(const segnb_conv_geom* g) {
 
 extern "C" int segnb_conv_fprop_upd_ok(const segnb_conv_geom* g, int dtype) {
     if (g == nullptr || dtype != SEGNB_BF16) return 0;
-    if (!segnb_knob_fprop_dma() || !segnb_knob_fprop_upd() || getenv("SEGNB_FPROP_GENERAL") != nullptr) return 0;
+    if (!segnb_knob_fprop_dma() || !segnb_knob_fprop_upd() || segnb_fprop_general_forced()) return 0;
     const long long ob = (((long long)g->N * g->Ho * g->Wo - 1) * g->ld_out + g->Co) * 2;
     return upd_geometry(g) && ob < (1ll << 31) ? 1 : 0;
 }

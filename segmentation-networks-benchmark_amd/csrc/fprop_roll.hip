@@ -754,7 +754,7 @@ extern "C" int segnb_conv_fprop_actmask_ok(const segnb_conv_geom* g, int dtype) 
 
 // conv_roll_kernel, EPI = 3 (32 -> <= 32 channels)
 int segnb_fprop_roll_actmask_ok(const segnb_conv_geom* g) {
-    if (!segnb_knob_fprop_roll() || getenv("SEGNB_FPROP_GENERAL") != nullptr) return 0;
+    if (!segnb_knob_fprop_roll() || segnb_fprop_general_forced()) return 0;
     if (!segnb_taps_3x3(g) || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return 0;
     if (g->QH != g->Ho || g->QW != g->Wo || g->Ci != 32 || g->Co > 32 || g->Co % 8 != 0 || g->Wo < 32) return 0;
     if (g->ld_in % 8 != 0 || g->ld_out % 8 != 0) return 0;
@@ -773,7 +773,7 @@ int segnb_fprop_roll_actmask_ok(const segnb_conv_geom* g) {
 }
 
 static bool roll_tf_geom_ok(const segnb_conv_geom* g, int dtype) {
-    if (g == nullptr || dtype != SEGNB_BF16 || !segnb_knob_fprop_roll() || getenv("SEGNB_FPROP_GENERAL") != nullptr) return false;
+    if (g == nullptr || dtype != SEGNB_BF16 || !segnb_knob_fprop_roll() || segnb_fprop_general_forced()) return false;
     if (!segnb_taps_3x3(g) || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return false;
     if (g->QH != g->Ho || g->QW != g->Wo || g->Hi != g->Ho || g->Wi != g->Wo) return false;
     if (g->Ci != 32 || g->Co > 32 || g->Co % 8 != 0 || g->Wo < 32 || g->ld_in % 8 != 0 || g->ld_out % 8 != 0) return false;

@@ -1,0 +1,231 @@
+"""What the convolution entry points of libsegnb_hip.so select, answer and refuse, as data: the cases of
+tests/test_conv_select_gpu.py and the functions that run them.
+
+Run as a script on the commit whose behaviour is to be pinned (the PARENT of a change to the host side of csrc/conv_igemm.hip):
+
+    python tests/conv_select.py tests/conv_select_parent.json
+
+It runs everything twice and refuses to write a table the library does not repeat itself.  The weight gradient of a row that the
+general kernel serves is left out of the digests (dW: null): that kernel sums with fp32 atomics and is not bit-reproducible.
+"""
+import hashlib
+import json
+import os
+import sys
+
+if __name__ == '__main__':
+    _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path[:0] = [os.path.join(_ROOT, 'segmentation-networks-benchmark_amd'), _ROOT]
+
+import torch
+
+from segnb import _native as nv
+from segnb import convplan as cp
+
+JSON_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'conv_select_parent.json')
+DW_EXCLUDED = 'kernel:wgrad_general sums with fp32 atomics: the parent does not repeat its own bits'
+
+# ------------------------------------------------------------------------------------------------ 1 + 3. selection and bits
+# id: (dtype, N, H, W, Ci, Co, kernel, stride, bias and statistics in the forward[, segnb_tune knobs set around the launches])
+CASES = {
+    'dma_64_64': ('bf16', 2, 16, 16, 64, 64, 3, 1, True),
+    'rw_32_64': ('bf16', 2, 12, 20, 32, 64, 3, 1, True),
+    'deepk_256_256': ('bf16', 1, 8, 8, 256, 256, 3, 1, True),
+    'c8_8_32': ('bf16', 2, 16, 16, 8, 32, 3, 1, True),
+    'c8roll_8_32': ('bf16', 2, 16, 32, 8, 32, 3, 1, True),
+    'general_16_64_plain': ('bf16', 2, 16, 16, 16, 64, 3, 1, False),
+    'roll_32_32': ('bf16', 2, 16, 32, 32, 32, 3, 1, True),
+    'wroll_32_32': ('bf16', 2, 16, 32, 32, 32, 3, 1, True, {'wgrad_roll': 1}),      # (the knob is off by default: runtime.hip)
+    's1_128_32': ('bf16', 2, 16, 16, 128, 32, 3, 1, True),
+    's1_128_32_plain': ('bf16', 2, 16, 16, 128, 32, 3, 1, False),
+    's1_48_48': ('bf16', 2, 16, 16, 48, 48, 3, 1, True),
+    'general_stride2': ('bf16', 2, 16, 16, 64, 64, 3, 2, True),
+    'wsx_1x1': ('bf16', 2, 16, 16, 64, 64, 1, 1, True),
+    'general_f32': ('f32', 2, 12, 20, 32, 64, 3, 1, True),
+}
+# selectors that no geometry of N <= 2, H, W <= 32 reaches, and the gate that keeps them away
+UNREACHED = {'kernel:fprop_thin': 'fprop_thin.hip thin_geometry: N * Ho * Wo >= 4096 pixels (2 x 32 x 32 = 2048)',
+             'kernel:fprop_sx': 'fprop_sx.hip segnb_fprop_sx_try: in_step == 2 and QW >= 24, an input 48 wide'}
+FPROP_SELECTORS = ['kernel:fprop_' + s for s in ('c8', 'thin', 'roll', 'rw', 'dma', 'deepk', 's1', 'sx', 'general')]
+WGRAD_SELECTORS = ['kernel:wgrad_' + s for s in ('roll', 'c8roll', 's1', 'sx', 'general')]
+
+
+def _randn(shape, seed, scale=1.0):
+    """bf16-exact fp32 values from a fixed-seed CPU generator"""
+    return (torch.randn(shape, generator=torch.Generator().manual_seed(seed)) * scale).bfloat16().float()
+
+
+def _sha(t):
+    t = t.detach().contiguous().cpu()
+    t = t.view(torch.int16) if t.dtype == torch.bfloat16 else t
+    return hashlib.sha256(t.numpy().tobytes()).hexdigest()
+
+
+class census(object):
+    def __enter__(self):
+        nv.call('segnb_tune', b'call_census', 1)
+        nv.census_read()
+        return self
+
+    def take(self):
+        return {k: v for k, v in nv.census_read().items() if k.startswith('kernel:')}
+
+    def __exit__(self, *a):
+        nv.call('segnb_tune', b'call_census', 0)
+
+
+def _operands(rt, case, seed=0):
+    """(op, x view with ld != C, dy view, H, W of the output) of a case, weights packed"""
+    from segnb.engine import ConvOp, View
+    dtype, N, H, W, Ci, Co, k, stride, full = case[:9]
+    dev = rt.device
+    w = _randn((Co, Ci, k, k), 71 + seed, (2.0 / (Ci * k * k)) ** 0.5).to(dev)
+    b = _randn((Co,), 72 + seed).to(dev) if full else None
+    op = ConvOp(rt, w, b, [(Ci, Ci)], stride, (k - 1) // 2, False, need_dgrad=True)
+    op.pack(H, W)
+    Ho, Wo = op.out_hw(H, W)
+    ld = Ci + 8
+    xv = View(rt.zeros((N, H, W, ld)), N, H, W, Ci, ld, 8)
+    xv.dense().copy_(_randn((N, H, W, Ci), 73 + seed).to(dev, rt.tdtype))
+    dyv = View.alloc(rt, N, Ho, Wo, Co)
+    dyv.dense().copy_(_randn((N, Ho, Wo, Co), 74 + seed).to(dev, rt.tdtype))
+    return op, xv, dyv, Ho, Wo
+
+
+def run_case(case):
+    """-> {'names': [forward, data gradient, weight gradient census], 'y', 'dx', 'dW': SHA-256 of the output bytes}"""
+    from segnb.engine import Runtime, View
+    dtype, N, H, W, Ci, Co, k, stride, full = case[:9]
+    knobs = case[9] if len(case) > 9 else {}
+    rt = Runtime(torch.device('cuda:0'), dtype)
+    op, xv, dyv, Ho, Wo = _operands(rt, case)
+    yv, dxv = View.alloc(rt, N, Ho, Wo, Co), View.alloc(rt, N, H, W, Ci)
+    stats = rt.zeros((16, 2, Co), torch.float64) if full else None
+    gw = torch.zeros_like(op.weight)
+    for knob, v in knobs.items():
+        nv.call('segnb_tune', knob.encode(), v)
+    try:
+        with census() as c:
+            op.fprop(xv, yv, stats)
+            kf = c.take()
+            op.dgrad(dyv, dxv)
+            kd = c.take()
+            op.wgrad(xv, dyv, gw)
+            kw = c.take()
+    finally:
+        for knob in knobs:
+            nv.call('segnb_tune', knob.encode(), 0)
+    torch.cuda.synchronize()
+    out = {'names': [kf, kd, kw], 'y': _sha(yv.dense()), 'dx': _sha(dxv.dense()), 'dW': _sha(gw)}
+    if 'kernel:wgrad_general' in kw:
+        out['dW'], out['dW_excluded'] = None, DW_EXCLUDED
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ 2. predicates
+GEOM_QUERIES = ('segnb_conv_fprop_drop_ok', 'segnb_conv_fprop_bnreduce_ok', 'segnb_conv_fprop_bnapply_ok',
+                'segnb_conv_fprop_actmask_ok', 'segnb_conv_fprop_u8_ok', 'segnb_conv_fprop_upd_ok', 'segnb_conv_wgrad_bnapply_ok',
+                'segnb_conv_wgrad_tf_ok', 'segnb_conv_wgrad_slabs')
+CU_QUERIES = ('segnb_conv_upcat_ok', 'segnb_conv_fprop_upsum_ok')                 # (g, dtype, Cu)
+UPCONV_QUERIES = ('segnb_upconv_fprop_ok', 'segnb_upconv_fprop_acc_ok')           # (N, H, W, Ci, Co, ld_out, dtype)
+TF_QUERY = 'segnb_conv_fprop_tf_ok'                                               # (g, dtype, kind)
+GRID_C_IN, GRID_C_OUT, GRID_W = (8, 16, 32, 64, 96, 128, 512), (8, 32, 64, 96, 256), (8, 12, 16, 32)
+GRID_TAPS = ((3, 1, 1), (3, 2, 1), (1, 1, 1), (3, 1, 2), (4, 2, 1))               # (kernel, stride, dilation); pad = dilation * ((kernel - 1) // 2)
+GRID_CU = (8, 32, 64)
+
+
+def _geom(N, H, W, Ci, Co, k, stride, dil, side='f'):
+    from segnb.engine import ConvOp
+    pad = dil * ((k - 1) // 2)
+    (Ho, Wo), fwd = cp.conv_fwd(H, W, k, k, stride, pad, dil)
+    if side == 'f':
+        return ConvOp._make_geom(fwd[0], N, H, W, Ci, Ci, Ho, Wo, Co, Co)
+    return ConvOp._make_geom(cp.conv_dgrad(H, W, k, k, stride, pad, dil)[0][0], N, Ho, Wo, Co, Co, H, W, Ci, Ci)
+
+
+def predicate_table():
+    """{query: its answers over the grid in grid order, comma-separated}; nothing is launched"""
+    lib = nv.load()
+    out = {q: [] for q in GEOM_QUERIES + CU_QUERIES + UPCONV_QUERIES + (TF_QUERY,)}
+    for k, stride, dil in GRID_TAPS:
+        for W in GRID_W:
+            for Ci in GRID_C_IN:
+                for Co in GRID_C_OUT:
+                    for side in 'fd':
+                        g = _geom(2, 8 if W < 16 else W, W, Ci, Co, k, stride, dil, side)
+                        for dt in (nv.BF16, nv.F32):
+                            for q in GEOM_QUERIES:
+                                out[q].append(getattr(lib, q)(g, dt))
+                        for q in CU_QUERIES:
+                            out[q] += [getattr(lib, q)(g, nv.BF16, cu) for cu in GRID_CU]
+                        out[TF_QUERY] += [getattr(lib, TF_QUERY)(g, nv.BF16, kind) for kind in (nv.TF_ACT, nv.TF_BNBWD)]
+    for W in GRID_W:
+        for Ci in GRID_C_IN:
+            for Co in GRID_C_OUT:
+                for q in UPCONV_QUERIES:
+                    out[q] += [getattr(lib, q)(2, W, W, Ci, Co, Co + pad, nv.BF16) for pad in (0, 8)]
+                    out[q].append(getattr(lib, q)(2, W, W, Ci, Co, Co, nv.F32))
+    return {q: ','.join(str(v) for v in a) for q, a in out.items()}
+
+
+# ------------------------------------------------------------------------------------------------ 4. error paths
+def error_paths():
+    """{name: [status, message, did a following un-armed segnb_conv_wgrad deliver into the parameter's gradient]}: every call below
+    is refused before it launches anything; a segnb_wgrad_target is armed in front of each"""
+    from segnb.engine import Runtime, View
+    lib = nv.load()
+    rt = Runtime(torch.device('cuda:0'), 'bf16')
+    case = CASES['dma_64_64']
+    dtype, N, H, W, Ci, Co = case[:6]
+    op, xv, dyv, Ho, Wo = _operands(rt, case)
+    p = op.plan(H, W)
+    g = op._launch_geom(p, 'f', 0, N, H, W, xv.ld, dyv.ld)
+    yv = View.alloc(rt, N, Ho, Wo, Co)
+    dwp, nslab, wp, st = nv.ptr(p['dwp'][0]), p['nslab'][0], nv.ptr(p['wp_fwd'][0]), rt.stream
+    assert op.direct_ok()
+
+    huge = _geom(1, 16384, 16384, 8, 8, 3, 1, 1)                  # 2^28 pixels x 8 channels x 2 bytes = 4 GiB
+    wide = _geom(N, H, W, Ci, Co, 3, 1, 1)                        # 64 output channels: what segnb_conv_fprop_drop_ok refuses
+    src = nv.UpcatSrc(xv.ptr, Ci, Ci)                             # Cu == Ci: what segnb_conv_upcat_ok refuses
+    calls = {
+        'oversize_plain': lambda: lib.segnb_conv_fprop(huge, nv.BF16, xv.ptr, wp, None, 0, yv.ptr, None, st),
+        'oversize_upconv': lambda: lib.segnb_upconv_fprop(nv.BF16, 1, 64, 64, 128, 1 << 19, xv.ptr, wp, 64, 64, None, 0, yv.ptr, 64,
+                                                          None, st),
+        'refused_drop': lambda: lib.segnb_conv_fprop_drop(wide, nv.BF16, xv.ptr, wp, None, 0, yv.ptr, xv.ptr, Co, None, 0, st),
+        'refused_upsum': lambda: lib.segnb_conv_fprop_upsum(wide, nv.BF16, xv.ptr, wp, yv.ptr, src, st),
+        'refused_wgrad_upcat': lambda: lib.segnb_conv_wgrad_upcat(g, nv.BF16, xv.ptr, src, dyv.ptr, dwp, nslab, st),
+        'refused_wgrad_tf': lambda: lib.segnb_conv_wgrad_tf(g, nv.BF16, xv.ptr, None, dyv.ptr, None, dwp, nslab, st),
+        'nslab_differs': lambda: lib.segnb_conv_wgrad(g, nv.BF16, xv.ptr, dyv.ptr, dwp, nslab + 1, st),
+    }
+    out = {}
+    for name in sorted(calls):
+        gw = torch.zeros_like(op.weight)
+        p['dwp'][0].zero_()
+        op._arm_target(p, 0, gw)
+        rc = calls[name]()
+        msg = (lib.segnb_last_error() or b'').decode()
+        nv.call('segnb_conv_wgrad', g, nv.BF16, xv.ptr, dyv.ptr, dwp, nslab, st)
+        torch.cuda.synchronize()
+        delivered, in_workspace = bool(gw.abs().sum() > 0), bool(p['dwp'][0][0].abs().sum() > 0)
+        assert delivered or in_workspace, name
+        out[name] = [rc, msg, delivered]
+    return out
+
+
+def record():
+    return {'cases': {k: run_case(v) for k, v in sorted(CASES.items())}, 'predicates': predicate_table(), 'errors': error_paths()}
+
+
+if __name__ == '__main__':
+    a, b = record(), record()
+    for k in a['cases']:
+        print(k, a['cases'][k]['names'])
+        assert a['cases'][k] == b['cases'][k], ('not reproducible', k, a['cases'][k], b['cases'][k])
+    assert a['predicates'] == b['predicates'] and a['errors'] == b['errors']
+    for k, v in sorted(a['errors'].items()):
+        print(k, v)
+    seen = {n for c in a['cases'].values() for side in c['names'] for n in side}
+    assert seen | set(UNREACHED) == set(FPROP_SELECTORS + WGRAD_SELECTORS), sorted(set(FPROP_SELECTORS + WGRAD_SELECTORS) - seen)
+    with open(sys.argv[1] if len(sys.argv) > 1 else JSON_PATH, 'w') as f:
+        json.dump(a, f, indent=0, sort_keys=True, separators=(',', ':'))
+        f.write('\n')
