@@ -20,13 +20,15 @@ struct bf16_t {
 // ------------------------------------------------------------------------------------------------
 void segnb_set_error(const char* fmt, ...);
 
-#define SEGNB_CHECK_ARG(cond, msg)                                   \
+// (the _AS forms: a helper shared by several entry points reports under the name the caller gives it)
+#define SEGNB_CHECK_ARG_AS(who, cond, msg)                           \
     do {                                                             \
         if (!(cond)) {                                               \
-            segnb_set_error("%s: bad argument: %s", __func__, msg);  \
+            segnb_set_error("%s: bad argument: %s", who, msg);       \
             return SEGNB_E_BADARG;                                   \
         }                                                            \
     } while (0)
+#define SEGNB_CHECK_ARG(cond, msg) SEGNB_CHECK_ARG_AS(__func__, cond, msg)
 
 // A launch that can carry the completion event of an armed cross-stream fork (segnb_stream_fork_arm / _commit, runtime.hip): the
 // event rides on the kernel's own dispatch packet (hipExtLaunchKernelGGL stopEvent) instead of a marker packet of its own between
@@ -41,14 +43,15 @@ hipEvent_t segnb_take_armed_event(hipStream_t stream);
             hipLaunchKernelGGL(kernel, grid, block, shmem, stream, __VA_ARGS__);                                \
     } while (0)
 
-#define SEGNB_LAUNCH_CHECK()                                                                  \
+#define SEGNB_LAUNCH_CHECK_AS(who)                                                            \
     do {                                                                                      \
         hipError_t e__ = hipGetLastError();                                                   \
         if (e__ != hipSuccess) {                                                              \
-            segnb_set_error("%s: launch failed: %s", __func__, hipGetErrorString(e__));       \
+            segnb_set_error("%s: launch failed: %s", who, hipGetErrorString(e__));            \
             return (int)e__;                                                                  \
         }                                                                                     \
     } while (0)
+#define SEGNB_LAUNCH_CHECK() SEGNB_LAUNCH_CHECK_AS(__func__)
 
 // ------------------------------------------------------------------------------------------------
 // launch plans (runtime.hip: segnb_plan_begin / _end / _run): while a plan is being recorded on this thread every
@@ -271,6 +274,50 @@ struct Elem<bf16_t> {
     }
     __device__ static __forceinline__ float round(float v) { return bf16_bits_to_f32(f32_to_bf16_bits(v)); }
 };
+
+// ------------------------------------------------------------------------------------------------
+// run-time dtype / flag / small count -> compile-time argument: a launch is written once, generically, in a lambda
+//     if (int rc = segnb_dispatch_dtype(dtype, "segnb_x", [&](auto tag) SEGNB_INLINE_LAMBDA {
+//             using T = SEGNB_TAG_T(tag);
+//             hipLaunchKernelGGL(x_kernel<T>, grid, block, 0, stream, (const T*)in, (T*)out);
+//         })) return rc;
+//     SEGNB_LAUNCH_CHECK();
+// Argument checks and SEGNB_LAUNCH_CHECK stay OUTSIDE the lambda: they print __func__, which inside it is "operator()".
+// SEGNB_INLINE_LAMBDA on every such lambda: left to the inliner a helper lambda became a call per use (conv_igemm.hip).
+// ------------------------------------------------------------------------------------------------
+template <typename T>
+struct segnb_type_tag {
+    using type = T;
+};
+#define SEGNB_TAG_T(tag) typename decltype(tag)::type
+#define SEGNB_INLINE_LAMBDA __attribute__((always_inline))
+// f(segnb_type_tag<bf16_t>) or f(segnb_type_tag<float>); any other dtype is refused here, once, under the caller's name
+template <class F>
+__attribute__((always_inline)) inline int segnb_dispatch_dtype(int dtype, const char* who, F&& f) {
+    if (dtype != SEGNB_BF16 && dtype != SEGNB_F32) {
+        segnb_set_error("%s: unknown dtype %d", who, dtype);
+        return SEGNB_E_BADARG;
+    }
+    dtype == SEGNB_BF16 ? f(segnb_type_tag<bf16_t>{}) : f(segnb_type_tag<float>{});
+    return 0;
+}
+// the refusal alone: for an entry point that has to refuse before it prepares its launch (scratch buffers, later checks)
+inline int segnb_check_dtype(int dtype, const char* who) {
+    return segnb_dispatch_dtype(dtype, who, [](auto) {});
+}
+// f(std::true_type) or f(std::false_type)
+template <class F>
+__attribute__((always_inline)) inline void segnb_dispatch_bool(bool v, F&& f) {
+    v ? f(std::true_type{}) : f(std::false_type{});
+}
+// f(std::integral_constant<int, K>) for the first of the ascending bounds K0, Ks... with v <= K (the last one if none holds)
+template <int K0, int... Ks, class F>
+__attribute__((always_inline)) inline void segnb_dispatch_le(int v, F&& f) {
+    if constexpr (sizeof...(Ks) > 0) {
+        if (v > K0) return segnb_dispatch_le<Ks...>(v, f);
+    }
+    f(std::integral_constant<int, K0>{});
+}
 
 // load / store 8 consecutive channels as fp32
 __device__ __forceinline__ void load8(const float* p, float (&v)[8]) {

@@ -351,16 +351,11 @@ extern "C" int segnb_pack_input_u8(const unsigned char* img, int N, int H, int W
     const long long npix = (long long)N * H * W;
     int grid = ceil_div(npix * (Cp / 8), 256);
     if (grid > 8192) grid = 8192;
-    if (dtype == SEGNB_BF16)
-        hipLaunchKernelGGL(pack_input_u8_kernel<bf16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, u, npix,
-                           (bf16_t*)out, Cp, ld_out);
-    else if (dtype == SEGNB_F32)
-        hipLaunchKernelGGL(pack_input_u8_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, u, npix, (float*)out,
-                           Cp, ld_out);
-    else {
-        segnb_set_error("segnb_pack_input_u8: unknown dtype %d", dtype);
-        return SEGNB_E_BADARG;
-    }
+    if (int rc = segnb_dispatch_dtype(dtype, "segnb_pack_input_u8", [&](auto tag) SEGNB_INLINE_LAMBDA {
+            using T = SEGNB_TAG_T(tag);
+            hipLaunchKernelGGL(pack_input_u8_kernel<T>, dim3(grid), dim3(256), 0, (hipStream_t)stream, u, npix, (T*)out, Cp, ld_out);
+        }))
+        return rc;
     SEGNB_LAUNCH_CHECK();
     return 0;
 }

@@ -4,7 +4,7 @@
 //        unet16.py:111): NHWC activations in, fp32 NCHW logits out (the reference's output layout).
 // loss : lib/losses.py:7-101 and lib/metrics.py:9-43 -- one streaming pass produces every global
 //        sum any of the losses/metrics needs; a second pass writes d(loss)/d(logits).
-#include "common.h"
+#include "ew.h"      // the chunk-column geometry of the head kernels is the one of the BatchNorm passes
 
 #include <mutex>
 #include <vector>
@@ -825,30 +825,24 @@ extern "C" int segnb_head_fwd(int dtype, const void* a, int ld_a, int N, int H, 
     SEGNB_CHECK_ARG(K >= 1 && K <= HEAD_MAXK, "head supports 1..32 classes");
     SEGNB_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && ld_a % 8 == 0 && ld_a >= ((C + 7) & ~7), "bad shape");
     const long long npix = (long long)N * H * W;
+    const hipStream_t st = (hipStream_t)stream;
     if (C > 64) {
         // wide activations: chunk-per-lane walk (whole pixels per wave)
-        const int cpp = (C + 7) / 8;
-        int ct = 1;
-        while (ct < cpp && ct < 32) ct <<= 1;
-        const int py = 256 / ct;
-        long long gx = (npix + py - 1) / py;
+        const EwShape s = make_shape(N, H, W, (C + 7) & ~7);
+        // (not make_grid: ONE block column whatever the chunk count -- the kernel walks the chunk tiles itself -- 4096 blocks
+        // at most, no items-per-thread floor)
+        long long gx = (npix + s.PY - 1) / s.PY;
         if (gx > 4096) gx = 4096;
-        const size_t wsm = (size_t)K * cpp * 8 * sizeof(float);
+        const size_t wsm = (size_t)K * s.CPP * 8 * sizeof(float);
         SEGNB_CHECK_ARG(wsm <= 48 * 1024, "head: K * C too large");
-        if (dtype == SEGNB_BF16)
-            (K == 1 ? head_fwd_wide_kernel<bf16_t, 1> : K <= MAXK ? head_fwd_wide_kernel<bf16_t, MAXK>
-                                                    : K <= 16 ? head_fwd_wide_kernel<bf16_t, 16> : head_fwd_wide_kernel<bf16_t, HEAD_MAXK>)
-                <<<dim3((unsigned)gx), dim3(256), wsm, (hipStream_t)stream>>>((const bf16_t*)a, ld_a, npix, (long long)H * W, C, w, bias, K,
-                                                                             logits, ct);
-        else if (dtype == SEGNB_F32)
-            (K == 1 ? head_fwd_wide_kernel<float, 1> : K <= MAXK ? head_fwd_wide_kernel<float, MAXK>
-                                                   : K <= 16 ? head_fwd_wide_kernel<float, 16> : head_fwd_wide_kernel<float, HEAD_MAXK>)
-                <<<dim3((unsigned)gx), dim3(256), wsm, (hipStream_t)stream>>>((const float*)a, ld_a, npix, (long long)H * W, C, w, bias, K,
-                                                                             logits, ct);
-        else {
-            segnb_set_error("segnb_head_fwd: unknown dtype %d", dtype);
-            return SEGNB_E_BADARG;
-        }
+        if (int rc = segnb_dispatch_dtype(dtype, "segnb_head_fwd", [&](auto tag) SEGNB_INLINE_LAMBDA {
+                using T = SEGNB_TAG_T(tag);
+                segnb_dispatch_le<1, MAXK, 16, HEAD_MAXK>(K, [&](auto KM) SEGNB_INLINE_LAMBDA {
+                    hipLaunchKernelGGL((head_fwd_wide_kernel<T, decltype(KM)::value>), dim3((unsigned)gx), dim3(256), wsm, st,
+                                       (const T*)a, ld_a, npix, (long long)H * W, C, w, bias, K, logits, s.CT);
+                });
+            }))
+            return rc;
         SEGNB_LAUNCH_CHECK();
         return 0;
     }
@@ -856,22 +850,14 @@ extern "C" int segnb_head_fwd(int dtype, const void* a, int ld_a, int N, int H, 
     if (grid > 4096) grid = 4096;
     const int smem = K * ((C + 7) & ~7) * 4;
     SEGNB_CHECK_ARG(smem <= 60 * 1024, "head too wide");
-    if (dtype == SEGNB_BF16 && K <= MAXK)
-        hipLaunchKernelGGL(head_fwd_kernel<bf16_t>, dim3(grid), dim3(256), smem, (hipStream_t)stream,
-                           (const bf16_t*)a, ld_a, npix, (long long)H * W, C, w, bias, K, logits);
-    else if (dtype == SEGNB_F32 && K <= MAXK)
-        hipLaunchKernelGGL(head_fwd_kernel<float>, dim3(grid), dim3(256), smem, (hipStream_t)stream, (const float*)a,
-                           ld_a, npix, (long long)H * W, C, w, bias, K, logits);
-    else if (dtype == SEGNB_BF16)        // 9 .. 32 classes
-        hipLaunchKernelGGL((head_fwd_kernel<bf16_t, HEAD_MAXK>), dim3(grid), dim3(256), smem, (hipStream_t)stream,
-                           (const bf16_t*)a, ld_a, npix, (long long)H * W, C, w, bias, K, logits);
-    else if (dtype == SEGNB_F32)
-        hipLaunchKernelGGL((head_fwd_kernel<float, HEAD_MAXK>), dim3(grid), dim3(256), smem, (hipStream_t)stream, (const float*)a,
-                           ld_a, npix, (long long)H * W, C, w, bias, K, logits);
-    else {
-        segnb_set_error("segnb_head_fwd: unknown dtype %d", dtype);
-        return SEGNB_E_BADARG;
-    }
+    if (int rc = segnb_dispatch_dtype(dtype, "segnb_head_fwd", [&](auto tag) SEGNB_INLINE_LAMBDA {
+            using T = SEGNB_TAG_T(tag);
+            segnb_dispatch_le<MAXK, HEAD_MAXK>(K, [&](auto KM) SEGNB_INLINE_LAMBDA {      // (HEAD_MAXK: 9 .. 32 classes)
+                hipLaunchKernelGGL((head_fwd_kernel<T, decltype(KM)::value>), dim3(grid), dim3(256), smem, st, (const T*)a, ld_a,
+                                   npix, (long long)H * W, C, w, bias, K, logits);
+            });
+        }))
+        return rc;
     SEGNB_LAUNCH_CHECK();
     return 0;
 }
@@ -945,42 +931,33 @@ extern "C" int segnb_head_bwd(int dtype, const void* a, int ld_a, int N, int H, 
     SEGNB_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && Cp % 8 == 0 && Cp >= C, "bad shape");
     const long long npix = (long long)N * H * W;
     SEGNB_CHECK_ARG(npix < (1ll << 30), "pixel count exceeds the 32-bit index range");
-    const int CPP = Cp / 8;
-    int ct = 1;
-    while (ct < CPP && ct < 32) ct <<= 1;
-    const int gy = ceil_div(CPP, ct);
-    const int py = 256 / ct;
-    long long gx = (npix + py - 1) / py;
-    if (gx > 2048 / gy) gx = 2048 / gy;
-    if (gx < 1) gx = 1;
-    const dim3 grid((unsigned)gx, (unsigned)gy);
-    if (dtype != SEGNB_BF16 && dtype != SEGNB_F32) {
-        segnb_set_error("segnb_head_bwd: unknown dtype %d", dtype);
-        return SEGNB_E_BADARG;
-    }
+    // (every block leaves partial sums for the finish launch: one item per thread row, without make_grid's items-per-thread floor)
+    const EwShape s = make_shape(N, H, W, Cp);
+    const dim3 grid = make_grid_dense(s, npix, 2048);
+    const hipStream_t st = (hipStream_t)stream;
+    if (int rc = segnb_check_dtype(dtype, "segnb_head_bwd")) return rc;       // (before the scratch buffer is asked for)
     // per-block partial sums of dw / db (summed in block order by head_bwd_finish_kernel): a library-owned scratch buffer
     // per (device, stream), grown on demand
-    float* part = head_scratch((size_t)gx * gy * K * (ct * 8 + 1) * sizeof(float), (hipStream_t)stream);
+    float* part = head_scratch((size_t)grid.x * grid.y * K * (s.CT * 8 + 1) * sizeof(float), st);
     if (part == nullptr) return SEGNB_E_BADARG;
-    if (K > MAXK) {
-        // 9 .. 32 classes: class chunks of MAXK along z, the weight slice [K][ct * 8] in LDS (32 KB at most)
-        const dim3 gridz((unsigned)gx, (unsigned)gy, (unsigned)ceil_div(K, MAXK));
-        const size_t wsm = (size_t)K * ct * 8 * sizeof(float);
-        if (dtype == SEGNB_BF16)
-            head_bwd_many_kernel<bf16_t><<<gridz, dim3(256), wsm, (hipStream_t)stream>>>(
-                (const bf16_t*)a, ld_a, npix, (long long)H * W, C, Cp, w, K, dlogits, (bf16_t*)da, ld_da, part, ct);
-        else
-            head_bwd_many_kernel<float><<<gridz, dim3(256), wsm, (hipStream_t)stream>>>(
-                (const float*)a, ld_a, npix, (long long)H * W, C, Cp, w, K, dlogits, (float*)da, ld_da, part, ct);
-    } else if (dtype == SEGNB_BF16)
-        (K == 1 ? head_bwd_kernel<bf16_t, 1> : head_bwd_kernel<bf16_t, MAXK>)<<<grid, dim3(256), 0, (hipStream_t)stream>>>(
-            (const bf16_t*)a, ld_a, npix, (long long)H * W, C, Cp, w, K, dlogits, (bf16_t*)da, ld_da, part, ct);
-    else
-        (K == 1 ? head_bwd_kernel<float, 1> : head_bwd_kernel<float, MAXK>)<<<grid, dim3(256), 0, (hipStream_t)stream>>>(
-            (const float*)a, ld_a, npix, (long long)H * W, C, Cp, w, K, dlogits, (float*)da, ld_da, part, ct);
+    segnb_dispatch_dtype(dtype, "segnb_head_bwd", [&](auto tag) SEGNB_INLINE_LAMBDA {
+        using T = SEGNB_TAG_T(tag);
+        if (K > MAXK) {
+            // 9 .. 32 classes: class chunks of MAXK along z, the weight slice [K][CT * 8] in LDS (32 KB at most)
+            const dim3 gridz(grid.x, grid.y, (unsigned)ceil_div(K, MAXK));
+            const size_t wsm = (size_t)K * s.CT * 8 * sizeof(float);
+            hipLaunchKernelGGL(head_bwd_many_kernel<T>, gridz, dim3(256), wsm, st, (const T*)a, ld_a, npix, (long long)H * W, C, Cp,
+                               w, K, dlogits, (T*)da, ld_da, part, s.CT);
+            return;
+        }
+        segnb_dispatch_le<1, MAXK>(K, [&](auto KM) SEGNB_INLINE_LAMBDA {
+            hipLaunchKernelGGL((head_bwd_kernel<T, decltype(KM)::value>), grid, dim3(256), 0, st, (const T*)a, ld_a, npix,
+                               (long long)H * W, C, Cp, w, K, dlogits, (T*)da, ld_da, part, s.CT);
+        });
+    });
     SEGNB_LAUNCH_CHECK();
     if (dw != nullptr || db != nullptr) {
-        head_bwd_finish_kernel<<<dim3(K * C + K), dim3(256), 0, (hipStream_t)stream>>>(part, (int)gx, gy, K, C, ct, dw, db, 1);
+        head_bwd_finish_kernel<<<dim3(K * C + K), dim3(256), 0, st>>>(part, (int)grid.x, (int)grid.y, K, C, s.CT, dw, db, 1);
         SEGNB_LAUNCH_CHECK();
     }
     return 0;
@@ -1001,31 +978,21 @@ extern "C" int segnb_head_conv_fwd(int dtype, const void* a, int ld_a, int N, in
     SEGNB_CHECK_ARG(Ho > 0 && Wo > 0, "empty output");
     const long long npix = (long long)N * Ho * Wo;
     SEGNB_CHECK_ARG(npix < (1ll << 30) && (long long)N * Hi * Wi < (1ll << 30), "pixel count exceeds the 32-bit index range");
-    const int cpp = (C + 7) / 8;
-    int ct = 1;
-    while (ct < cpp) ct <<= 1;
-    const int py = 256 / ct;
-    long long gx = (npix + py - 1) / py;
+    // (C <= 64 -- segnb_head_conv_ok above -- is at most 8 chunks: make_shape's bound of 32 columns never binds here)
+    const EwShape s = make_shape(N, Ho, Wo, (C + 7) & ~7);
+    // (not make_grid: one block column, a cap of 16384 blocks of its own, no items-per-thread floor)
+    long long gx = (npix + s.PY - 1) / s.PY;
     if (gx > 16384) gx = 16384;
     const int grid = (int)gx;
-    const int smem = K * kh * kw * cpp * 8 * 4;
-    const int nt = kh * kw;
-#define SEGNB_HEAD_CONV_FWD(TT, NTM_)                                                                                         \
-    hipLaunchKernelGGL((head_conv_fwd_kernel<TT, NTM_>), dim3(grid), dim3(256), smem, (hipStream_t)stream, (const TT*)a, ld_a, N, Hi, \
-                       Wi, C, w, kh, kw, pad, bias, K, Ho, Wo, logits, ct)
-    if (dtype == SEGNB_BF16) {
-        if (nt == 1) SEGNB_HEAD_CONV_FWD(bf16_t, 1);
-        else if (nt <= 4) SEGNB_HEAD_CONV_FWD(bf16_t, 4);
-        else SEGNB_HEAD_CONV_FWD(bf16_t, MAXK);
-    } else if (dtype == SEGNB_F32) {
-        if (nt == 1) SEGNB_HEAD_CONV_FWD(float, 1);
-        else if (nt <= 4) SEGNB_HEAD_CONV_FWD(float, 4);
-        else SEGNB_HEAD_CONV_FWD(float, MAXK);
-    } else {
-        segnb_set_error("segnb_head_conv_fwd: unknown dtype %d", dtype);
-        return SEGNB_E_BADARG;
-    }
-#undef SEGNB_HEAD_CONV_FWD
+    const int smem = K * kh * kw * s.CPP * 8 * 4;
+    if (int rc = segnb_dispatch_dtype(dtype, "segnb_head_conv_fwd", [&](auto tag) SEGNB_INLINE_LAMBDA {
+            using T = SEGNB_TAG_T(tag);
+            segnb_dispatch_le<1, 4, MAXK>(kh * kw, [&](auto NTM) SEGNB_INLINE_LAMBDA {      // window positions
+                hipLaunchKernelGGL((head_conv_fwd_kernel<T, decltype(NTM)::value>), dim3(grid), dim3(256), smem, (hipStream_t)stream,
+                                   (const T*)a, ld_a, N, Hi, Wi, C, w, kh, kw, pad, bias, K, Ho, Wo, logits, s.CT);
+            });
+        }))
+        return rc;
     SEGNB_LAUNCH_CHECK();
     return 0;
 }
@@ -1043,43 +1010,29 @@ extern "C" int segnb_head_conv_bwd(int dtype, const void* a, int ld_a, int N, in
     SEGNB_CHECK_ARG(da == nullptr || (ld_da % 8 == 0 && ld_da >= Cp), "bad gradient stride");
     SEGNB_CHECK_ARG(act < 0 || ((act == SEGNB_ACT_NONE || act == SEGNB_ACT_RELU || act == SEGNB_ACT_LEAKY) && da != nullptr),
                     "act: -1 (plain gradient) or the producing layer's activation, with da");
-    if (dtype != SEGNB_BF16 && dtype != SEGNB_F32) {
-        segnb_set_error("segnb_head_conv_bwd: unknown dtype %d", dtype);
-        return SEGNB_E_BADARG;
-    }
+    if (int rc = segnb_check_dtype(dtype, "segnb_head_conv_bwd")) return rc;      // (in front of the checks below, as it always was)
     const int Ho = Hi + 2 * pad - kh + 1, Wo = Wi + 2 * pad - kw + 1;
     SEGNB_CHECK_ARG(Ho > 0 && Wo > 0, "empty output");
     const int Hu = Hi > Ho ? Hi : Ho, Wu = Wi > Wo ? Wi : Wo;
     const long long npix = (long long)N * Hu * Wu;
     SEGNB_CHECK_ARG(npix < (1ll << 30), "pixel count exceeds the 32-bit index range");
     const int KT = K * kh * kw;
-    const int CPP = Cp / 8;
-    int ct = 1;
-    while (ct < CPP && ct < 32) ct <<= 1;
-    const int gy = ceil_div(CPP, ct);
-    const int py = 256 / ct;
-    long long gx = (npix + py - 1) / py;
-    if (gx > 2048 / gy) gx = 2048 / gy;
-    if (gx < 1) gx = 1;
-    const dim3 grid((unsigned)gx, (unsigned)gy);
-    float* part = head_scratch((size_t)gx * gy * KT * (ct * 8 + 1) * sizeof(float), (hipStream_t)stream);
+    // (partial sums per block, as segnb_head_bwd: one item per thread row)
+    const EwShape s = make_shape(N, Hu, Wu, Cp);
+    const dim3 grid = make_grid_dense(s, npix, 2048);
+    const hipStream_t st = (hipStream_t)stream;
+    float* part = head_scratch((size_t)grid.x * grid.y * KT * (s.CT * 8 + 1) * sizeof(float), st);
     if (part == nullptr) return SEGNB_E_BADARG;
-#define SEGNB_HEAD_CONV_BWD(TT, KM_)                                                                                              \
-    head_conv_bwd_kernel<TT, KM_><<<grid, dim3(256), 0, (hipStream_t)stream>>>((const TT*)a, ld_a, N, Hi, Wi, C, Cp, w, kh, kw, pad, K, \
-                                                                              Ho, Wo, dlogits, act, slope, (TT*)da, ld_da, part, sums, ct)
-    if (dtype == SEGNB_BF16) {
-        if (KT == 1) SEGNB_HEAD_CONV_BWD(bf16_t, 1);
-        else if (KT <= 4) SEGNB_HEAD_CONV_BWD(bf16_t, 4);
-        else SEGNB_HEAD_CONV_BWD(bf16_t, MAXK);
-    } else {
-        if (KT == 1) SEGNB_HEAD_CONV_BWD(float, 1);
-        else if (KT <= 4) SEGNB_HEAD_CONV_BWD(float, 4);
-        else SEGNB_HEAD_CONV_BWD(float, MAXK);
-    }
-#undef SEGNB_HEAD_CONV_BWD
+    segnb_dispatch_dtype(dtype, "segnb_head_conv_bwd", [&](auto tag) SEGNB_INLINE_LAMBDA {
+        using T = SEGNB_TAG_T(tag);
+        segnb_dispatch_le<1, 4, MAXK>(KT, [&](auto KM) SEGNB_INLINE_LAMBDA {      // classes x window positions
+            hipLaunchKernelGGL((head_conv_bwd_kernel<T, decltype(KM)::value>), grid, dim3(256), 0, st, (const T*)a, ld_a, N, Hi, Wi, C,
+                               Cp, w, kh, kw, pad, K, Ho, Wo, dlogits, act, slope, (T*)da, ld_da, part, sums, s.CT);
+        });
+    });
     SEGNB_LAUNCH_CHECK();
     if (dw != nullptr || db != nullptr) {
-        head_bwd_finish_kernel<<<dim3(KT * C + K), dim3(256), 0, (hipStream_t)stream>>>(part, (int)gx, gy, KT, C, ct, dw, db, kh * kw);
+        head_bwd_finish_kernel<<<dim3(KT * C + K), dim3(256), 0, st>>>(part, (int)grid.x, (int)grid.y, KT, C, s.CT, dw, db, kh * kw);
         SEGNB_LAUNCH_CHECK();
     }
     return 0;

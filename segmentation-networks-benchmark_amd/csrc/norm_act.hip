@@ -1,4 +1,4 @@
-// BatchNorm / activation / Dropout2d / MaxPool2d(2) / nearest-x2 Upsample, fused, NHWC, gfx950.
+// BatchNorm + activation, with Dropout2d / MaxPool2d(2) / nearest-x2 Upsample fused into its passes, NHWC, gfx950.
 //
 // Replaces nn.BatchNorm2d + nn.ReLU (lib/models/zf_unet.py:9-10,15-16), nn.Dropout2d (:25,31),
 // nn.MaxPool2d(2) (:41), nn.Upsample(scale_factor=2) (:42) and torch.cat (:78-90, via `ld` slices)
@@ -7,44 +7,18 @@
 //
 // All kernels are HBM-bound streams: 16-byte vectors (8 channels per thread), one thread column per
 // 8-channel chunk so per-channel sums stay in registers, wave/LDS reduction, fp64 global atomics.
-#include "common.h"
+//
+// This file is the BatchNorm family: the statistics pass, the two finalize pairs, the activation pass forward (with its fused
+// finalize, pooled / upsampled / residual / classifier / output-statistics forms) and backward (reduction over the gradient
+// sources, the apply forms), the head-fused last layer, segnb_bias_grad_multi and the segnb_abn_* pair.  The other element-wise
+// passes (add, general MaxPool2d, bilinear upsampling, layout move, optimizer steps) are elementwise.hip; the launch geometry
+// both share is ew.h.  Every entry point writes its launch once, generically in the element type (segnb_dispatch_dtype,
+// common.h).
+#include "ew.h"
 
 namespace {
 
-constexpr int NTHR = 256;
 constexpr int REPL = SEGNB_STAT_REPLICAS;
-
-struct EwShape {
-    int N, H, W, Cp;
-    int CPP;  // 8-channel chunks per pixel
-    int CT;   // chunk columns per block (power of two <= 32)
-    int PY;   // pixel rows per block = 256 / CT
-};
-
-static EwShape make_shape(int N, int H, int W, int Cp) {
-    EwShape s;
-    s.N = N; s.H = H; s.W = W; s.Cp = Cp;
-    s.CPP = Cp / 8;
-    int ct = 1;
-    while (ct < s.CPP && ct < 32) ct <<= 1;
-    s.CT = ct;
-    s.PY = NTHR / ct;
-    return s;
-}
-
-static dim3 make_grid(const EwShape& s, long long items, int max_blocks = 2048) {
-    // few, fat blocks: every block ends with one atomic per channel into the same addresses, and
-    // same-address atomics serialise (MI355X_MICROARCH: ~14x slower than spread ones)
-    const int gy = ceil_div(s.CPP, s.CT);
-    long long gx = (items + s.PY - 1) / s.PY;
-    long long cap = max_blocks / gy;
-    if (cap < 1) cap = 1;
-    if (gx > cap) gx = cap;
-    const long long want = (items + 4ll * s.PY - 1) / (4ll * s.PY);     // >= 4 items per thread
-    if (gx > want) gx = want;
-    if (gx < 1) gx = 1;
-    return dim3((unsigned)gx, (unsigned)gy);
-}
 
 // Branch-free activations: none / ReLU / LeakyReLU are all "negative side scaled by s" with s = 1 / 0 / slope (a
 // switch on `act` per element compiled to two scalar branches per element -- 153 branches in the pooled backward
@@ -63,20 +37,21 @@ __device__ __forceinline__ float act_grad(float z, int act, float slope) {
 // per-channel forward coefficients from the replicated statistics (training) or the running statistics (eval);
 // `update` = this thread owns the channel's side effects (running statistics)
 struct BnFwdParams {
-    const double* stats;        // [REPL][2][Cp]; read-only in the fused kernel
-    double count;
-    const float* gamma;
-    const float* beta;
-    float eps, momentum;
-    float* running_mean;
-    float* running_var;
-    long long* nbt;
-    int C, training;
-    float* coef;                // [4][Cp] out
-    double* zero_buf;           // fused only: the BACKWARD accumulators of this layer, cleared for this step
-    int keep_stats;             // segnb_bn_finalize_keep: the statistics are left for the backward to clear (fused protocol)
-    int stats_ld;               // channel stride between the [REPL][2] rows of `stats` (0: Cp) -- a channel RANGE of a wider table
+    const double* stats = nullptr;      // [REPL][2][Cp]; read-only in the fused kernel
+    double count = 0.0;
+    const float* gamma = nullptr;
+    const float* beta = nullptr;
+    float eps = 0.f, momentum = 0.f;
+    float* running_mean = nullptr;
+    float* running_var = nullptr;
+    long long* nbt = nullptr;
+    int C = 0, training = 0;
+    float* coef = nullptr;              // [4][Cp] out
+    double* zero_buf = nullptr;         // fused only: the BACKWARD accumulators of this layer, cleared for this step
+    int keep_stats = 0;                 // segnb_bn_finalize_keep: the statistics are left for the backward to clear (fused protocol)
+    int stats_ld = 0;                   // channel stride between the [REPL][2] rows of `stats` (0: Cp) -- a channel RANGE of a wider table
 };
+static_assert(sizeof(BnFwdParams) == 96, "BnFwdParams is a kernel argument: its layout is part of the device code");
 
 __device__ __forceinline__ void bn_fwd_coef(const BnFwdParams& p, int Cp, int c, bool update, float& scale,
                                             float& shift, float& mean, float& invstd) {
@@ -225,19 +200,6 @@ __device__ __forceinline__ void round_store8(bf16_t* p, float (&v)[8]) {
     v[6] = __uint_as_float(u.w << 16); v[7] = __uint_as_float(u.w & 0xffff0000u);
     if (p != nullptr) *reinterpret_cast<uint4*>(p) = u;
 }
-
-// exact a / d for 0 <= a < 2^31 through a double reciprocal (8 instructions; the integer division sequence is ~35 and
-// the pooled kernels are VALU-bound): the truncated product is off by at most one, the remainder says which way
-struct FastDiv {
-    int d;
-    double inv;
-    __device__ __forceinline__ explicit FastDiv(int d_) : d(d_), inv(1.0 / (double)d_) {}
-    __device__ __forceinline__ int div(int a) const {
-        const int q = (int)((double)a * inv);
-        const int r = a - q * d;
-        return q + (r >= d ? 1 : 0) - (r < 0 ? 1 : 0);
-    }
-};
 
 // the 1x1 classifier on the activated values of the pass (segnb_bn_fwd_fused_head): fp32 NCHW logits
 struct HeadFwd {
@@ -530,15 +492,16 @@ __global__ __launch_bounds__(NTHR) void bn_act_fwd_kernel(const T* __restrict__ 
 }
 
 struct BnBwdParams {
-    const double* sums;         // [REPL][2][Cp]: sum dz, sum dz*yhat; read-only in the fused kernel
-    double count;
-    const float* gamma;
-    float* dgamma;
-    float* dbeta;
-    int C, accumulate;
-    float* bcoef;               // [3][Cp] out
-    double* zero_buf;           // fused only: the FORWARD statistics of this layer, cleared for the next step
+    const double* sums = nullptr;       // [REPL][2][Cp]: sum dz, sum dz*yhat; read-only in the fused kernel
+    double count = 0.0;
+    const float* gamma = nullptr;
+    float* dgamma = nullptr;
+    float* dbeta = nullptr;
+    int C = 0, accumulate = 0;
+    float* bcoef = nullptr;             // [3][Cp] out
+    double* zero_buf = nullptr;         // fused only: the FORWARD statistics of this layer, cleared for the next step
 };
+static_assert(sizeof(BnBwdParams) == 64, "BnBwdParams is a kernel argument: its layout is part of the device code");
 
 // bcoef = (gamma*invstd, mean(dz), mean(dz*yhat)); `update` = this thread owns dgamma / dbeta of the channel
 __device__ __forceinline__ void bn_bwd_coef(const BnBwdParams& p, const float* __restrict__ coef, int Cp, int c,
@@ -1275,41 +1238,6 @@ __global__ __launch_bounds__(NTHR) void bn_bwd_apply_kernel(const T* __restrict_
 // from 4.835 to 4.869 ms (+0.7 %; LinkNet34 +1.5 %): the weight gradients it now shares CUs with finish later and the data gradients
 // behind the pass get fewer free CUs.  Removed; profiles/r05_ab.txt.)
 
-__global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, long long n, float lr) {
-    const long long n4 = n >> 2;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += stride) {
-        float4 pv = reinterpret_cast<float4*>(p)[i];
-        const float4 gv = reinterpret_cast<const float4*>(g)[i];
-        pv.x -= lr * gv.x; pv.y -= lr * gv.y; pv.z -= lr * gv.z; pv.w -= lr * gv.w;
-        reinterpret_cast<float4*>(p)[i] = pv;
-    }
-    for (long long i = (n4 << 2) + blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += stride)
-        p[i] -= lr * g[i];
-}
-
-// ------------------------------------------------------------------------------------------------
-// small generic NHWC ops for the other model families (LinkNet34 / FCDenseNet / UNet16)
-// ------------------------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(NTHR) void add_kernel(const T* __restrict__ a, int ld_a, const T* __restrict__ b, int ld_b,
-                                                   T* __restrict__ out, int ld_out, long long npix, int CPP) {
-    const long long total = npix * CPP;
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
-         i += (long long)gridDim.x * blockDim.x) {
-        const long long pix = i / CPP;
-        const int c0 = (int)(i - pix * CPP) * 8;
-        float x[8], yv[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) x[e] = yv[e] = 0.f;
-        if (a != nullptr) load8(a + pix * ld_a + c0, x);          // (a missing operand counts as zeros: copy / clear)
-        if (b != nullptr) load8(b + pix * ld_b + c0, yv);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) x[e] += yv[e];
-        store8(out + pix * ld_out + c0, x);
-    }
-}
-
 // per-channel sum / sum of squares of an NHWC tensor (BatchNorm statistics of an arbitrary input:
 // pre-activation BatchNorm of tiramisu.py:12,50)
 template <typename T>
@@ -1338,186 +1266,65 @@ __global__ __launch_bounds__(NTHR) void bn_stats_kernel(const T* __restrict__ x,
     block_channel_sum2(s1, s2, s, tx, blockIdx.y * s.CT, rep, rep + stats_ld, sred);
 }
 
-// MaxPool2d(k, stride, pad) forward (floor mode) and its gather-form backward: every input pixel checks the
-// (up to ceil(k/stride)^2) windows that contain it and takes the window's gradient if it is that window's
-// FIRST maximum in scan order (torch's tie rule).
-template <typename T>
-__global__ __launch_bounds__(NTHR) void maxpool_fwd_kernel(const T* __restrict__ x, int ld_x, int N, int H, int W, int CPP,
-                                                           int k, int st, int pd, int Ho, int Wo, T* __restrict__ out,
-                                                           int ld_out, unsigned char* __restrict__ idx) {
-    const long long total = (long long)N * Ho * Wo * CPP;
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
-         i += (long long)gridDim.x * blockDim.x) {
-        const int c0 = (int)(i % CPP) * 8;
-        long long q = i / CPP;
-        const int wo = (int)(q % Wo);
-        q /= Wo;
-        const int ho = (int)(q % Ho);
-        const int n = (int)(q / Ho);
-        float m[8];
-        unsigned am[8];                    // window position a * k + b of the FIRST maximum in scan order (torch's tie rule)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            m[e] = -INFINITY;
-            am[e] = 255u;
-        }
-        for (int a = 0; a < k; ++a)
-            for (int b = 0; b < k; ++b) {
-                const int hi = ho * st - pd + a, wi = wo * st - pd + b;
-                if ((unsigned)hi < (unsigned)H && (unsigned)wi < (unsigned)W) {
-                    float v[8];
-                    load8(x + (((long long)n * H + hi) * W + wi) * ld_x + c0, v);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e)
-                        if (v[e] > m[e] || am[e] == 255u) {
-                            m[e] = v[e];
-                            am[e] = (unsigned)(a * k + b);
-                        }
-                }
-            }
-        store8(out + (((long long)n * Ho + ho) * Wo + wo) * ld_out + c0, m);
-        if (idx != nullptr) {
-            uint2 pk;
-            pk.x = am[0] | (am[1] << 8) | (am[2] << 16) | (am[3] << 24);
-            pk.y = am[4] | (am[5] << 8) | (am[6] << 16) | (am[7] << 24);
-            *reinterpret_cast<uint2*>(idx + (i / CPP) * (long long)(CPP * 8) + c0) = pk;
-        }
-    }
+// ------------------------------------------------------------------------------------------------
+// host side: what several entry points say, said once
+// ------------------------------------------------------------------------------------------------
+// training-mode forward block; a caller that keeps the statistics or reads a channel range of a wider table sets
+// keep_stats / stats_ld by name
+inline BnFwdParams make_bn_fwd_params(const double* stats, double count, const float* gamma, const float* beta, float eps,
+                                      float momentum, float* running_mean, float* running_var, long long* nbt, int C,
+                                      float* coef, double* bwd_sums_to_clear) {
+    BnFwdParams p;
+    p.stats = stats, p.count = count;
+    p.gamma = gamma, p.beta = beta;
+    p.eps = eps, p.momentum = momentum;
+    p.running_mean = running_mean, p.running_var = running_var, p.nbt = nbt;
+    p.C = C, p.training = 1;
+    p.coef = coef, p.zero_buf = bwd_sums_to_clear;
+    return p;
 }
 
-template <typename T>
-__global__ __launch_bounds__(NTHR) void maxpool_bwd_kernel(const T* __restrict__ x, int ld_x, const T* __restrict__ go,
-                                                           int ld_go, int N, int H, int W, int CPP, int k, int st,
-                                                           int pd, int Ho, int Wo, T* __restrict__ dx, int ld_dx) {
-    const long long total = (long long)N * H * W * CPP;
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
-         i += (long long)gridDim.x * blockDim.x) {
-        const int c0 = (int)(i % CPP) * 8;
-        long long q = i / CPP;
-        const int w = (int)(q % W);
-        q /= W;
-        const int h = (int)(q % H);
-        const int n = (int)(q / H);
-        float me[8], g[8];
-        load8(x + (((long long)n * H + h) * W + w) * ld_x + c0, me);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) g[e] = 0.f;
-        // windows (ho, wo) with ho*st - pd <= h <= ho*st - pd + k - 1
-        int ho_lo = (h + pd - k + st) / st;
-        if (h + pd - k + 1 < 0) ho_lo = 0;
-        int wo_lo = (w + pd - k + st) / st;
-        if (w + pd - k + 1 < 0) wo_lo = 0;
-        const int ho_hi = min((h + pd) / st, Ho - 1), wo_hi = min((w + pd) / st, Wo - 1);
-        for (int ho = ho_lo; ho <= ho_hi; ++ho)
-            for (int wo = wo_lo; wo <= wo_hi; ++wo) {
-                // is (h, w) the first maximum of window (ho, wo)?
-                bool win[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) win[e] = true;
-                for (int a = 0; a < k; ++a)
-                    for (int b = 0; b < k; ++b) {
-                        const int hi = ho * st - pd + a, wi = wo * st - pd + b;
-                        if ((unsigned)hi >= (unsigned)H || (unsigned)wi >= (unsigned)W) continue;
-                        if (hi == h && wi == w) continue;
-                        const bool before = hi < h || (hi == h && wi < w);
-                        float v[8];
-                        load8(x + (((long long)n * H + hi) * W + wi) * ld_x + c0, v);
-#pragma unroll
-                        for (int e = 0; e < 8; ++e)
-                            if (before ? v[e] >= me[e] : v[e] > me[e]) win[e] = false;
-                    }
-                float gv[8];
-                load8(go + (((long long)n * Ho + ho) * Wo + wo) * ld_go + c0, gv);
-#pragma unroll
-                for (int e = 0; e < 8; ++e)
-                    if (win[e]) g[e] += gv[e];
-            }
-        store8(dx + (((long long)n * H + h) * W + w) * ld_dx + c0, g);
-    }
+inline BnBwdParams make_bn_bwd_params(const double* sums, double count, const float* gamma, float* dgamma, float* dbeta, int C,
+                                      int accumulate, float* bcoef, double* fwd_stats_to_clear) {
+    BnBwdParams p;
+    p.sums = sums, p.count = count;
+    p.gamma = gamma, p.dgamma = dgamma, p.dbeta = dbeta;
+    p.C = C, p.accumulate = accumulate;
+    p.bcoef = bcoef, p.zero_buf = fwd_stats_to_clear;
+    return p;
 }
 
-// The same from the argmax positions the forward pass recorded (segnb_maxpool_fwd idx): a pixel reads one index vector and
-// one gradient vector per covering window (<= ceil(k / stride)^2 of them) instead of re-scanning every window --
-// 3x3 stride 2 at 256x256x64 (the ResNet stem of LinkNet34 at 512x512): 2.4 ms -> the price of a streaming pass.
-// I32: N * H * W * CPP < 2^31 -- the index decomposition on 32-bit integers with reciprocal divisions (three 64-bit divisions per
-// item were half of the kernel's issue slots: 89 -> 6x us on LinkNet34's stem, 16 x 256 x 256 x 64)
-template <typename T, bool I32>
-__global__ __launch_bounds__(NTHR) void maxpool_bwd_idx_kernel(const unsigned char* __restrict__ idx, const T* __restrict__ go,
-                                                               int ld_go, int N, int H, int W, int CPP, int k, int st,
-                                                               int pd, int Ho, int Wo, T* __restrict__ dx, int ld_dx,
-                                                               const T* __restrict__ go2, int ld_go2) {
-    // go2 (segnb_maxpool_bwd_add): a second gradient of the pooled tensor (two consumers: linknet.py:41-62's first BasicBlock and
-    // its identity branch); the routed value is round(go + go2), what segnb_add would have stored
-    const long long total = (long long)N * H * W * CPP;
-    const FastDiv d_cpp(CPP), d_w(W), d_h(H);
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
-         i += (long long)gridDim.x * blockDim.x) {
-        int c0, w, h, n;
-        if constexpr (I32) {
-            const int ii = (int)i;
-            const int q0 = d_cpp.div(ii);
-            c0 = (ii - q0 * CPP) * 8;
-            const int q1 = d_w.div(q0);
-            w = q0 - q1 * W;
-            n = d_h.div(q1);
-            h = q1 - n * H;
-        } else {
-            c0 = (int)(i % CPP) * 8;
-            long long q = i / CPP;
-            w = (int)(q % W);
-            q /= W;
-            h = (int)(q % H);
-            n = (int)(q / H);
-        }
-        float g[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) g[e] = 0.f;
-        int ho_lo = (h + pd - k + st) / st;
-        if (h + pd - k + 1 < 0) ho_lo = 0;
-        int wo_lo = (w + pd - k + st) / st;
-        if (w + pd - k + 1 < 0) wo_lo = 0;
-        const int ho_hi = min((h + pd) / st, Ho - 1), wo_hi = min((w + pd) / st, Wo - 1);
-        for (int ho = ho_lo; ho <= ho_hi; ++ho)
-            for (int wo = wo_lo; wo <= wo_hi; ++wo) {
-                const unsigned mine = (unsigned)((h - (ho * st - pd)) * k + (w - (wo * st - pd)));
-                const long long wpix = ((long long)n * Ho + ho) * Wo + wo;
-                const uint2 pk = *reinterpret_cast<const uint2*>(idx + wpix * (long long)(CPP * 8) + c0);
-                float gv[8];
-                load8(go + wpix * ld_go + c0, gv);
-                if (go2 != nullptr) {
-                    float g2[8];
-                    load8(go2 + wpix * ld_go2 + c0, g2);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) gv[e] = round_as(gv[e] + g2[e], (const T*)nullptr);
-                }
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const unsigned a = ((e < 4 ? pk.x : pk.y) >> (8 * (e & 3))) & 0xffu;
-                    if (a == mine) g[e] += gv[e];
-                }
-            }
-        store8(dx + (((long long)n * H + h) * W + w) * ld_dx + c0, g);
-    }
-}
-
-template <typename T>
-__global__ void nhwc_to_nchw_f32_kernel(const T* __restrict__ a, int ld, int N, int H, int W, int C,
-                                        float* __restrict__ out) {
-    const long long total = (long long)N * C * H * W;
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
-         i += (long long)gridDim.x * blockDim.x) {
-        const long long hw = i % ((long long)H * W);
-        const long long q = i / ((long long)H * W);
-        const int c = (int)(q % C);
-        const long long n = q / C;
-        out[i] = Elem<T>::to_f32(a[(n * H * W + hw) * ld + c]);
-    }
-}
-
-int check_ew(int N, int H, int W, int Cp) {
-    SEGNB_CHECK_ARG(N > 0 && H > 0 && W > 0 && Cp > 0 && Cp % 8 == 0, "bad NHWC shape (Cp % 8 != 0?)");
-    SEGNB_CHECK_ARG((long long)N * H * W * 4 < (1ll << 31), "pixel count exceeds int32");
+// what a fused apply needs before it builds its block
+inline int check_bn_bwd_params(const char* who, const double* sums, const float* bcoef, int C, int Cp) {
+    SEGNB_CHECK_ARG_AS(who, sums != nullptr && bcoef != nullptr && C > 0 && Cp >= C, "missing sums / coefficient buffer");
     return 0;
+}
+
+// the launch tails of segnb_bn_finalize / _keep and of segnb_bn_bwd_finalize / _clear
+inline int launch_bn_finalize(const char* who, const BnFwdParams& fp, int Cp, segnb_stream_t stream) {
+    hipLaunchKernelGGL(bn_finalize_kernel, dim3(ceil_div(Cp, 64)), dim3(64), 0, (hipStream_t)stream, fp, Cp);
+    SEGNB_LAUNCH_CHECK_AS(who);
+    return 0;
+}
+
+inline int launch_bn_bwd_finalize(const char* who, const BnBwdParams& bp, const float* coef, int Cp, segnb_stream_t stream) {
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(ceil_div(Cp, 64)), dim3(64), 0, (hipStream_t)stream, bp, coef, Cp);
+    SEGNB_LAUNCH_CHECK_AS(who);
+    return 0;
+}
+
+// The gradient sources of a backward pass -- direct, pooled (MaxPool2d(2) of the activation), upsampled (nearest x2) -- as the
+// HAS_D / HAS_P / HAS_U arguments of bn_act_bwd_reduce_kernel: f(D, P, U), three std::bool_constant.  Every caller refuses a pass
+// without a source, so that combination has no instantiation; the pass walks walk_items(N, H, W, g_pool != nullptr) items.
+template <class F>
+__attribute__((always_inline)) inline void dispatch_sources(const void* g_direct, const void* g_pool, const void* g_up, F&& f) {
+    segnb_dispatch_bool(g_direct != nullptr, [&](auto D) SEGNB_INLINE_LAMBDA {
+        segnb_dispatch_bool(g_pool != nullptr, [&](auto P) SEGNB_INLINE_LAMBDA {
+            segnb_dispatch_bool(g_up != nullptr, [&](auto U) SEGNB_INLINE_LAMBDA {
+                if constexpr (decltype(D)::value || decltype(P)::value || decltype(U)::value) f(D, P, U);
+            });
+        });
+    });
 }
 
 }  // namespace
@@ -1530,10 +1337,9 @@ extern "C" int segnb_bn_finalize(double* stats, int C, int Cp, double count, con
     SEGNB_CHECK_ARG(coef != nullptr && C > 0 && Cp >= C && Cp % 8 == 0, "bad channel counts");
     SEGNB_CHECK_ARG(training ? stats != nullptr : (running_mean != nullptr && running_var != nullptr),
                     "missing statistics source");
-    BnFwdParams fp = {stats, count, gamma, beta, eps, momentum, running_mean, running_var, nbt, C, training, coef, nullptr};
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3(ceil_div(Cp, 64)), dim3(64), 0, (hipStream_t)stream, fp, Cp);
-    SEGNB_LAUNCH_CHECK();
-    return 0;
+    BnFwdParams fp = make_bn_fwd_params(stats, count, gamma, beta, eps, momentum, running_mean, running_var, nbt, C, coef, nullptr);
+    fp.training = training;
+    return launch_bn_finalize("segnb_bn_finalize", fp, Cp, stream);
 }
 
 // The finalize of a layer whose activation pass does not exist (its consumer applies the activation while it loads:
@@ -1545,10 +1351,9 @@ extern "C" int segnb_bn_finalize_keep(const double* stats, int C, int Cp, double
                                       float* coef, double* clear_sums, segnb_stream_t stream) {
     SEGNB_PLAN_RECORD(segnb_bn_finalize_keep, stats, C, Cp, count, gamma, beta, eps, momentum, running_mean, running_var, nbt, coef, clear_sums, stream);
     SEGNB_CHECK_ARG(stats != nullptr && coef != nullptr && C > 0 && Cp >= C && Cp % 8 == 0, "bad arguments");
-    BnFwdParams fp = {stats, count, gamma, beta, eps, momentum, running_mean, running_var, nbt, C, 1, coef, clear_sums, 1};
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3(ceil_div(Cp, 64)), dim3(64), 0, (hipStream_t)stream, fp, Cp);
-    SEGNB_LAUNCH_CHECK();
-    return 0;
+    BnFwdParams fp = make_bn_fwd_params(stats, count, gamma, beta, eps, momentum, running_mean, running_var, nbt, C, coef, clear_sums);
+    fp.keep_stats = 1;
+    return launch_bn_finalize("segnb_bn_finalize_keep", fp, Cp, stream);
 }
 
 static int launch_bn_act_fwd(int dtype, const void* y, int ld_y, int N, int H, int W, int Cp, const float* coef,
@@ -1561,7 +1366,7 @@ extern "C" int segnb_bn_act_fwd(int dtype, const void* y, int ld_y, int N, int H
                                 int ld_out, void* pool_out, int ld_pool, void* up_out, int ld_up, const void* res,
                                 int ld_res, segnb_stream_t stream) {
     SEGNB_PLAN_RECORD(segnb_bn_act_fwd, dtype, y, ld_y, N, H, W, Cp, coef, act, slope, dropmul, out, ld_out, pool_out, ld_pool, up_out, ld_up, res, ld_res, stream);
-    BnFwdParams fp = {};
+    const BnFwdParams fp;
     return launch_bn_act_fwd(dtype, y, ld_y, N, H, W, Cp, coef, act, slope, dropmul, out, ld_out, pool_out, ld_pool,
                              up_out, ld_up, res, ld_res, fp, "segnb_bn_act_fwd", stream);
 }
@@ -1574,8 +1379,8 @@ extern "C" int segnb_bn_fwd_fused(int dtype, const void* y, int ld_y, int N, int
                                   const void* res, int ld_res, segnb_stream_t stream) {
     SEGNB_PLAN_RECORD(segnb_bn_fwd_fused, dtype, y, ld_y, N, H, W, C, Cp, stats, gamma, beta, eps, momentum, running_mean, running_var, nbt, coef, bwd_sums_to_clear, act, slope, dropmul, out, ld_out, pool_out, ld_pool, up_out, ld_up, res, ld_res, stream);
     SEGNB_CHECK_ARG(stats != nullptr && coef != nullptr && C > 0 && Cp >= C, "missing statistics / coefficient buffer");
-    BnFwdParams fp = {stats, (double)N * H * W, gamma, beta, eps, momentum, running_mean, running_var, nbt, C, 1, coef,
-                      bwd_sums_to_clear};
+    const BnFwdParams fp = make_bn_fwd_params(stats, (double)N * H * W, gamma, beta, eps, momentum, running_mean, running_var, nbt,
+                                              C, coef, bwd_sums_to_clear);
     return launch_bn_act_fwd(dtype, y, ld_y, N, H, W, Cp, nullptr, act, slope, dropmul, out, ld_out, pool_out, ld_pool,
                              up_out, ld_up, res, ld_res, fp, "segnb_bn_fwd_fused", stream);
 }
@@ -1589,7 +1394,7 @@ extern "C" int segnb_bn_act_fwd_stats(int dtype, const void* y, int ld_y, int N,
                                       int out_stats_ld, segnb_stream_t stream) {
     SEGNB_PLAN_RECORD(segnb_bn_act_fwd_stats, dtype, y, ld_y, N, H, W, Cp, coef, act, slope, dropmul, out, ld_out, out_stats, out_stats_ld, stream);
     SEGNB_CHECK_ARG(out != nullptr && out_stats != nullptr, "NULL tensor");
-    BnFwdParams fp = {};
+    const BnFwdParams fp;
     const OutStats so = {out_stats, out_stats_ld};
     return launch_bn_act_fwd(dtype, y, ld_y, N, H, W, Cp, coef, act, slope, dropmul, out, ld_out, nullptr, 0, nullptr, 0,
                              nullptr, 0, fp, "segnb_bn_act_fwd_stats", stream, nullptr, &so);
@@ -1603,8 +1408,9 @@ extern "C" int segnb_bn_fwd_fused_ld(int dtype, const void* y, int ld_y, int N, 
     SEGNB_PLAN_RECORD(segnb_bn_fwd_fused_ld, dtype, y, ld_y, N, H, W, C, Cp, stats, stats_ld, gamma, beta, eps, momentum, running_mean, running_var, nbt, coef, bwd_sums_to_clear, act, slope, dropmul, out, ld_out, stream);
     SEGNB_CHECK_ARG(stats != nullptr && coef != nullptr && out != nullptr && C > 0 && Cp >= C && stats_ld >= Cp,
                     "missing statistics / coefficient buffer, or a statistics stride below Cp");
-    BnFwdParams fp = {stats, (double)N * H * W, gamma, beta, eps, momentum, running_mean, running_var, nbt, C, 1, coef,
-                      bwd_sums_to_clear, 0, stats_ld};
+    BnFwdParams fp = make_bn_fwd_params(stats, (double)N * H * W, gamma, beta, eps, momentum, running_mean, running_var, nbt, C,
+                                        coef, bwd_sums_to_clear);
+    fp.stats_ld = stats_ld;
     return launch_bn_act_fwd(dtype, y, ld_y, N, H, W, Cp, nullptr, act, slope, dropmul, out, ld_out, nullptr, 0, nullptr, 0,
                              nullptr, 0, fp, "segnb_bn_fwd_fused_ld", stream);
 }
@@ -1624,8 +1430,8 @@ extern "C" int segnb_bn_fwd_fused_head(int dtype, const void* y, int ld_y, int N
     SEGNB_PLAN_RECORD(segnb_bn_fwd_fused_head, dtype, y, ld_y, N, H, W, C, Cp, stats, gamma, beta, eps, momentum, running_mean, running_var, nbt, coef, bwd_sums_to_clear, act, slope, dropmul, out, ld_out, head_w, head_b, K, logits, stream);
     SEGNB_CHECK_ARG(stats != nullptr && coef != nullptr && C > 0 && Cp >= C, "missing statistics / coefficient buffer");
     SEGNB_CHECK_ARG(segnb_head_fused_ok(K, Cp), "classifier variant: 1..4 classes, Cp / 8 a power of two <= 32 (segnb_head_fused_ok)");
-    BnFwdParams fp = {stats, (double)N * H * W, gamma, beta, eps, momentum, running_mean, running_var, nbt, C, 1, coef,
-                      bwd_sums_to_clear};
+    const BnFwdParams fp = make_bn_fwd_params(stats, (double)N * H * W, gamma, beta, eps, momentum, running_mean, running_var, nbt,
+                                              C, coef, bwd_sums_to_clear);
     const HeadFwd hd = {head_w, head_b, logits, K, C};
     return launch_bn_act_fwd(dtype, y, ld_y, N, H, W, Cp, nullptr, act, slope, dropmul, out, ld_out, nullptr, 0, nullptr, 0,
                              nullptr, 0, fp, "segnb_bn_fwd_fused_head", stream, &hd);
@@ -1638,71 +1444,47 @@ static int launch_bn_act_fwd(int dtype, const void* y, int ld_y, int N, int H, i
     if (int rc = check_ew(N, H, W, Cp)) return rc;
     SEGNB_CHECK_ARG(y != nullptr && (out || pool_out || up_out || hd), "NULL tensor");
     const EwShape s = make_shape(N, H, W, Cp);
+    const hipStream_t st = (hipStream_t)stream;
+    int rc;
     if (so != nullptr) {
         // the variant that also accumulates the statistics of what it writes
         SEGNB_CHECK_ARG(hd == nullptr && pool_out == nullptr && res == nullptr && so->p != nullptr && so->ld >= Cp,
                         "output statistics: no pooling / residual / classifier, statistics stride >= Cp");
-        const dim3 grid = make_grid(s, (long long)N * H * W, 2048);
-#define SEGNB_FWDS(TT)                                                                                              \
-    hipLaunchKernelGGL((bn_act_fwd_kernel<TT, false, false, 0, true>), grid, dim3(NTHR), 0, (hipStream_t)stream, (const TT*)y, \
-                       ld_y, s, coef, act, slope, dropmul, (TT*)out, ld_out, (TT*)nullptr, 0, (TT*)up_out, ld_up,    \
-                       (const TT*)nullptr, 0, fp, HeadFwd{}, *so)
-        if (dtype == SEGNB_BF16) {
-            SEGNB_FWDS(bf16_t);
-        } else if (dtype == SEGNB_F32) {
-            SEGNB_FWDS(float);
-        } else {
-            segnb_set_error("%s: unknown dtype %d", who, dtype);
-            return SEGNB_E_BADARG;
-        }
-#undef SEGNB_FWDS
-        SEGNB_LAUNCH_CHECK();
-        return 0;
-    }
-    if (hd != nullptr) {
+        const dim3 grid = make_grid(s, walk_items(N, H, W, false), 2048);
+        rc = segnb_dispatch_dtype(dtype, who, [&](auto tag) SEGNB_INLINE_LAMBDA {
+            using T = SEGNB_TAG_T(tag);
+            hipLaunchKernelGGL((bn_act_fwd_kernel<T, false, false, 0, true>), grid, dim3(NTHR), 0, st, (const T*)y, ld_y, s, coef,
+                               act, slope, dropmul, (T*)out, ld_out, (T*)nullptr, 0, (T*)up_out, ld_up, (const T*)nullptr, 0, fp,
+                               HeadFwd{}, *so);
+        });
+    } else if (hd != nullptr) {
         // the classifier variant: a pixel's channel chunks are CT consecutive lanes of one wave (one block column)
         SEGNB_CHECK_ARG(pool_out == nullptr && res == nullptr && s.CT == s.CPP && hd->K >= 1 && hd->K <= 4 && hd->w && hd->logits,
                         "classifier variant: no pooling / residual, Cp / 8 a power of two <= 32, 1..4 classes (segnb_head_fused_ok)");
-        const dim3 grid = make_grid(s, (long long)N * H * W, 4096);
-#define SEGNB_FWDH(TT, HKK)                                                                                         \
-    hipLaunchKernelGGL((bn_act_fwd_kernel<TT, false, false, HKK>), grid, dim3(NTHR), 0, (hipStream_t)stream, (const TT*)y, \
-                       ld_y, s, coef, act, slope, dropmul, (TT*)out, ld_out, (TT*)nullptr, 0, (TT*)up_out, ld_up,    \
-                       (const TT*)nullptr, 0, fp, *hd)
-        if (dtype == SEGNB_BF16) {
-            if (hd->K == 1) SEGNB_FWDH(bf16_t, 1); else SEGNB_FWDH(bf16_t, 4);
-        } else if (dtype == SEGNB_F32) {
-            if (hd->K == 1) SEGNB_FWDH(float, 1); else SEGNB_FWDH(float, 4);
-        } else {
-            segnb_set_error("%s: unknown dtype %d", who, dtype);
-            return SEGNB_E_BADARG;
-        }
-#undef SEGNB_FWDH
-        SEGNB_LAUNCH_CHECK();
-        return 0;
-    }
-    // pooling: one item per pixel column of a row pair, over an even padded width
-    const long long items = pool_out != nullptr ? (long long)N * ((H + 1) / 2) * (2 * ((W + 1) / 2)) : (long long)N * H * W;
-    const dim3 grid = make_grid(s, items, pool_out != nullptr ? 2048 : 4096);
-#define SEGNB_FWD(TT, P, R)                                                                                         \
-    hipLaunchKernelGGL((bn_act_fwd_kernel<TT, P, R>), grid, dim3(NTHR), 0, (hipStream_t)stream, (const TT*)y, ld_y, s, \
-                       coef, act, slope, dropmul, (TT*)out, ld_out, (TT*)pool_out, ld_pool, (TT*)up_out, ld_up,     \
-                       (const TT*)res, ld_res, fp)
-#define SEGNB_FWD_ALL(TT)                                            \
-    if (pool_out != nullptr) {                                       \
-        if (res != nullptr) SEGNB_FWD(TT, true, true); else SEGNB_FWD(TT, true, false);      \
-    } else {                                                         \
-        if (res != nullptr) SEGNB_FWD(TT, false, true); else SEGNB_FWD(TT, false, false);    \
-    }
-    if (dtype == SEGNB_BF16) {
-        SEGNB_FWD_ALL(bf16_t)
-    } else if (dtype == SEGNB_F32) {
-        SEGNB_FWD_ALL(float)
+        const dim3 grid = make_grid(s, walk_items(N, H, W, false), 4096);
+        rc = segnb_dispatch_dtype(dtype, who, [&](auto tag) SEGNB_INLINE_LAMBDA {
+            using T = SEGNB_TAG_T(tag);
+            segnb_dispatch_le<1, 4>(hd->K, [&](auto HK) SEGNB_INLINE_LAMBDA {
+                hipLaunchKernelGGL((bn_act_fwd_kernel<T, false, false, decltype(HK)::value>), grid, dim3(NTHR), 0, st, (const T*)y,
+                                   ld_y, s, coef, act, slope, dropmul, (T*)out, ld_out, (T*)nullptr, 0, (T*)up_out, ld_up,
+                                   (const T*)nullptr, 0, fp, *hd);
+            });
+        });
     } else {
-        segnb_set_error("%s: unknown dtype %d", who, dtype);
-        return SEGNB_E_BADARG;
+        // pooling: one item per pixel column of a row pair, over an even padded width
+        const dim3 grid = make_grid(s, walk_items(N, H, W, pool_out != nullptr), pool_out != nullptr ? 2048 : 4096);
+        rc = segnb_dispatch_dtype(dtype, who, [&](auto tag) SEGNB_INLINE_LAMBDA {
+            using T = SEGNB_TAG_T(tag);
+            segnb_dispatch_bool(pool_out != nullptr, [&](auto P) SEGNB_INLINE_LAMBDA {
+                segnb_dispatch_bool(res != nullptr, [&](auto R) SEGNB_INLINE_LAMBDA {
+                    hipLaunchKernelGGL((bn_act_fwd_kernel<T, decltype(P)::value, decltype(R)::value>), grid, dim3(NTHR), 0, st,
+                                       (const T*)y, ld_y, s, coef, act, slope, dropmul, (T*)out, ld_out, (T*)pool_out, ld_pool,
+                                       (T*)up_out, ld_up, (const T*)res, ld_res, fp);
+                });
+            });
+        });
     }
-#undef SEGNB_FWD_ALL
-#undef SEGNB_FWD
+    if (rc) return rc;
     SEGNB_LAUNCH_CHECK();
     return 0;
 }
@@ -1720,37 +1502,26 @@ extern "C" int segnb_bn_act_bwd_reduce(int dtype, const void* y, int ld_y, int N
                     "segnb_bn_bwd_apply_direct / segnb_bn_bwd_apply_fused_src)");
     SEGNB_CHECK_ARG(!(res && g_pool), "residual input and pooled gradient cannot be combined");
     const EwShape s = make_shape(N, H, W, Cp);
-    const bool hd = g_direct != nullptr, hp = g_pool != nullptr, hu = g_up != nullptr;
-    const long long items = hp ? (long long)N * ((H + 1) / 2) * (2 * ((W + 1) / 2)) : (long long)N * H * W;
-    const dim3 grid = make_grid(s, items);
-    const int variant = (hd ? 1 : 0) | (hp ? 2 : 0) | (hu ? 4 : 0);
-#define SEGNB_RED(TT, D, P, U, R)                                                                                   \
-    SEGNB_LAUNCH_FORKABLE((bn_act_bwd_reduce_kernel<TT, D, P, U, false, R>), grid, dim3(NTHR), 0, (hipStream_t)stream, \
-                       (const TT*)y, ld_y, s, coef, act, slope, dropmul, (const TT*)g_direct, ld_gd,              \
-                       (const TT*)g_pool, ld_gp, (const TT*)g_up, ld_gu, (TT*)dz, ld_dz, sums, (const TT*)res, ld_res, BnBwdParams{})
-#define SEGNB_RED_R(TT, D, U)                                                                                       \
-    if (res != nullptr) SEGNB_RED(TT, D, false, U, true); else SEGNB_RED(TT, D, false, U, false)
-#define SEGNB_RED_ALL(TT)                                                       \
-    switch (variant) {                                                          \
-        case 1: SEGNB_RED_R(TT, true, false); break;                            \
-        case 2: SEGNB_RED(TT, false, true, false, false); break;                \
-        case 3: SEGNB_RED(TT, true, true, false, false); break;                 \
-        case 4: SEGNB_RED_R(TT, false, true); break;                            \
-        case 5: SEGNB_RED_R(TT, true, true); break;                             \
-        case 6: SEGNB_RED(TT, false, true, true, false); break;                 \
-        default: SEGNB_RED(TT, true, true, true, false); break;                 \
-    }
-    if (dtype == SEGNB_BF16) {
-        SEGNB_RED_ALL(bf16_t)
-    } else if (dtype == SEGNB_F32) {
-        SEGNB_RED_ALL(float)
-    } else {
-        segnb_set_error("segnb_bn_act_bwd_reduce: unknown dtype %d", dtype);
-        return SEGNB_E_BADARG;
-    }
-#undef SEGNB_RED_ALL
-#undef SEGNB_RED_R
-#undef SEGNB_RED
+    const dim3 grid = make_grid(s, walk_items(N, H, W, g_pool != nullptr));
+    const hipStream_t st = (hipStream_t)stream;
+    if (int rc = segnb_dispatch_dtype(dtype, "segnb_bn_act_bwd_reduce", [&](auto tag) SEGNB_INLINE_LAMBDA {
+            using T = SEGNB_TAG_T(tag);
+            dispatch_sources(g_direct, g_pool, g_up, [&](auto D, auto P, auto U) SEGNB_INLINE_LAMBDA {
+                const auto launch = [&](auto R) SEGNB_INLINE_LAMBDA {
+                    SEGNB_LAUNCH_FORKABLE((bn_act_bwd_reduce_kernel<T, decltype(D)::value, decltype(P)::value, decltype(U)::value,
+                                                                    false, decltype(R)::value>),
+                                          grid, dim3(NTHR), 0, st, (const T*)y, ld_y, s, coef, act, slope, dropmul,
+                                          (const T*)g_direct, ld_gd, (const T*)g_pool, ld_gp, (const T*)g_up, ld_gu, (T*)dz, ld_dz,
+                                          sums, (const T*)res, ld_res, BnBwdParams{});
+                };
+                // (the pooled forms have no residual arm: the combination is refused above)
+                if constexpr (decltype(P)::value)
+                    launch(std::false_type{});
+                else
+                    segnb_dispatch_bool(res != nullptr, launch);
+            });
+        }))
+        return rc;
     SEGNB_LAUNCH_CHECK();
     return 0;
 }
@@ -1764,20 +1535,18 @@ extern "C" int segnb_bn_act_bwd_reduce_add(int dtype, const void* y, int ld_y, i
     SEGNB_CHECK_ARG(y != nullptr && g_direct != nullptr && g_add != nullptr, "NULL tensor");
     SEGNB_CHECK_ARG(dz != nullptr || sums != nullptr, "a pass without dz needs the sums");
     const EwShape s = make_shape(N, H, W, Cp);
-    const dim3 grid = make_grid(s, (long long)N * H * W);
-#define SEGNB_RED_A(TT, R)                                                                                                     \
-    SEGNB_LAUNCH_FORKABLE((bn_act_bwd_reduce_kernel<TT, true, false, false, false, R, true>), grid, dim3(NTHR), 0, (hipStream_t)stream, \
-                          (const TT*)y, ld_y, s, coef, act, slope, dropmul, (const TT*)g_direct, ld_gd, (const TT*)nullptr, 0,    \
-                          (const TT*)g_add, ld_ga, (TT*)dz, ld_dz, sums, (const TT*)res, ld_res, BnBwdParams{})
-    if (dtype == SEGNB_BF16) {
-        if (res != nullptr) SEGNB_RED_A(bf16_t, true); else SEGNB_RED_A(bf16_t, false);
-    } else if (dtype == SEGNB_F32) {
-        if (res != nullptr) SEGNB_RED_A(float, true); else SEGNB_RED_A(float, false);
-    } else {
-        segnb_set_error("segnb_bn_act_bwd_reduce_add: unknown dtype %d", dtype);
-        return SEGNB_E_BADARG;
-    }
-#undef SEGNB_RED_A
+    const dim3 grid = make_grid(s, walk_items(N, H, W, false));
+    const hipStream_t st = (hipStream_t)stream;
+    if (int rc = segnb_dispatch_dtype(dtype, "segnb_bn_act_bwd_reduce_add", [&](auto tag) SEGNB_INLINE_LAMBDA {
+            using T = SEGNB_TAG_T(tag);
+            segnb_dispatch_bool(res != nullptr, [&](auto R) SEGNB_INLINE_LAMBDA {
+                SEGNB_LAUNCH_FORKABLE((bn_act_bwd_reduce_kernel<T, true, false, false, false, decltype(R)::value, true>), grid,
+                                      dim3(NTHR), 0, st, (const T*)y, ld_y, s, coef, act, slope, dropmul, (const T*)g_direct, ld_gd,
+                                      (const T*)nullptr, 0, (const T*)g_add, ld_ga, (T*)dz, ld_dz, sums, (const T*)res, ld_res,
+                                      BnBwdParams{});
+            });
+        }))
+        return rc;
     SEGNB_LAUNCH_CHECK();
     return 0;
 }
@@ -1790,24 +1559,21 @@ extern "C" int segnb_head_bn_bwd(int dtype, const void* y, int ld_y, int N, int 
     SEGNB_CHECK_ARG(y && coef && head_w && dlogits && sums && C > 0 && Cp >= C, "NULL tensor");      // (dz NULL: sums only)
     SEGNB_CHECK_ARG(segnb_head_fused_ok(K, Cp), "1..4 classes, Cp / 8 a power of two <= 32 (segnb_head_fused_ok)");
     const EwShape s = make_shape(N, H, W, Cp);
-    const dim3 grid = make_grid(s, (long long)N * H * W);
-    float* part = segnb_head_scratch((size_t)grid.x * grid.y * K * (s.CT * 8 + 1) * sizeof(float), (hipStream_t)stream);
+    const dim3 grid = make_grid(s, walk_items(N, H, W, false));
+    const hipStream_t st = (hipStream_t)stream;
+    float* part = segnb_head_scratch((size_t)grid.x * grid.y * K * (s.CT * 8 + 1) * sizeof(float), st);
     if (part == nullptr) return SEGNB_E_BADARG;
-#define SEGNB_HBB(TT, KMM)                                                                                          \
-    hipLaunchKernelGGL((head_bn_bwd_kernel<TT, KMM>), grid, dim3(NTHR), 0, (hipStream_t)stream, (const TT*)y, ld_y, s, coef, \
-                       act, slope, dropmul, head_w, C, K, dlogits, (TT*)dz, ld_dz, sums, part)
-    if (dtype == SEGNB_BF16) {
-        if (K == 1) SEGNB_HBB(bf16_t, 1); else SEGNB_HBB(bf16_t, 4);
-    } else if (dtype == SEGNB_F32) {
-        if (K == 1) SEGNB_HBB(float, 1); else SEGNB_HBB(float, 4);
-    } else {
-        segnb_set_error("segnb_head_bn_bwd: unknown dtype %d", dtype);
-        return SEGNB_E_BADARG;
-    }
-#undef SEGNB_HBB
+    if (int rc = segnb_dispatch_dtype(dtype, "segnb_head_bn_bwd", [&](auto tag) SEGNB_INLINE_LAMBDA {
+            using T = SEGNB_TAG_T(tag);
+            segnb_dispatch_le<1, 4>(K, [&](auto KM) SEGNB_INLINE_LAMBDA {
+                hipLaunchKernelGGL((head_bn_bwd_kernel<T, decltype(KM)::value>), grid, dim3(NTHR), 0, st, (const T*)y, ld_y, s, coef,
+                                   act, slope, dropmul, head_w, C, K, dlogits, (T*)dz, ld_dz, sums, part);
+            });
+        }))
+        return rc;
     SEGNB_LAUNCH_CHECK();
     if (dw != nullptr || db != nullptr) {
-        segnb_head_bwd_finish(part, (int)grid.x, (int)grid.y, K, C, s.CT, dw, db, (hipStream_t)stream);
+        segnb_head_bwd_finish(part, (int)grid.x, (int)grid.y, K, C, s.CT, dw, db, st);
         SEGNB_LAUNCH_CHECK();
     }
     return 0;
@@ -1825,20 +1591,17 @@ extern "C" int segnb_head_bn_bwd_apply(int dtype, const void* y, int ld_y, int N
     SEGNB_CHECK_ARG(segnb_head_fused_ok(K, Cp), "1..4 classes, Cp / 8 a power of two <= 32 (segnb_head_fused_ok)");
     SEGNB_CHECK_ARG(ld_y % 8 == 0 && ld_dy % 8 == 0 && ld_y >= Cp && ld_dy >= Cp, "bad strides");
     const EwShape s = make_shape(N, H, W, Cp);
-    const dim3 grid = make_grid(s, (long long)N * H * W);
-    const BnBwdParams bp = {sums, (double)N * H * W, gamma, dgamma, dbeta, C, accumulate, bcoef, fwd_stats_to_clear};
-#define SEGNB_HBA(TT, KMM)                                                                                                    \
-    SEGNB_LAUNCH_FORKABLE((head_bn_apply_kernel<TT, KMM>), grid, dim3(NTHR), 0, (hipStream_t)stream, (const TT*)y, ld_y, s, coef, \
-                          act, slope, dropmul, head_w, C, K, dlogits, (TT*)dy, ld_dy, bp)
-    if (dtype == SEGNB_BF16) {
-        if (K == 1) SEGNB_HBA(bf16_t, 1); else SEGNB_HBA(bf16_t, 4);
-    } else if (dtype == SEGNB_F32) {
-        if (K == 1) SEGNB_HBA(float, 1); else SEGNB_HBA(float, 4);
-    } else {
-        segnb_set_error("segnb_head_bn_bwd_apply: unknown dtype %d", dtype);
-        return SEGNB_E_BADARG;
-    }
-#undef SEGNB_HBA
+    const dim3 grid = make_grid(s, walk_items(N, H, W, false));
+    const hipStream_t st = (hipStream_t)stream;
+    const BnBwdParams bp = make_bn_bwd_params(sums, (double)N * H * W, gamma, dgamma, dbeta, C, accumulate, bcoef, fwd_stats_to_clear);
+    if (int rc = segnb_dispatch_dtype(dtype, "segnb_head_bn_bwd_apply", [&](auto tag) SEGNB_INLINE_LAMBDA {
+            using T = SEGNB_TAG_T(tag);
+            segnb_dispatch_le<1, 4>(K, [&](auto KM) SEGNB_INLINE_LAMBDA {
+                SEGNB_LAUNCH_FORKABLE((head_bn_apply_kernel<T, decltype(KM)::value>), grid, dim3(NTHR), 0, st, (const T*)y, ld_y, s,
+                                      coef, act, slope, dropmul, head_w, C, K, dlogits, (T*)dy, ld_dy, bp);
+            });
+        }))
+        return rc;
     SEGNB_LAUNCH_CHECK();
     return 0;
 }
@@ -1885,10 +1648,8 @@ extern "C" int segnb_bn_bwd_finalize(double* sums, int C, int Cp, double count, 
                                      int accumulate, segnb_stream_t stream) {
     SEGNB_PLAN_RECORD(segnb_bn_bwd_finalize, sums, C, Cp, count, gamma, coef, bcoef, dgamma, dbeta, accumulate, stream);
     SEGNB_CHECK_ARG(sums && coef && bcoef && C > 0 && Cp >= C && Cp % 8 == 0, "bad arguments");
-    BnBwdParams bp = {sums, count, gamma, dgamma, dbeta, C, accumulate, bcoef, nullptr};
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(ceil_div(Cp, 64)), dim3(64), 0, (hipStream_t)stream, bp, coef, Cp);
-    SEGNB_LAUNCH_CHECK();
-    return 0;
+    const BnBwdParams bp = make_bn_bwd_params(sums, count, gamma, dgamma, dbeta, C, accumulate, bcoef, nullptr);
+    return launch_bn_bwd_finalize("segnb_bn_bwd_finalize", bp, coef, Cp, stream);
 }
 
 // the same, and the layer's FORWARD statistics buffer cleared (what the fused apply launches do on the way): for a layer
@@ -1898,12 +1659,11 @@ extern "C" int segnb_bn_bwd_finalize_clear(double* sums, int C, int Cp, double c
                                            int accumulate, double* fwd_stats_to_clear, segnb_stream_t stream) {
     SEGNB_PLAN_RECORD(segnb_bn_bwd_finalize_clear, sums, C, Cp, count, gamma, coef, bcoef, dgamma, dbeta, accumulate, fwd_stats_to_clear, stream);
     SEGNB_CHECK_ARG(sums && coef && bcoef && C > 0 && Cp >= C && Cp % 8 == 0, "bad arguments");
-    BnBwdParams bp = {sums, count, gamma, dgamma, dbeta, C, accumulate, bcoef, fwd_stats_to_clear};
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(ceil_div(Cp, 64)), dim3(64), 0, (hipStream_t)stream, bp, coef, Cp);
-    SEGNB_LAUNCH_CHECK();
-    return 0;
+    const BnBwdParams bp = make_bn_bwd_params(sums, count, gamma, dgamma, dbeta, C, accumulate, bcoef, fwd_stats_to_clear);
+    return launch_bn_bwd_finalize("segnb_bn_bwd_finalize_clear", bp, coef, Cp, stream);
 }
 
+// acc: dy += result (bn_bwd_apply_kernel's ACC form)
 static int launch_bn_bwd_apply(int dtype, const void* y, int ld_y, int N, int H, int W, int Cp, const float* coef,
                                const float* bcoef, const void* dz, int ld_dz, void* dy, int ld_dy, float* dbias, int C,
                                const BnBwdParams& bp, const char* who, segnb_stream_t stream, const void* g = nullptr,
@@ -1911,27 +1671,16 @@ static int launch_bn_bwd_apply(int dtype, const void* y, int ld_y, int N, int H,
     if (int rc = check_ew(N, H, W, Cp)) return rc;
     SEGNB_CHECK_ARG(y && coef && (bcoef || bp.bcoef) && (dz || g) && dy, "NULL tensor");
     const EwShape s = make_shape(N, H, W, Cp);
-    const dim3 grid = make_grid(s, (long long)N * H * W, 1536);
-    if (acc && dtype == SEGNB_BF16)
-        SEGNB_LAUNCH_FORKABLE((bn_bwd_apply_kernel<bf16_t, true>), grid, dim3(NTHR), 0, (hipStream_t)stream, (const bf16_t*)y,
-                           ld_y, s, coef, bcoef, (const bf16_t*)dz, ld_dz, (bf16_t*)dy, ld_dy, dbias, C, bp,
-                           (const bf16_t*)g, ld_g, act, slope);
-    else if (acc && dtype == SEGNB_F32)
-        SEGNB_LAUNCH_FORKABLE((bn_bwd_apply_kernel<float, true>), grid, dim3(NTHR), 0, (hipStream_t)stream, (const float*)y,
-                           ld_y, s, coef, bcoef, (const float*)dz, ld_dz, (float*)dy, ld_dy, dbias, C, bp,
-                           (const float*)g, ld_g, act, slope);
-    else if (dtype == SEGNB_BF16)
-        SEGNB_LAUNCH_FORKABLE(bn_bwd_apply_kernel<bf16_t>, grid, dim3(NTHR), 0, (hipStream_t)stream, (const bf16_t*)y,
-                           ld_y, s, coef, bcoef, (const bf16_t*)dz, ld_dz, (bf16_t*)dy, ld_dy, dbias, C, bp,
-                           (const bf16_t*)g, ld_g, act, slope);
-    else if (dtype == SEGNB_F32)
-        SEGNB_LAUNCH_FORKABLE(bn_bwd_apply_kernel<float>, grid, dim3(NTHR), 0, (hipStream_t)stream, (const float*)y,
-                           ld_y, s, coef, bcoef, (const float*)dz, ld_dz, (float*)dy, ld_dy, dbias, C, bp,
-                           (const float*)g, ld_g, act, slope);
-    else {
-        segnb_set_error("%s: unknown dtype %d", who, dtype);
-        return SEGNB_E_BADARG;
-    }
+    const dim3 grid = make_grid(s, walk_items(N, H, W, false), 1536);
+    const hipStream_t st = (hipStream_t)stream;
+    if (int rc = segnb_dispatch_dtype(dtype, who, [&](auto tag) SEGNB_INLINE_LAMBDA {
+            using T = SEGNB_TAG_T(tag);
+            segnb_dispatch_bool(acc, [&](auto ACC) SEGNB_INLINE_LAMBDA {
+                SEGNB_LAUNCH_FORKABLE((bn_bwd_apply_kernel<T, decltype(ACC)::value>), grid, dim3(NTHR), 0, st, (const T*)y, ld_y, s,
+                                      coef, bcoef, (const T*)dz, ld_dz, (T*)dy, ld_dy, dbias, C, bp, (const T*)g, ld_g, act, slope);
+            });
+        }))
+        return rc;
     SEGNB_LAUNCH_CHECK();
     return 0;
 }
@@ -1940,7 +1689,7 @@ extern "C" int segnb_bn_bwd_apply(int dtype, const void* y, int ld_y, int N, int
                                   const float* coef, const float* bcoef, const void* dz, int ld_dz, void* dy,
                                   int ld_dy, float* dbias, int C, segnb_stream_t stream) {
     SEGNB_PLAN_RECORD(segnb_bn_bwd_apply, dtype, y, ld_y, N, H, W, Cp, coef, bcoef, dz, ld_dz, dy, ld_dy, dbias, C, stream);
-    BnBwdParams bp = {};
+    const BnBwdParams bp;
     return launch_bn_bwd_apply(dtype, y, ld_y, N, H, W, Cp, coef, bcoef, dz, ld_dz, dy, ld_dy, dbias, C, bp,
                                "segnb_bn_bwd_apply", stream);
 }
@@ -1950,7 +1699,7 @@ extern "C" int segnb_bn_bwd_apply_direct(int dtype, const void* y, int ld_y, int
                                          int ld_g, void* dy, int ld_dy, float* dbias, int C, segnb_stream_t stream) {
     SEGNB_PLAN_RECORD(segnb_bn_bwd_apply_direct, dtype, y, ld_y, N, H, W, Cp, coef, bcoef, act, slope, g, ld_g, dy, ld_dy, dbias, C, stream);
     SEGNB_CHECK_ARG(g != nullptr, "NULL gradient");
-    BnBwdParams bp = {};
+    const BnBwdParams bp;
     return launch_bn_bwd_apply(dtype, y, ld_y, N, H, W, Cp, coef, bcoef, nullptr, 0, dy, ld_dy, dbias, C, bp,
                                "segnb_bn_bwd_apply_direct", stream, g, ld_g, act, slope);
 }
@@ -1960,8 +1709,8 @@ extern "C" int segnb_bn_bwd_apply_fused(int dtype, const void* y, int ld_y, int 
                                         float* dgamma, float* dbeta, int accumulate, double* fwd_stats_to_clear,
                                         const void* dz, int ld_dz, void* dy, int ld_dy, segnb_stream_t stream) {
     SEGNB_PLAN_RECORD(segnb_bn_bwd_apply_fused, dtype, y, ld_y, N, H, W, C, Cp, coef, sums, gamma, bcoef, dgamma, dbeta, accumulate, fwd_stats_to_clear, dz, ld_dz, dy, ld_dy, stream);
-    SEGNB_CHECK_ARG(sums != nullptr && bcoef != nullptr && C > 0 && Cp >= C, "missing sums / coefficient buffer");
-    BnBwdParams bp = {sums, (double)N * H * W, gamma, dgamma, dbeta, C, accumulate, bcoef, fwd_stats_to_clear};
+    if (int rc = check_bn_bwd_params("segnb_bn_bwd_apply_fused", sums, bcoef, C, Cp)) return rc;
+    const BnBwdParams bp = make_bn_bwd_params(sums, (double)N * H * W, gamma, dgamma, dbeta, C, accumulate, bcoef, fwd_stats_to_clear);
     return launch_bn_bwd_apply(dtype, y, ld_y, N, H, W, Cp, coef, nullptr, dz, ld_dz, dy, ld_dy, nullptr, C, bp,
                                "segnb_bn_bwd_apply_fused", stream);
 }
@@ -1971,9 +1720,9 @@ extern "C" int segnb_bn_bwd_apply_fused_acc(int dtype, const void* y, int ld_y, 
                                             float* dgamma, float* dbeta, int accumulate, double* fwd_stats_to_clear,
                                             const void* dz, int ld_dz, void* dy, int ld_dy, segnb_stream_t stream) {
     SEGNB_PLAN_RECORD(segnb_bn_bwd_apply_fused_acc, dtype, y, ld_y, N, H, W, C, Cp, coef, sums, gamma, bcoef, dgamma, dbeta, accumulate, fwd_stats_to_clear, dz, ld_dz, dy, ld_dy, stream);
-    SEGNB_CHECK_ARG(sums != nullptr && bcoef != nullptr && C > 0 && Cp >= C, "missing sums / coefficient buffer");
+    if (int rc = check_bn_bwd_params("segnb_bn_bwd_apply_fused_acc", sums, bcoef, C, Cp)) return rc;
     SEGNB_CHECK_ARG(dz != nullptr && dz != dy, "the accumulating form needs dz in a buffer of its own");
-    BnBwdParams bp = {sums, (double)N * H * W, gamma, dgamma, dbeta, C, accumulate, bcoef, fwd_stats_to_clear};
+    const BnBwdParams bp = make_bn_bwd_params(sums, (double)N * H * W, gamma, dgamma, dbeta, C, accumulate, bcoef, fwd_stats_to_clear);
     return launch_bn_bwd_apply(dtype, y, ld_y, N, H, W, Cp, coef, nullptr, dz, ld_dz, dy, ld_dy, nullptr, C, bp,
                                "segnb_bn_bwd_apply_fused_acc", stream, nullptr, 0, 0, 0.f, true);
 }
@@ -1987,9 +1736,9 @@ extern "C" int segnb_bn_bwd_apply_fused_direct(int dtype, const void* y, int ld_
                                                double* fwd_stats_to_clear, int act, float slope, const void* g,
                                                int ld_g, void* dy, int ld_dy, segnb_stream_t stream) {
     SEGNB_PLAN_RECORD(segnb_bn_bwd_apply_fused_direct, dtype, y, ld_y, N, H, W, C, Cp, coef, sums, gamma, bcoef, dgamma, dbeta, accumulate, fwd_stats_to_clear, act, slope, g, ld_g, dy, ld_dy, stream);
-    SEGNB_CHECK_ARG(sums != nullptr && bcoef != nullptr && C > 0 && Cp >= C, "missing sums / coefficient buffer");
+    if (int rc = check_bn_bwd_params("segnb_bn_bwd_apply_fused_direct", sums, bcoef, C, Cp)) return rc;
     SEGNB_CHECK_ARG(g != nullptr, "NULL gradient");
-    BnBwdParams bp = {sums, (double)N * H * W, gamma, dgamma, dbeta, C, accumulate, bcoef, fwd_stats_to_clear};
+    const BnBwdParams bp = make_bn_bwd_params(sums, (double)N * H * W, gamma, dgamma, dbeta, C, accumulate, bcoef, fwd_stats_to_clear);
     return launch_bn_bwd_apply(dtype, y, ld_y, N, H, W, Cp, coef, nullptr, nullptr, 0, dy, ld_dy, nullptr, C, bp,
                                "segnb_bn_bwd_apply_fused_direct", stream, g, ld_g, act, slope);
 }
@@ -2000,9 +1749,9 @@ extern "C" int segnb_bn_bwd_apply_fused_direct_acc(int dtype, const void* y, int
                                                    double* fwd_stats_to_clear, int act, float slope, const void* g,
                                                    int ld_g, void* dy, int ld_dy, segnb_stream_t stream) {
     SEGNB_PLAN_RECORD(segnb_bn_bwd_apply_fused_direct_acc, dtype, y, ld_y, N, H, W, C, Cp, coef, sums, gamma, bcoef, dgamma, dbeta, accumulate, fwd_stats_to_clear, act, slope, g, ld_g, dy, ld_dy, stream);
-    SEGNB_CHECK_ARG(sums != nullptr && bcoef != nullptr && C > 0 && Cp >= C, "missing sums / coefficient buffer");
+    if (int rc = check_bn_bwd_params("segnb_bn_bwd_apply_fused_direct_acc", sums, bcoef, C, Cp)) return rc;
     SEGNB_CHECK_ARG(g != nullptr && g != dy, "the accumulating form needs the incoming gradient in a buffer of its own");
-    BnBwdParams bp = {sums, (double)N * H * W, gamma, dgamma, dbeta, C, accumulate, bcoef, fwd_stats_to_clear};
+    const BnBwdParams bp = make_bn_bwd_params(sums, (double)N * H * W, gamma, dgamma, dbeta, C, accumulate, bcoef, fwd_stats_to_clear);
     return launch_bn_bwd_apply(dtype, y, ld_y, N, H, W, Cp, coef, nullptr, nullptr, 0, dy, ld_dy, nullptr, C, bp,
                                "segnb_bn_bwd_apply_fused_direct_acc", stream, g, ld_g, act, slope, true);
 }
@@ -2023,35 +1772,19 @@ extern "C" int segnb_bn_bwd_apply_fused_src(int dtype, const void* y, int ld_y, 
     SEGNB_CHECK_ARG(g_direct || g_pool || g_up, "no gradient source");
     SEGNB_CHECK_ARG(dy != g_direct && dy != g_pool && dy != g_up, "dy must not alias a gradient source (windows are re-read)");
     const EwShape s = make_shape(N, H, W, Cp);
-    const bool hd = g_direct != nullptr, hp = g_pool != nullptr, hu = g_up != nullptr;
-    const long long items = hp ? (long long)N * ((H + 1) / 2) * (2 * ((W + 1) / 2)) : (long long)N * H * W;
-    const dim3 grid = make_grid(s, items);
-    const int variant = (hd ? 1 : 0) | (hp ? 2 : 0) | (hu ? 4 : 0);
-    const BnBwdParams bp = {sums, (double)N * H * W, gamma, dgamma, dbeta, C, accumulate, bcoef, fwd_stats_to_clear};
-#define SEGNB_APS(TT, D, P, U)                                                                                      \
-    SEGNB_LAUNCH_FORKABLE((bn_act_bwd_reduce_kernel<TT, D, P, U, true>), grid, dim3(NTHR), 0, (hipStream_t)stream, \
-                       (const TT*)y, ld_y, s, coef, act, slope, dropmul, (const TT*)g_direct, ld_gd,              \
-                       (const TT*)g_pool, ld_gp, (const TT*)g_up, ld_gu, (TT*)dy, ld_dy, nullptr, (const TT*)nullptr, 0, bp)
-#define SEGNB_APS_ALL(TT)                                                       \
-    switch (variant) {                                                          \
-        case 1: SEGNB_APS(TT, true, false, false); break;                       \
-        case 2: SEGNB_APS(TT, false, true, false); break;                       \
-        case 3: SEGNB_APS(TT, true, true, false); break;                        \
-        case 4: SEGNB_APS(TT, false, false, true); break;                       \
-        case 5: SEGNB_APS(TT, true, false, true); break;                        \
-        case 6: SEGNB_APS(TT, false, true, true); break;                        \
-        default: SEGNB_APS(TT, true, true, true); break;                        \
-    }
-    if (dtype == SEGNB_BF16) {
-        SEGNB_APS_ALL(bf16_t)
-    } else if (dtype == SEGNB_F32) {
-        SEGNB_APS_ALL(float)
-    } else {
-        segnb_set_error("segnb_bn_bwd_apply_fused_src: unknown dtype %d", dtype);
-        return SEGNB_E_BADARG;
-    }
-#undef SEGNB_APS_ALL
-#undef SEGNB_APS
+    const dim3 grid = make_grid(s, walk_items(N, H, W, g_pool != nullptr));
+    const hipStream_t st = (hipStream_t)stream;
+    const BnBwdParams bp = make_bn_bwd_params(sums, (double)N * H * W, gamma, dgamma, dbeta, C, accumulate, bcoef, fwd_stats_to_clear);
+    if (int rc = segnb_dispatch_dtype(dtype, "segnb_bn_bwd_apply_fused_src", [&](auto tag) SEGNB_INLINE_LAMBDA {
+            using T = SEGNB_TAG_T(tag);
+            dispatch_sources(g_direct, g_pool, g_up, [&](auto D, auto P, auto U) SEGNB_INLINE_LAMBDA {
+                SEGNB_LAUNCH_FORKABLE((bn_act_bwd_reduce_kernel<T, decltype(D)::value, decltype(P)::value, decltype(U)::value, true>),
+                                      grid, dim3(NTHR), 0, st, (const T*)y, ld_y, s, coef, act, slope, dropmul, (const T*)g_direct,
+                                      ld_gd, (const T*)g_pool, ld_gp, (const T*)g_up, ld_gu, (T*)dy, ld_dy, nullptr,
+                                      (const T*)nullptr, 0, bp);
+            });
+        }))
+        return rc;
     SEGNB_LAUNCH_CHECK();
     return 0;
 }
@@ -2088,110 +1821,17 @@ extern "C" int segnb_abn_dscale(const float* w, float* dscale, float* dw, int n,
     return 0;
 }
 
-// torch.optim.RMSprop (alpha, eps; no momentum / centering / weight decay) and torch.optim.Adam (betas, eps; no
-// amsgrad / weight decay) over the flat buffers: get_optimizer('rms' | 'adam') of torch_train.py:73-77
-__global__ void rmsprop_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ sq, long long n,
-                               float lr, float alpha, float eps) {
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += stride) {
-        const float gi = g[i];
-        const float v = alpha * sq[i] + (1.f - alpha) * gi * gi;
-        sq[i] = v;
-        p[i] -= lr * gi / (sqrtf(v) + eps);
-    }
-}
-
-__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                            float* __restrict__ v, long long n, float step_size, float beta1, float beta2,
-                            float inv_sqrt_bc2, float eps) {
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += stride) {
-        const float gi = g[i];
-        const float mi = beta1 * m[i] + (1.f - beta1) * gi;         // exp_avg.lerp_(grad, 1 - beta1)
-        const float vi = beta2 * v[i] + (1.f - beta2) * gi * gi;
-        m[i] = mi;
-        v[i] = vi;
-        p[i] -= step_size * mi / (sqrtf(vi) * inv_sqrt_bc2 + eps);
-    }
-}
-
-extern "C" int segnb_rmsprop_step(float* p, const float* g, float* square_avg, long long n, float lr, float alpha,
-                                  float eps, segnb_stream_t stream) {
-    SEGNB_PLAN_RECORD(segnb_rmsprop_step, p, g, square_avg, n, lr, alpha, eps, stream);
-    SEGNB_CHECK_ARG(p && g && square_avg && n > 0, "bad arguments");
-    int grid = ceil_div(n, 256);
-    if (grid > 4096) grid = 4096;
-    hipLaunchKernelGGL(rmsprop_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, square_avg, n, lr, alpha, eps);
-    SEGNB_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int segnb_adam_step(float* p, const float* g, float* exp_avg, float* exp_avg_sq, long long n, float lr,
-                               float beta1, float beta2, float eps, int step, segnb_stream_t stream) {
-    SEGNB_PLAN_RECORD(segnb_adam_step, p, g, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, step, stream);
-    SEGNB_CHECK_ARG(p && g && exp_avg && exp_avg_sq && n > 0 && step >= 1, "bad arguments");
-    const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-    int grid = ceil_div(n, 256);
-    if (grid > 4096) grid = 4096;
-    hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, exp_avg, exp_avg_sq, n,
-                       (float)((double)lr / bc1), beta1, beta2, (float)(1.0 / sqrt(bc2)), eps);
-    SEGNB_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int segnb_sgd_step(float* p, const float* g, long long n, float lr, segnb_stream_t stream) {
-    SEGNB_PLAN_RECORD(segnb_sgd_step, p, g, n, lr, stream);
-    SEGNB_CHECK_ARG(p && g && n > 0, "bad arguments");
-    SEGNB_CHECK_ARG((((uintptr_t)p | (uintptr_t)g) & 15) == 0, "buffers must be 16-byte aligned");
-    int grid = ceil_div(n / 4 + 1, 256);
-    if (grid > 2048) grid = 2048;
-    hipLaunchKernelGGL(sgd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, n, lr);
-    SEGNB_LAUNCH_CHECK();
-    return 0;
-}
-
-#define SEGNB_DISPATCH_T(CALL_BF16, CALL_F32, NAME)                 \
-    if (dtype == SEGNB_BF16) {                                      \
-        CALL_BF16;                                                  \
-    } else if (dtype == SEGNB_F32) {                                \
-        CALL_F32;                                                   \
-    } else {                                                        \
-        segnb_set_error(NAME ": unknown dtype %d", dtype);          \
-        return SEGNB_E_BADARG;                                      \
-    }
-
-extern "C" int segnb_add(int dtype, const void* a, int ld_a, const void* b, int ld_b, void* out, int ld_out, int N,
-                         int H, int W, int Cp, segnb_stream_t stream) {
-    SEGNB_PLAN_RECORD(segnb_add, dtype, a, ld_a, b, ld_b, out, ld_out, N, H, W, Cp, stream);
-    if (int rc = check_ew(N, H, W, Cp)) return rc;
-    SEGNB_CHECK_ARG(out, "NULL tensor");
-    const long long npix = (long long)N * H * W;
-    int grid = ceil_div(npix * (Cp / 8), NTHR);
-    if (grid > 4096) grid = 4096;
-    SEGNB_DISPATCH_T(
-        hipLaunchKernelGGL(add_kernel<bf16_t>, dim3(grid), dim3(NTHR), 0, (hipStream_t)stream, (const bf16_t*)a, ld_a,
-                           (const bf16_t*)b, ld_b, (bf16_t*)out, ld_out, npix, Cp / 8),
-        hipLaunchKernelGGL(add_kernel<float>, dim3(grid), dim3(NTHR), 0, (hipStream_t)stream, (const float*)a, ld_a,
-                           (const float*)b, ld_b, (float*)out, ld_out, npix, Cp / 8),
-        "segnb_add")
-    SEGNB_LAUNCH_CHECK();
-    return 0;
-}
-
 static int launch_bn_stats(int dtype, const void* x, int ld, int N, int H, int W, int Cp, double* stats, int stats_ld,
                            const char* who, segnb_stream_t stream) {
     if (int rc = check_ew(N, H, W, Cp)) return rc;
     SEGNB_CHECK_ARG(x && stats && stats_ld >= Cp, "NULL tensor / statistics stride below the channel count");
     const EwShape s = make_shape(N, H, W, Cp);
-    const dim3 grid = make_grid(s, (long long)N * H * W);
-    if (dtype == SEGNB_BF16)
-        hipLaunchKernelGGL(bn_stats_kernel<bf16_t>, grid, dim3(NTHR), 0, (hipStream_t)stream, (const bf16_t*)x, ld, s, stats, stats_ld);
-    else if (dtype == SEGNB_F32)
-        hipLaunchKernelGGL(bn_stats_kernel<float>, grid, dim3(NTHR), 0, (hipStream_t)stream, (const float*)x, ld, s, stats, stats_ld);
-    else {
-        segnb_set_error("%s: unknown dtype %d", who, dtype);
-        return SEGNB_E_BADARG;
-    }
+    const dim3 grid = make_grid(s, walk_items(N, H, W, false));
+    if (int rc = segnb_dispatch_dtype(dtype, who, [&](auto tag) SEGNB_INLINE_LAMBDA {
+            using T = SEGNB_TAG_T(tag);
+            hipLaunchKernelGGL(bn_stats_kernel<T>, grid, dim3(NTHR), 0, (hipStream_t)stream, (const T*)x, ld, s, stats, stats_ld);
+        }))
+        return rc;
     SEGNB_LAUNCH_CHECK();
     return 0;
 }
@@ -2206,213 +1846,4 @@ extern "C" int segnb_bn_stats_ld(int dtype, const void* x, int ld, int N, int H,
                                  segnb_stream_t stream) {
     SEGNB_PLAN_RECORD(segnb_bn_stats_ld, dtype, x, ld, N, H, W, Cp, stats, stats_ld, stream);
     return launch_bn_stats(dtype, x, ld, N, H, W, Cp, stats, stats_ld, "segnb_bn_stats_ld", stream);
-}
-
-// ------------------------------------------------------------------------------------------------
-// nn.Upsample(scale_factor=2, mode='bilinear') of the DecoderBlock's non-deconvolution branch (lib/models/unet16.py:42-46;
-// align_corners=False, torch's default): output row 2i = 0.25 in[i-1] + 0.75 in[i], row 2i+1 = 0.75 in[i] + 0.25 in[i+1] with the
-// neighbour index clamped to the image (columns alike).  fp32 arithmetic in torch's order -- rows of column-interpolated values
-// -- rounded once.  The backward is the exact transpose in gather form: an input pixel collects from the <= 4 x 4 outputs that
-// read it, so no atomics and a fixed summation order.
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void bilin_src(int o, int n, int& i0, int& i1, float& w0, float& w1) {
-    const int i = o >> 1;
-    if (o & 1) { i0 = i; i1 = i + 1 < n ? i + 1 : n - 1; w0 = 0.75f; w1 = 0.25f; }
-    else       { i0 = i > 0 ? i - 1 : 0; i1 = i; w0 = 0.25f; w1 = 0.75f; }
-}
-template <typename T>
-__global__ __launch_bounds__(NTHR) void upsample_bilinear2x_fwd_kernel(const T* __restrict__ x, int ld_x, int N, int H, int W, int CPP,
-                                                                       T* __restrict__ out, int ld_out) {
-    const int Ho = 2 * H, Wo = 2 * W;
-    const long long total = (long long)N * Ho * Wo * CPP;
-    for (long long i = blockIdx.x * (long long)NTHR + threadIdx.x; i < total; i += (long long)gridDim.x * NTHR) {
-        const int cc = (int)(i % CPP);
-        long long q = i / CPP;
-        const int ox = (int)(q % Wo);
-        q /= Wo;
-        const int oy = (int)(q % Ho);
-        const int n = (int)(q / Ho);
-        int y0, y1, x0, x1;
-        float wy0, wy1, wx0, wx1;
-        bilin_src(oy, H, y0, y1, wy0, wy1);
-        bilin_src(ox, W, x0, x1, wx0, wx1);
-        float a[8], b[8], c[8], d[8], v[8];
-        const T* base = x + (long long)n * H * W * ld_x + cc * 8;
-        load8(base + ((long long)y0 * W + x0) * ld_x, a);
-        load8(base + ((long long)y0 * W + x1) * ld_x, b);
-        load8(base + ((long long)y1 * W + x0) * ld_x, c);
-        load8(base + ((long long)y1 * W + x1) * ld_x, d);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = wy0 * (wx0 * a[e] + wx1 * b[e]) + wy1 * (wx0 * c[e] + wx1 * d[e]);
-        store8(out + (((long long)n * Ho + oy) * Wo + ox) * ld_out + cc * 8, v);
-    }
-}
-template <typename T>
-__global__ __launch_bounds__(NTHR) void upsample_bilinear2x_bwd_kernel(const T* __restrict__ go, int ld_go, int N, int H, int W, int CPP,
-                                                                       T* __restrict__ dx, int ld_dx) {
-    const int Ho = 2 * H, Wo = 2 * W;
-    const long long total = (long long)N * H * W * CPP;
-    for (long long i = blockIdx.x * (long long)NTHR + threadIdx.x; i < total; i += (long long)gridDim.x * NTHR) {
-        const int cc = (int)(i % CPP);
-        long long q = i / CPP;
-        const int ix = (int)(q % W);
-        q /= W;
-        const int iy = (int)(q % H);
-        const int n = (int)(q / H);
-        float acc[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc[e] = 0.f;
-        for (int oy = 2 * iy - 2; oy <= 2 * iy + 3; ++oy) {
-            if (oy < 0 || oy >= Ho) continue;
-            int y0, y1;
-            float wy0, wy1;
-            bilin_src(oy, H, y0, y1, wy0, wy1);
-            const float wy = (y0 == iy ? wy0 : 0.f) + (y1 == iy ? wy1 : 0.f);
-            if (wy == 0.f) continue;
-            for (int ox = 2 * ix - 2; ox <= 2 * ix + 3; ++ox) {
-                if (ox < 0 || ox >= Wo) continue;
-                int x0, x1;
-                float wx0, wx1;
-                bilin_src(ox, W, x0, x1, wx0, wx1);
-                const float wx = (x0 == ix ? wx0 : 0.f) + (x1 == ix ? wx1 : 0.f);
-                if (wx == 0.f) continue;
-                float g[8];
-                load8(go + (((long long)n * Ho + oy) * Wo + ox) * ld_go + cc * 8, g);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) acc[e] += (wy * wx) * g[e];
-            }
-        }
-        store8(dx + (((long long)n * H + iy) * W + ix) * ld_dx + cc * 8, acc);
-    }
-}
-
-extern "C" int segnb_upsample_bilinear2x_fwd(int dtype, const void* x, int ld_x, int N, int H, int W, int Cp, void* out, int ld_out,
-                                             segnb_stream_t stream) {
-    SEGNB_PLAN_RECORD(segnb_upsample_bilinear2x_fwd, dtype, x, ld_x, N, H, W, Cp, out, ld_out, stream);
-    if (int rc = check_ew(N, 2 * H, 2 * W, Cp)) return rc;
-    SEGNB_CHECK_ARG(x && out && ld_x >= Cp && ld_out >= Cp, "bad arguments");
-    int grid = ceil_div((long long)N * 4 * H * W * (Cp / 8), NTHR);
-    if (grid > 16384) grid = 16384;
-    SEGNB_DISPATCH_T(
-        hipLaunchKernelGGL(upsample_bilinear2x_fwd_kernel<bf16_t>, dim3(grid), dim3(NTHR), 0, (hipStream_t)stream, (const bf16_t*)x,
-                           ld_x, N, H, W, Cp / 8, (bf16_t*)out, ld_out),
-        hipLaunchKernelGGL(upsample_bilinear2x_fwd_kernel<float>, dim3(grid), dim3(NTHR), 0, (hipStream_t)stream, (const float*)x,
-                           ld_x, N, H, W, Cp / 8, (float*)out, ld_out),
-        "segnb_upsample_bilinear2x_fwd")
-    SEGNB_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int segnb_upsample_bilinear2x_bwd(int dtype, const void* g_out, int ld_go, int N, int H, int W, int Cp, void* dx,
-                                             int ld_dx, segnb_stream_t stream) {
-    SEGNB_PLAN_RECORD(segnb_upsample_bilinear2x_bwd, dtype, g_out, ld_go, N, H, W, Cp, dx, ld_dx, stream);
-    if (int rc = check_ew(N, 2 * H, 2 * W, Cp)) return rc;
-    SEGNB_CHECK_ARG(g_out && dx && ld_go >= Cp && ld_dx >= Cp, "bad arguments");
-    int grid = ceil_div((long long)N * H * W * (Cp / 8), NTHR);
-    if (grid > 16384) grid = 16384;
-    SEGNB_DISPATCH_T(
-        hipLaunchKernelGGL(upsample_bilinear2x_bwd_kernel<bf16_t>, dim3(grid), dim3(NTHR), 0, (hipStream_t)stream, (const bf16_t*)g_out,
-                           ld_go, N, H, W, Cp / 8, (bf16_t*)dx, ld_dx),
-        hipLaunchKernelGGL(upsample_bilinear2x_bwd_kernel<float>, dim3(grid), dim3(NTHR), 0, (hipStream_t)stream, (const float*)g_out,
-                           ld_go, N, H, W, Cp / 8, (float*)dx, ld_dx),
-        "segnb_upsample_bilinear2x_bwd")
-    SEGNB_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int segnb_maxpool_fwd(int dtype, const void* x, int ld_x, int N, int H, int W, int Cp, int k, int stride,
-                                 int pad, void* out, int ld_out, unsigned char* idx, segnb_stream_t stream) {
-    SEGNB_PLAN_RECORD(segnb_maxpool_fwd, dtype, x, ld_x, N, H, W, Cp, k, stride, pad, out, ld_out, idx, stream);
-    if (int rc = check_ew(N, H, W, Cp)) return rc;
-    SEGNB_CHECK_ARG(x && out && k >= 1 && stride >= 1 && pad >= 0 && pad < k, "bad pooling arguments");
-    const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
-    SEGNB_CHECK_ARG(Ho > 0 && Wo > 0, "empty pooled output");
-    int grid = ceil_div((long long)N * Ho * Wo * (Cp / 8), NTHR);
-    if (grid > 8192) grid = 8192;
-    SEGNB_DISPATCH_T(
-        hipLaunchKernelGGL(maxpool_fwd_kernel<bf16_t>, dim3(grid), dim3(NTHR), 0, (hipStream_t)stream, (const bf16_t*)x,
-                           ld_x, N, H, W, Cp / 8, k, stride, pad, Ho, Wo, (bf16_t*)out, ld_out, idx),
-        hipLaunchKernelGGL(maxpool_fwd_kernel<float>, dim3(grid), dim3(NTHR), 0, (hipStream_t)stream, (const float*)x,
-                           ld_x, N, H, W, Cp / 8, k, stride, pad, Ho, Wo, (float*)out, ld_out, idx),
-        "segnb_maxpool_fwd")
-    SEGNB_LAUNCH_CHECK();
-    return 0;
-}
-
-static int maxpool_bwd_impl(int dtype, const void* x, int ld_x, const void* g_out, int ld_go, int N, int H, int W, int Cp, int k,
-                            int stride, int pad, void* dx, int ld_dx, const unsigned char* idx, const void* g_out2, int ld_go2,
-                            segnb_stream_t stream);
-
-extern "C" int segnb_maxpool_bwd(int dtype, const void* x, int ld_x, const void* g_out, int ld_go, int N, int H, int W,
-                                 int Cp, int k, int stride, int pad, void* dx, int ld_dx, const unsigned char* idx,
-                                 segnb_stream_t stream) {
-    SEGNB_PLAN_RECORD(segnb_maxpool_bwd, dtype, x, ld_x, g_out, ld_go, N, H, W, Cp, k, stride, pad, dx, ld_dx, idx, stream);
-    return maxpool_bwd_impl(dtype, x, ld_x, g_out, ld_go, N, H, W, Cp, k, stride, pad, dx, ld_dx, idx, nullptr, 0, stream);
-}
-
-extern "C" int segnb_maxpool_bwd_add(int dtype, const void* x, int ld_x, const void* g_out, int ld_go, const void* g_out2,
-                                     int ld_go2, int N, int H, int W, int Cp, int k, int stride, int pad, void* dx, int ld_dx,
-                                     const unsigned char* idx, segnb_stream_t stream) {
-    SEGNB_PLAN_RECORD(segnb_maxpool_bwd_add, dtype, x, ld_x, g_out, ld_go, g_out2, ld_go2, N, H, W, Cp, k, stride, pad, dx, ld_dx, idx, stream);
-    SEGNB_CHECK_ARG(g_out2 != nullptr && idx != nullptr, "the two-source form takes the recorded argmax positions");
-    return maxpool_bwd_impl(dtype, x, ld_x, g_out, ld_go, N, H, W, Cp, k, stride, pad, dx, ld_dx, idx, g_out2, ld_go2, stream);
-}
-
-static int maxpool_bwd_impl(int dtype, const void* x, int ld_x, const void* g_out, int ld_go, int N, int H, int W, int Cp, int k,
-                            int stride, int pad, void* dx, int ld_dx, const unsigned char* idx, const void* g_out2, int ld_go2,
-                            segnb_stream_t stream) {
-    if (int rc = check_ew(N, H, W, Cp)) return rc;
-    SEGNB_CHECK_ARG(x && g_out && dx && k >= 1 && stride >= 1 && pad >= 0 && pad < k && k * k < 255, "bad pooling arguments");
-    const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
-    int grid = ceil_div((long long)N * H * W * (Cp / 8), NTHR);
-    if (grid > 8192) grid = 8192;
-    if (idx != nullptr) {
-        const bool i32 = (long long)N * H * W * (Cp / 8) < (1ll << 31);
-        if (i32) {
-            SEGNB_DISPATCH_T(
-                hipLaunchKernelGGL((maxpool_bwd_idx_kernel<bf16_t, true>), dim3(grid), dim3(NTHR), 0, (hipStream_t)stream, idx,
-                                   (const bf16_t*)g_out, ld_go, N, H, W, Cp / 8, k, stride, pad, Ho, Wo, (bf16_t*)dx, ld_dx,
-                                   (const bf16_t*)g_out2, ld_go2),
-                hipLaunchKernelGGL((maxpool_bwd_idx_kernel<float, true>), dim3(grid), dim3(NTHR), 0, (hipStream_t)stream, idx,
-                                   (const float*)g_out, ld_go, N, H, W, Cp / 8, k, stride, pad, Ho, Wo, (float*)dx, ld_dx,
-                                   (const float*)g_out2, ld_go2),
-                "segnb_maxpool_bwd")
-            SEGNB_LAUNCH_CHECK();
-            return 0;
-        }
-        SEGNB_DISPATCH_T(
-            hipLaunchKernelGGL((maxpool_bwd_idx_kernel<bf16_t, false>), dim3(grid), dim3(NTHR), 0, (hipStream_t)stream, idx,
-                               (const bf16_t*)g_out, ld_go, N, H, W, Cp / 8, k, stride, pad, Ho, Wo, (bf16_t*)dx, ld_dx,
-                               (const bf16_t*)g_out2, ld_go2),
-            hipLaunchKernelGGL((maxpool_bwd_idx_kernel<float, false>), dim3(grid), dim3(NTHR), 0, (hipStream_t)stream, idx,
-                               (const float*)g_out, ld_go, N, H, W, Cp / 8, k, stride, pad, Ho, Wo, (float*)dx, ld_dx,
-                               (const float*)g_out2, ld_go2),
-            "segnb_maxpool_bwd")
-        SEGNB_LAUNCH_CHECK();
-        return 0;
-    }
-    SEGNB_DISPATCH_T(
-        hipLaunchKernelGGL(maxpool_bwd_kernel<bf16_t>, dim3(grid), dim3(NTHR), 0, (hipStream_t)stream, (const bf16_t*)x,
-                           ld_x, (const bf16_t*)g_out, ld_go, N, H, W, Cp / 8, k, stride, pad, Ho, Wo, (bf16_t*)dx, ld_dx),
-        hipLaunchKernelGGL(maxpool_bwd_kernel<float>, dim3(grid), dim3(NTHR), 0, (hipStream_t)stream, (const float*)x,
-                           ld_x, (const float*)g_out, ld_go, N, H, W, Cp / 8, k, stride, pad, Ho, Wo, (float*)dx, ld_dx),
-        "segnb_maxpool_bwd")
-    SEGNB_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int segnb_nhwc_to_nchw_f32(int dtype, const void* a, int ld, int N, int H, int W, int C, float* out,
-                                      segnb_stream_t stream) {
-    SEGNB_PLAN_RECORD(segnb_nhwc_to_nchw_f32, dtype, a, ld, N, H, W, C, out, stream);
-    SEGNB_CHECK_ARG(a && out && N > 0 && H > 0 && W > 0 && C > 0 && ld >= C, "bad arguments");
-    int grid = ceil_div((long long)N * C * H * W, 256);
-    if (grid > 8192) grid = 8192;
-    SEGNB_DISPATCH_T(
-        hipLaunchKernelGGL(nhwc_to_nchw_f32_kernel<bf16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream,
-                           (const bf16_t*)a, ld, N, H, W, C, out),
-        hipLaunchKernelGGL(nhwc_to_nchw_f32_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream,
-                           (const float*)a, ld, N, H, W, C, out),
-        "segnb_nhwc_to_nchw_f32")
-    SEGNB_LAUNCH_CHECK();
-    return 0;
 }

@@ -619,16 +619,11 @@ extern "C" int segnb_pack_weight(const float* w, void* wpacked, int dtype, int M
     const long long total = (long long)Mp * ntaps * Cp;
     int grid = ceil_div(total, 256);
     if (grid > 4096) grid = 4096;
-    if (dtype == SEGNB_BF16)
-        hipLaunchKernelGGL(pack_weight_kernel<bf16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, w,
-                           (bf16_t*)wpacked, p);
-    else if (dtype == SEGNB_F32)
-        hipLaunchKernelGGL(pack_weight_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, w,
-                           (float*)wpacked, p);
-    else {
-        segnb_set_error("segnb_pack_weight: unknown dtype %d", dtype);
-        return SEGNB_E_BADARG;
-    }
+    if (int rc = segnb_dispatch_dtype(dtype, "segnb_pack_weight", [&](auto tag) SEGNB_INLINE_LAMBDA {
+            using T = SEGNB_TAG_T(tag);
+            hipLaunchKernelGGL(pack_weight_kernel<T>, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, (T*)wpacked, p);
+        }))
+        return rc;
     SEGNB_LAUNCH_CHECK();
     return 0;
 }
@@ -774,16 +769,12 @@ extern "C" int segnb_pack_input_nchw(const float* x, int N, int C, int H, int W,
     const long long total = (long long)N * H * W * (Cp / 8);
     int grid = ceil_div(total, 256);
     if (grid > 8192) grid = 8192;
-    if (dtype == SEGNB_BF16)
-        hipLaunchKernelGGL(pack_input_kernel<bf16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x,
-                           (bf16_t*)out, N, C, H, W, Cp, ld_out);
-    else if (dtype == SEGNB_F32)
-        hipLaunchKernelGGL(pack_input_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, (float*)out,
-                           N, C, H, W, Cp, ld_out);
-    else {
-        segnb_set_error("segnb_pack_input_nchw: unknown dtype %d", dtype);
-        return SEGNB_E_BADARG;
-    }
+    if (int rc = segnb_dispatch_dtype(dtype, "segnb_pack_input_nchw", [&](auto tag) SEGNB_INLINE_LAMBDA {
+            using T = SEGNB_TAG_T(tag);
+            hipLaunchKernelGGL(pack_input_kernel<T>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, (T*)out, N, C, H, W, Cp,
+                               ld_out);
+        }))
+        return rc;
     SEGNB_LAUNCH_CHECK();
     return 0;
 }
