@@ -229,6 +229,14 @@ GCN_SIGNATURES = {
 }
 GCN_PLAIN = {'segnb_gcn_ok': (c_int, [c_int, c_int, c_int, c_int, c_int])}
 
+# the ELU passes (nn.ELU, with the nearest x2 upsample + skip add of squeezenet.py:137-149), declared in include/segnb_elu.h
+# (csrc/elu.hip)
+ELU_SIGNATURES = {
+    'segnb_elu_fwd': [c_int, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, c_int, _P, c_int, _P],
+    'segnb_elu_bwd': [c_int, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, _P],
+}
+ELU_PLAIN = {'segnb_elu_ok': (c_int, [c_int, c_int, c_int, c_int, c_int])}
+
 _lib = None
 _test_backend = None
 
@@ -252,11 +260,12 @@ def load():
     # anything imported torch.  With torch's runtime already loaded the dynamic linker resolves this library's HIP symbols to it.
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in list(SIGNATURES.items()) + list(MC_SIGNATURES.items()) + list(GCN_SIGNATURES.items()):
+    for name, argtypes in (list(SIGNATURES.items()) + list(MC_SIGNATURES.items()) + list(GCN_SIGNATURES.items())
+                           + list(ELU_SIGNATURES.items())):
         fn = getattr(lib, name)         # AttributeError if the ABI and the header drift apart
         fn.argtypes = argtypes
         fn.restype = c_int
-    for name, (res, argtypes) in list(PLAIN.items()) + list(MC_PLAIN.items()) + list(GCN_PLAIN.items()):
+    for name, (res, argtypes) in list(PLAIN.items()) + list(MC_PLAIN.items()) + list(GCN_PLAIN.items()) + list(ELU_PLAIN.items()):
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = res

@@ -36,7 +36,7 @@ class Act(object):
     coef None: the tensor is act(conv) WITHOUT BatchNorm (y = the activated tensor itself); a consumer that can apply act' while it
     writes the gradient (the classifier heads: segnb_head_conv_bwd) then stores dz itself and sums it into `sums` -- g_is_dz then
     means .g IS dz and the producer's segnb_bn_act_bwd_reduce pass is skipped."""
-    __slots__ = ('v', '_g', '_g2', '_settle', 'needs_grad', 'consumers', 'producer', 'g_is_dz', 'lazy_ok', 'lazy_dgrad')
+    __slots__ = ('v', '_g', '_g2', '_settle', 'needs_grad', 'consumers', 'producer', 'g_is_dz', 'lazy_ok', 'lazy_dgrad', 'pieces')
 
     def __init__(self, v, needs_grad=True):
         self.v, self._g, self._g2, self._settle, self.needs_grad = v, None, None, None, needs_grad
@@ -45,6 +45,9 @@ class Act(object):
         # (ConvOp, dy View) set by the ONE consumer's _data_gradient, which then only ran the sums launch -- the gradient tensor
         # itself never exists (segnb_conv_fprop_bnsums / _bnapply)
         self.lazy_ok, self.lazy_dgrad = False, None
+        # pieces: [(Act, channel offset)] when this tensor is a zero-copy concatenation (concat): an operator over the whole view that
+        # can serve each piece's producer (elu) finds them here
+        self.pieces = None
 
     # The gradient.  A SECOND contribution is held back (Tape.contribute: _g2 + the launch that would add it): the convolution units
     # hand both sources to their reduction pass (segnb_bn_act_bwd_reduce_add) instead of an add pass over three tensors; any other
@@ -898,6 +901,7 @@ def add(tape, a, b, tag='add'):
 def concat(tape, pieces, cat_view):
     """pieces: [(Act, channel offset)] already WRITTEN into slices of cat_view (zero-copy torch.cat)."""
     ca = Act(cat_view)
+    ca.pieces = list(pieces)
     tape.consume(*[act for act, _ in pieces])
 
     def backward():
@@ -908,6 +912,93 @@ def concat(tape, pieces, cat_view):
 
     tape.record(backward)
     return ca
+
+
+def _elu_targets(x):
+    """The convolutions whose dz an ELU over x may write: [(Act, channel offset)] when x -- or every piece of the concat x is,
+    pieces tiling its channels in order -- is the output of a convolution WITHOUT BatchNorm or activation on its fused-epilogue path
+    (Act.producer with coef None, ACT_NONE) that nothing else reads; else None."""
+    def qualifies(a):
+        pr = a.producer
+        return (pr is not None and pr[1] is None and pr[3] == nv.ACT_NONE and a.consumers == 1 and a._g is None and a.needs_grad
+                and not a.g_is_dz)
+    if not Tape.fold_head_mask:
+        return None
+    if x.pieces is None:
+        return [(x, 0)] if qualifies(x) else None
+    if x.consumers != 1 or x._g is not None or not 1 <= len(x.pieces) <= 2:
+        return None
+    off = 0
+    for a, o in x.pieces:
+        if o != off or not qualifies(a):
+            return None
+        off += a.v.Cp
+    return list(x.pieces) if off == x.v.Cp else None
+
+
+def elu(tape, x, up_skip=None, out=None, tag='elu'):
+    """nn.ELU (alpha = 1) of x, in place on x.v unless `out` is given (squeezenet.py:14-20) -- in place only when this pass is the
+    ONE reader of x (ValueError otherwise: a second reader would see activated values); with up_skip also
+    up = F.upsample(elu(x), scale_factor=2, mode='nearest') + up_skip in the same launch (squeezenet.py:137-149: segnb_elu_fwd).
+    -> Act of the activated tensor, or (that, Act of up).
+
+    Backward: ONE segnb_elu_bwd over the gradient sources -- the direct gradient(s) of the activated tensor (two where
+    Tape.lazy_add held a second one back) and the gradient of up, which the skip operand also receives as it is.  When x is the
+    output of a convolution without BatchNorm whose only reader is this ELU -- or a concat of two such outputs -- the launch's dz
+    IS that convolution's gradient and its sums that convolution's bias-gradient sums (Act.g_is_dz, as head_conv does through
+    _head_mask): the convolution then runs no pass of its own.  Otherwise dz is contributed as a plain gradient."""
+    rt, xv = tape.rt, x.v
+    site = tape.site(tag)
+    tape.consume(x, up_skip)
+    N, H, W, Cp = xv.N, xv.H, xv.W, xv.Cp
+    if not nv.query('segnb_elu_ok', rt.code, N, H, W, Cp):
+        raise ValueError('ELU pass: a %dx%dx%d map of %d channels is out of range (segnb_elu_ok)' % (N, H, W, Cp))
+    av = out if out is not None else xv
+    # in place the raw values are gone: nothing but this pass may read x (a reader registered later is caught in the backward)
+    if out is None and x.consumers != 1:
+        raise ValueError('elu in place on a tensor with %d readers: the others would read activated values (pass out=)' % x.consumers)
+    uv = None
+    if up_skip is not None:
+        sv = up_skip.v
+        if (sv.N, sv.H, sv.W, sv.Cp) != (N, 2 * H, 2 * W, Cp):
+            raise ValueError('elu: skip %s does not match the upsampled output %s' % ((sv.N, sv.H, sv.W, sv.Cp), (N, 2 * H, 2 * W, Cp)))
+        uv = tape.view(site + '/up', N, 2 * H, 2 * W, Cp)
+    nv.call('segnb_elu_fwd', rt.code, xv.ptr, xv.ld, N, H, W, Cp, av.ptr, av.ld, vptr(up_skip.v if up_skip is not None else None),
+            vld(up_skip.v if up_skip is not None else None), vptr(uv), vld(uv), rt.stream)
+    oa = Act(av)
+    ua = Act(uv) if uv is not None else None
+
+    def backward():
+        gu = ua.g if ua is not None else None
+        if oa._g is None and gu is None:
+            return
+        if out is None and x.consumers != 1:
+            raise RuntimeError('elu ran in place on a tensor that %d operators read' % x.consumers)
+        if not x.needs_grad:
+            if gu is not None:
+                tape.contribute(up_skip, gu)
+            return
+        g1, g2 = tape.sources(oa, True)
+        targets = _elu_targets(x)
+        dz = tape.view(site + '/dz', N, H, W, Cp)
+        sums0 = sums1 = None
+        c0p = 0
+        if targets is not None:
+            sums0, c0p = targets[0][0].producer[2], targets[0][0].v.Cp
+            sums1 = targets[1][0].producer[2] if len(targets) == 2 else None
+        nv.call('segnb_elu_bwd', rt.code, av.ptr, av.ld, N, H, W, Cp, vptr(g1), vld(g1), vptr(g2), vld(g2), vptr(gu), vld(gu),
+                dz.ptr, dz.ld, nv.ptr(sums0), c0p, nv.ptr(sums1), rt.stream)
+        if gu is not None:
+            tape.contribute(up_skip, gu)          # (the skip operand's gradient is the gradient of up itself: no copy)
+        if targets is None:
+            tape.contribute(x, dz)
+            return
+        for a, off in targets:
+            a.g_is_dz = True
+            tape.contribute(a, dz if a is x else dz.slice(off, a.v.Cp))
+
+    tape.record(backward)
+    return (oa, ua) if ua is not None else oa
 
 
 def head_1x1(tape, x, weight, bias, dlogits_ref, tag='head'):

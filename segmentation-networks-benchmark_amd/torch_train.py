@@ -50,6 +50,9 @@ def get_model(model_name, patch_size=None, num_channels=3):
     if name == 'gcn34':
         from lib.models.gcn import GCN34
         return GCN34(input_size=patch_size, num_classes=1)
+    if name == 'squeezenet':
+        from lib.models.squeezenet import SqueezeNet
+        return SqueezeNet(num_classes=1, in_channels=num_channels)
     if name == 'tiramisu67':
         from lib.models.tiramisu import FCDenseNet67
         return FCDenseNet67(n_classes=1)
