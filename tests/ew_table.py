@@ -539,6 +539,18 @@ F32_ONLY = ('bias_grad_multi/', 'abn/', 'optim_', 'finalize_', 'bwd_finalize')  
 CASES = sorted('%s:%s' % (row, dt) for row in ROWS for dt in DTYPES if dt == 'f32' or not row.startswith(F32_ONLY))
 
 
+def run_outputs(case, device=None):
+    """the output buffers themselves, on the device they were written on (tests/ew_oracle.py compares them with a float64
+    oracle; run_case digests them) -> {output: tensor}"""
+    row, dt = case.rsplit(':', 1)
+    fn, args = ROWS[row]
+    r = Run(dt, device)
+    outs = fn(r, *args)
+    if r.dev.type == 'cuda':
+        torch.cuda.synchronize()
+    return outs
+
+
 def run_case(case, device=None):
     """-> {'entries': the entry points called, 'sha': {output: SHA-256 of the whole buffer}, 'excluded': {output: reason}}"""
     row, dt = case.rsplit(':', 1)

@@ -8,8 +8,9 @@ which any fp32 summation order of the K exact products satisfies, and operands t
 compared with `==`: the only check that sees a lost product behind thousands of terms (the deep-K shapes).
 
 The shapes are the case tables of test_hip_ops.py (each the smallest that reaches its kernel), with the kernel families forced
-the way the tests there force them.  The BatchNorm-fused variants (bnapply, bnreduce, tf, upcat, drop), the head kernels and the
-element-wise passes round more than once and are not covered here."""
+the way the tests there force them.  The head kernels and the element-wise passes round more than once: they are held to a
+float64 oracle in tests/test_ew_oracle_gpu.py (exact operands, `==`) and tests/test_ew_errbound_gpu.py (dense operands, derived
+bound).  The BatchNorm-fused variants of the convolutions (bnapply, bnreduce, tf, upcat, drop) keep the tests of test_hip_ops.py."""
 import os
 
 import pytest

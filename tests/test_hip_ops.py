@@ -10,7 +10,9 @@ Tolerances (written per check; check() below):
               (2^-8 relative) of an ELEMENT, but check() allows 2e-2 of the tensor's largest magnitude + 2e-2 of the element:
               10 to 35 times that on a typical element, enough to pass a kernel that drops one product per output.  The
               tight check of the convolutions -- a derived per-element bound against float64, and exact impulse probes -- is
-              tests/test_conv_errbound_gpu.py (tests/errbound.py).
+              tests/test_conv_errbound_gpu.py (tests/errbound.py).  The tight check of the BatchNorm, element-wise and head
+              passes -- a float64 oracle written from the contract, `==` on exact operands and a derived bound on dense ones
+              -- is tests/test_ew_oracle_gpu.py and tests/test_ew_errbound_gpu.py (tests/ew_oracle.py, tests/ew_dense.py).
 """
 import zlib
 
