@@ -46,10 +46,11 @@ int segnb_version(void);
 int segnb_device_cus(void);
 /* Kernel-selection knobs for A/B measurements and tests (results never depend on them beyond rounding order):
  *   "fprop_dma"      0 = never use the direct-to-LDS 3x3 pipeline (fprop_dma.hip), 1 = use it where it applies
- *   "fprop_dma_cfg"  -1 = automatic tile configuration, n >= 0 = force configuration n
+ *   "fprop_dma_cfg"  -1 = automatic tile configuration, n >= 0 = force configuration n (0: 8 x 32 pixels, 1: 16 x 16, 2: tall 36 x 7,
+ *                    3: 14 x 14 in 224 rows -- where a configuration does not serve a launch, the launch takes its default)
  *   "fprop_rw"       0 = never use the resident-weights pipeline of the thin layers (fprop_rw.hip)
  *   "fprop_dma_dbg"  timing builds (parts of the pipeline removed; results are WRONG when non-zero)
- *   "conv_cu_pct"    percentage (10..100) of the CUs the persistent convolution kernels size their grids for
+ *   "conv_cu_pct"    percentage (1..100) of the CUs the persistent convolution kernels size their grids for
  * Defaults come from the environment variables SEGNB_FPROP_DMA / SEGNB_FPROP_DMA_CFG.  Not thread-safe.
  * (The weight-gradient launches read SEGNB_WG_CU_FRACTION / SEGNB_WG_CU_FRACTION_THIN once: share of the CUs their
  * pixel split is sized for, default 0.5 / 1.0; segnb_conv_wgrad_slabs reports the resulting slab count.) */

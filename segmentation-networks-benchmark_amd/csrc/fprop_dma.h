@@ -122,9 +122,14 @@ template <int N>
 __device__ __forceinline__ void ws_wait1(bf16x8_t& f0) {
     asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(f0) : "n"(N));
 }
-template <int N>
-__device__ __forceinline__ void ws_wait5(bf16x8_t& f0, bf16x8_t& f1, bf16x8_t& f2, bf16x8_t& f3, bf16x8_t& f4) {
-    asm volatile("s_waitcnt lgkmcnt(%5)" : "+v"(f0), "+v"(f1), "+v"(f2), "+v"(f3), "+v"(f4) : "n"(N));
+// ... the first pixel fragment and the TN weight fragments of a 16x16x32 slice (wave tiles of 4 or 2 channel fragments)
+template <int N, int TN>
+__device__ __forceinline__ void ws_wait_xw(bf16x8_t& x0, bf16x8_t (&w)[TN]) {
+    static_assert(TN == 4 || TN == 2, "weight fragments per slice");
+    if constexpr (TN == 4)
+        asm volatile("s_waitcnt lgkmcnt(%5)" : "+v"(x0), "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]) : "n"(N));
+    else
+        asm volatile("s_waitcnt lgkmcnt(%3)" : "+v"(x0), "+v"(w[0]), "+v"(w[1]) : "n"(N));
 }
 __device__ __forceinline__ void raw_barrier() { asm volatile("s_barrier" ::: "memory"); }
 

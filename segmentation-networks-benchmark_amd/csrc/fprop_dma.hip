@@ -86,11 +86,18 @@ struct WsCfg {
     static_assert(!UPD_ || (NTAP_ == 4 && !TALL_ && MF16_), "plane gather: 2 x 2 window, 16x16x32 form");
     static constexpr bool TALL = TALL_;
     static constexpr bool MF16 = MF16_;                  // v_mfma_f32_16x16x32_bf16 (else 32x32x16)
-    static constexpr int TM16 = (TALL_ ? 256 : R_ * WT_) / CW_M_ / 16, TN16 = BN_ / (4 / CW_M_) / 16;
+    // BM matrix rows per tile: the R x WT pixels rounded up to whole 16-row fragments per M-wave.  16 x 16 and 8 x 32 tiles: 256;
+    // 14 x 14 tiles (CW_M_ = 2): 196 pixels in 224 rows -- rows >= R * WT are dummies: they read pixel 0's fragments, their
+    // pixel-table entry is -1 (never stored, never in the statistics)
+    static constexpr int BM = TALL_ ? 256 : (R_ * WT_ + 16 * CW_M_ - 1) / (16 * CW_M_) * (16 * CW_M_);
+    static constexpr int TM16 = BM / CW_M_ / 16, TN16 = BN_ / (4 / CW_M_) / 16;
     static constexpr int NB = 4;
     static constexpr int NT = 512, NCW = 4, NLW = 4;
-    static constexpr int BM = TALL_ ? 256 : R * WT;
     static_assert(R * WT <= BM, "tile pixels");
+    // 16x16x32 stream: NRD fragment reads of the NEXT K slice go out in the gaps of the NMF MFMAs of the current one, evenly
+    // spread; rd_before(q) of them have been issued before MFMA q
+    static constexpr int NRD = TM16 + TN16, NMF = TM16 * TN16;
+    static constexpr int rd_before(int q) { return (q * NRD + NMF - 1) / NMF; }
     static constexpr int WAVES_M = CW_M_, WAVES_N = NCW / CW_M_;
     static constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N;
     static constexpr int TM = WM / 32, TN = WN / 32;
@@ -120,9 +127,11 @@ struct WsCfg {
     static constexpr int OFF_TICKET = OFF_SCALE + BN * 4;     // split K: the ticket the block drew (one word)
     static constexpr int SMEM = OFF_TICKET + 16;
     static constexpr int RED_BYTES = MT * 16 * 8;
-    static_assert(WM % 32 == 0 && WN % 32 == 0 && WAVES_M * WAVES_N == NCW, "wave tiling");
+    static_assert(WM % (MF16_ ? 16 : 32) == 0 && WN % (MF16_ ? 16 : 32) == 0 && WAVES_M * WAVES_N == NCW, "wave tiling");
     static_assert(BPIECES % NBW == 0 && NBW + NAW == NLW, "fetch wave roles");
-    static_assert(MT % OC == 0 && MT >= 2 * BN && RPT <= 8 && BM == MT, "store pass / statistics threads");
+    static_assert(MT % OC == 0 && MT >= 2 * BN && RPT <= 8 && BM <= MT && BM % (MT / OC) == 0, "store pass / statistics threads");
+    // the activation-mask instantiation (conv_fprop_ws_kernel<..., MASK>): 256 x 64 tiles of four M-waves, 2 KB behind the layout
+    static constexpr bool MASK_OK = MF16_ && !TALL_ && BM == 256 && CW_M_ == 4 && SMEM + 2048 <= 160 * 1024;
     static_assert(RED_BYTES <= OFF_STG, "statistics reduction scratch");
     static_assert(SMEM <= 160 * 1024, "LDS");
     static_assert(TM + TN <= 6, "fragment wait statement");
@@ -421,10 +430,11 @@ __global__ __launch_bounds__(512) void conv_fprop_ws_kernel(const FdArgs a) {
         #pragma unroll
                 for (int rr = t128; rr < BM; rr += C::NAW * 64) {
                     const int ho = hb * R + rr / WT, wo = wb * WT + rr % WT;
+                    const bool in_tile = R * WT == BM || rr < R * WT;      // (14 x 14 tiles: rows 196..223 are dummies)
                     if constexpr (C::UPF)       // the tile row's pixel of this block's phase in the high-resolution output
                         sPix[table * BM + rr] = (live && ho < a.H && wo < a.W) ? (n * 2 * a.H + 2 * ho + py) * (2 * a.W) + 2 * wo + px : -1;
                     else
-                        sPix[table * BM + rr] = (live && ho < a.H && wo < a.W) ? (n * a.H + ho) * a.W + wo : -1;
+                        sPix[table * BM + rr] = (live && in_tile && ho < a.H && wo < a.W) ? (n * a.H + ho) * a.W + wo : -1;
                 }
             };
             auto fetch_a = [&](int p0, int p1, int c_, int buf) {
@@ -605,7 +615,8 @@ __global__ __launch_bounds__(512) void conv_fprop_ws_kernel(const FdArgs a) {
             for (int dwi = 0; dwi < KW; ++dwi)
     #pragma unroll
                 for (int i = 0; i < TM16; ++i) {
-                    const int m = wm * C::WM + 16 * i + r16;
+                    const int m_ = wm * C::WM + 16 * i + r16;
+                    const int m = (R * WT == BM || m_ < R * WT) ? m_ : 0;        // (dummy rows read pixel 0: finite values, inside the halo)
                     const int p = (m / WT) * XC + (m % WT) + a.dw[dwi];          // column-shifted pixel, tap row 0
                     const int key = p % XC;
                     int v = (p << 7) + ((g4 ^ ((key >> 1) & 7)) << 4);
@@ -651,14 +662,24 @@ __global__ __launch_bounds__(512) void conv_fprop_ws_kernel(const FdArgs a) {
         // run on registers after the MFMAs.
         int row_pix = -1, row_pix2 = -1;
         u32x4_t row_v = {0, 0, 0, 0}, row_v2 = {0, 0, 0, 0};     // (second set: two store rows per step, short 2 x 2-window tiles)
-        auto row_load = [&](int k, const int* tab) {           // staged row row0 + k * (MT / OC) of the previous tile
-            const int row = row0 + k * (C::MT / OC);
+        // Which staged row a thread stores at step k.  Full tiles: row0 + k * (MT / OC).  The 14 x 14 tile keeps the pixel ->
+        // thread assignment of the 16 x 16 tile on a 14 x 14 image -- thread row0 owns column row0 % 16 of the pixel rows
+        // row0 / 16 + 2 k -- so that every thread's fp32 statistics are the sums of the same values in the same order and a
+        // 14 x 14 image's statistics are the 16 x 16 tile's bit for bit; the threads of columns 14, 15 take a dummy row (not
+        // stored, not counted), as their rows are outside the image there.
+        constexpr bool T14 = !C::TALL && R * WT != BM;          // (the tall form's dummy rows are the tail of its 256)
+        static_assert(!T14 || (R == 14 && WT == 14 && C::MT / OC == 32 && C::RPT == 7), "store rows of the 14 x 14 tile");
+        const bool row_live = !T14 || (row0 & 15) < WT;
+        const int row_first = !T14 ? row0 : (row_live ? (row0 >> 4) * WT + (row0 & 15) : R * WT);
+        const int row_step = !T14 ? C::MT / OC : (row_live ? 2 * WT : 0);
+        auto row_load = [&](int k, const int* tab) {           // the staged row of step k of the previous tile
+            const int row = row_first + k * row_step;
             const unsigned a_pix = (unsigned)(size_t)(tab + row), a_v = (unsigned)(size_t)(sOut + row * OUT_ROW + cc * 16);
             asm volatile("ds_read_b32 %0, %1" : "=v"(row_pix) : "v"(a_pix));
             asm volatile("ds_read_b128 %0, %1" : "=v"(row_v) : "v"(a_v));
         };
         auto row_load2 = [&](int k, const int* tab) {
-            const int row = row0 + k * (C::MT / OC);
+            const int row = row_first + k * row_step;
             const unsigned a_pix = (unsigned)(size_t)(tab + row), a_v = (unsigned)(size_t)(sOut + row * OUT_ROW + cc * 16);
             asm volatile("ds_read_b32 %0, %1" : "=v"(row_pix2) : "v"(a_pix));
             asm volatile("ds_read_b128 %0, %1" : "=v"(row_v2) : "v"(a_v));
@@ -763,21 +784,26 @@ __global__ __launch_bounds__(512) void conv_fprop_ws_kernel(const FdArgs a) {
             // 16 channels (4 x 4: 16 MFMAs of 16 cycles per slice).  Two fragment sets (set = slice parity): the 8 reads of
             // the NEXT slice go out in the first 8 MFMA gaps of the current one, in consumption order (x0 w0 w1 w2 w3 x1 x2
             // x3), and every use waits only for what it consumes (counted lgkmcnt).
-            static_assert(TM16 == 4 && TN16 == 4, "16x16x32 wave tile is 64 pixels x 64 channels");
+            // The same stream serves the 14 x 14 tile (two M-waves x two N-waves): 112 rows x 32 channels per wave = 7 x 2 tiles, 14
+            // MFMAs and 7 + 2 reads per slice.  NRD reads of the next slice are spread evenly over the NMF gaps: rd_before(q) of them
+            // are out before MFMA q (4 x 4: one every second gap; 7 x 2: gaps 0 1 3 4 6 7 9 10 12).
+            static_assert((TM16 == 4 && TN16 == 4) || (TM16 == 7 && TN16 == 2), "16x16x32 wave tile: 64 x 64 or 112 pixels x 32 channels");
+            constexpr int NRD = C::NRD;
+            static_assert(NRD + TM16 - 1 <= 15, "counted lgkmcnt");
             bf16x8_t fw[2][TN16], fx[2][TM16];
             // q-th read of a fragment set, in consumption order; t = tap of the slice being fetched, k = its K slice,
             // wbase / xbase = wave-uniform LDS bases of its weight stage / halo buffer (+ the tap's row term)
             auto issue = [&](int q, int set, int wbase, int xbase, int t, int k) {
                 if (q == 0) { const int ad = a_rd16[t % KW][0][k] + xbase; FD_READ(fx[set][0], ad); }
-                else if (q <= 4) { const int ad = b_rd16[k][q - 1] + wbase; FD_READ(fw[set][q - 1], ad); }
-                else { const int ad = a_rd16[t % KW][q - 4][k] + xbase; FD_READ(fx[set][q - 4], ad); }
+                else if (q <= TN16) { const int ad = b_rd16[k][q - 1] + wbase; FD_READ(fw[set][q - 1], ad); }
+                else { const int ad = a_rd16[t % KW][q - TN16][k] + xbase; FD_READ(fx[set][q - TN16], ad); }
             };
             int arow[KW];                                          // row term of the tap rows (bytes)
 #pragma unroll
             for (int k = 0; k < KW; ++k) arow[k] = __builtin_amdgcn_readfirstlane(a.dh[KW * k] * XC * 128);
             if (!(DBG && (a.dbg & 4))) {
 #pragma unroll
-                for (int q = 0; q < 8; ++q) issue(q, 0, 0, arow[0], 0, 0);
+                for (int q = 0; q < NRD; ++q) issue(q, 0, 0, arow[0], 0, 0);
             }
             int tile_no = 0;
             bool pending = false;
@@ -843,19 +869,21 @@ __global__ __launch_bounds__(512) void conv_fprop_ws_kernel(const FdArgs a) {
                                 const int xbase = kk == 0 ? a_base + arow[t / KW] : anext + arow[tn / KW];
                                 // the current slice's x0, w0..w3 have landed (its x1..x3 may still be in flight; the
                                 // two row-store reads of a row tap are younger: the count is then conservative)
-                                ws_wait5<3>(fx[cur][0], fw[cur][0], fw[cur][1], fw[cur][2], fw[cur][3]);
+                                ws_wait_xw<TM16 - 1>(fx[cur][0], fw[cur]);
 #pragma unroll
                                 for (int i = 0; i < TM16; ++i) {
-                                    // one read of the next slice every second MFMA gap: at the waits below 2 i of the 8 are out
-                                    if (i == 1) ws_wait1<4>(fx[cur][1]);      // older x2, x3 + 2 new reads may be outstanding
-                                    if (i == 2) ws_wait1<5>(fx[cur][2]);      // older x3 + 4 new
-                                    if (i == 3) ws_wait1<6>(fx[cur][3]);      // 6 new
+                                    // row i's pixels have landed: the older x(i+1).. and the rd_before(i * TN16) reads of the next
+                                    // slice may be outstanding (4 x 4: counts 4, 5, 6 -- one read every second MFMA gap)
+                                    static_for<TM16 - 1>([&](auto k_c) {
+                                        constexpr int k = decltype(k_c)::value + 1;
+                                        if (i == k) ws_wait1<TM16 - 1 - k + C::rd_before(k * TN16)>(fx[cur][k]);
+                                    });
 #pragma unroll
                                     for (int j = 0; j < TN16; ++j) {
                                         const int q = i * TN16 + j;
-                                        if (q % 2 == 0 && !(SEGNB_EXP & 16) && !(DBG && (a.dbg & 16))) {
-                                            if (kk == 0) issue(q / 2, nxt, wbase, xbase, t, 1);
-                                            else issue(q / 2, nxt, wbase, xbase, tn, 0);
+                                        if (C::rd_before(q + 1) > C::rd_before(q) && !(SEGNB_EXP & 16) && !(DBG && (a.dbg & 16))) {
+                                            if (kk == 0) issue(C::rd_before(q), nxt, wbase, xbase, t, 1);
+                                            else issue(C::rd_before(q), nxt, wbase, xbase, tn, 0);
                                         }
                                         if (t == 0 && kk == 0 && c == 0)
                                             FD_MFMA16_0(accr[i][j], fw[cur][j], fx[cur][i]);
@@ -871,9 +899,9 @@ __global__ __launch_bounds__(512) void conv_fprop_ws_kernel(const FdArgs a) {
                             if (do_row) {
                                 if (DBG && (a.dbg & 4)) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                                 if constexpr (NTAP != 9)
-                                    asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(row_pix), "+v"(row_v), "+v"(row_pix2), "+v"(row_v2));
+                                    asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(row_pix), "+v"(row_v), "+v"(row_pix2), "+v"(row_v2) : "n"(NRD));
                                 else
-                                    asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(row_pix), "+v"(row_v));     // older than the 8 look-ahead reads
+                                    asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(row_pix), "+v"(row_v) : "n"(NRD));     // older than the NRD look-ahead reads
                                 row_store();
                                 if constexpr (NTAP != 9)
                                     if (a.RPS == 2) row_store_of(row_pix2, row_v2);
@@ -884,10 +912,9 @@ __global__ __launch_bounds__(512) void conv_fprop_ws_kernel(const FdArgs a) {
                     });
                 }
                 // look-ahead reads of the next tile's first slice must have LANDED before compiler-scheduled code runs
-                ws_wait5<0>(fx[0][0], fw[0][0], fw[0][1], fw[0][2], fw[0][3]);
-                ws_wait1<0>(fx[0][1]);
-                ws_wait1<0>(fx[0][2]);
-                ws_wait1<0>(fx[0][3]);
+                ws_wait_xw<0>(fx[0][0], fw[0]);
+#pragma unroll
+                for (int i = 1; i < TM16; ++i) ws_wait1<0>(fx[0][i]);
                 asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::);
                 if constexpr (SPLITK) {
                     ks_last = ks_publish([&](auto p_c) { constexpr int p = decltype(p_c)::value; return acc[p / TN16][p % TN16]; });
@@ -1195,7 +1222,7 @@ constexpr int NOT_HANDLED = -12345;
 
 template <class C>
 int launch_ws(FdArgs& a, hipStream_t stream) {
-    if (a.bn_y != nullptr && !(C::MF16 && !C::TALL && C::SMEM + 2048 <= 160 * 1024)) return NOT_HANDLED;      // (activation mask: 16 x 16 tiles, 16x16x32 form)
+    if (a.bn_y != nullptr && !C::MASK_OK) return NOT_HANDLED;      // (activation mask: 16 x 16 tiles, 16x16x32 form)
     static int attr_rc = [] {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fprop_ws_kernel<C, false>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM);
@@ -1208,7 +1235,7 @@ int launch_ws(FdArgs& a, hipStream_t stream) {
         if (e == hipSuccess)
             e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fprop_ws_kernel<C, false, false, false>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM);
-        if constexpr (C::MF16 && !C::TALL && C::SMEM + 2048 <= 160 * 1024) {
+        if constexpr (C::MASK_OK) {
             if (e == hipSuccess)
                 e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fprop_ws_kernel<C, false, false, true, false, true>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM + 2048);
@@ -1257,7 +1284,7 @@ int launch_ws(FdArgs& a, hipStream_t stream) {
     if (gm > a.IT) gm = a.IT;
     a.GM = gm;
     if (a.bn_y != nullptr) {      // activation mask of the producing layer (MASK instantiation: 16x16x32 form only)
-        if constexpr (C::MF16 && !C::TALL && C::SMEM + 2048 <= 160 * 1024) {
+        if constexpr (C::MASK_OK) {
             hipLaunchKernelGGL((conv_fprop_ws_kernel<C, false, false, true, false, true>), dim3(a.GM * a.NTL), dim3(C::NT), C::SMEM + 2048,
                                stream, a);
             return 0;
@@ -1271,6 +1298,49 @@ int launch_ws(FdArgs& a, hipStream_t stream) {
         hipLaunchKernelGGL((conv_fprop_ws_kernel<C, false, false, false>), dim3(a.GM * a.NTL), dim3(C::NT), C::SMEM, stream, a);
     else if (a.dbg)
         hipLaunchKernelGGL((conv_fprop_ws_kernel<C, true>), dim3(a.GM * a.NTL), dim3(C::NT), C::SMEM, stream, a);
+    else
+        hipLaunchKernelGGL((conv_fprop_ws_kernel<C, false>), dim3(a.GM * a.NTL), dim3(C::NT), C::SMEM, stream, a);
+    return 0;
+}
+
+// 14 x 14-pixel tiles in 224 matrix rows (cfg 3) for images whose sides are multiples of 14: the tile count, block order and
+// rounds of a launch are those of the 16 x 16 tiles (1, 4, 16 tiles per image at 14^2, 28^2, 56^2) and every tile issues 14
+// MFMAs per K slice and SIMD instead of 16.  The per-element K order (chunk, tap, K slice) is the 16 x 16 form's, so the
+// stored outputs are the same bits; the statistics are summed in another order.  Two instantiations: with statistics (the
+// forwards, the virtual concat among them) and without (the data gradients); everything else stays on the 256-row tiles.
+using WsCfg14 = WsCfg<64, 14, 14, 2, false, true>;
+
+bool ws14_serves(const FdArgs& a) {
+    return a.H % 14 == 0 && a.W % 14 == 0 && a.W <= 56 && a.Co > 32 && a.bn_y == nullptr && a.ep_act < 0 && !a.dbg &&
+           a.up_out == nullptr && segnb_knob_fprop_mf16();
+}
+
+int launch_ws14(FdArgs& a, hipStream_t stream) {
+    using C = WsCfg14;
+    static int attr_rc = [] {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fprop_ws_kernel<C, false>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM);
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fprop_ws_kernel<C, false, false, false>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM);
+        if (e != hipSuccess) segnb_set_error("fprop_ws hipFuncSetAttribute: %s", hipGetErrorString(e));
+        return (int)e;
+    }();
+    if (attr_rc) return attr_rc;
+    a.HB = a.H / C::R;
+    a.WB = a.W / C::WT;
+    a.IT = a.N * a.HB * a.WB;
+    a.NTL = (a.Co + C::BN - 1) / C::BN;
+    a.NCH = a.Ci / 64;
+    a.KS = 1;
+    a.ntmajor = 0;
+    int gm = segnb_knob_conv_cus() / a.NTL;
+    if (gm < 1) gm = 1;
+    if (gm > a.IT) gm = a.IT;
+    a.GM = gm;
+    if (g_segnb_census_on) segnb_census("tile:ws14");      // (beside the selector's "kernel:fprop_dma": which tile served it)
+    if (a.stats == nullptr && segnb_knob_fprop_nostats())
+        hipLaunchKernelGGL((conv_fprop_ws_kernel<C, false, false, false>), dim3(a.GM * a.NTL), dim3(C::NT), C::SMEM, stream, a);
     else
         hipLaunchKernelGGL((conv_fprop_ws_kernel<C, false>), dim3(a.GM * a.NTL), dim3(C::NT), C::SMEM, stream, a);
     return 0;
@@ -1361,9 +1431,25 @@ int try_upd(const segnb_conv_geom* g, FdArgs& a, hipStream_t stream) {
     return launch_ws_upd<WsCfg<64, 16, 16, 4, false, true, 4, 1>>(a, stream);
 }
 
+// The levels at which the 14 x 14 tile is the default (bit k: square images of 14 << k pixels).  Measured per launch of the
+// bs = 32 224 x 224 step, parent build against this one, alternating on one box (tools/tile14_bench.py, profiles/tile14_ab.txt):
+// forced, all 18 launches at 56^2, 28^2 and 14^2 are 6-12 % faster (741 -> 678 us in sum: 8.6 % of the 12.5 % fewer MFMA rows).
+// By default it serves the 12 of them whose every stored bit AND statistic stays the parent's -- the data gradients of the three
+// levels and the forwards at 14^2 (dispatch_fd: same_stats) -- 1.9-8.3 us each, 741 -> 700 us.  The LDS pays for part of the rest:
+// SQ_LDS_BANK_CONFLICT 6 -> 12 % and SQ_LDS_IDX_ACTIVE 19 -> 29 % of the wave cycles (7 + 2 fragment reads per 14 MFMAs instead
+// of 4 + 4 per 16), SQ_WAIT_INST_LDS unchanged at 2 %.  Other sizes made of 14 x 14 tiles (42^2, 28 x 56 ...)
+// were not measured: they take the tile under the knob only.
+constexpr unsigned WS14_DEFAULT_LEVELS = 7u;
+
 int dispatch_fd(FdArgs& a, hipStream_t stream) {
     // A/B testing (segnb_tune / environment): "fprop_dma" = 0 disables this path, "fprop_dma_cfg" forces a configuration
+    // (0: 8 x 32, 1: 16 x 16, 2: tall 36 x 7, 3: 14 x 14 in 224 rows -- a launch the 14 x 14 form does not serve takes its
+    // default tile: declined, not refused)
     int cfg = segnb_knob_fprop_dma_cfg();
+    bool row_major_taps = true;          // the 16x16x32 form indexes its address tables by (t / 3, t % 3)
+    for (int t = 0; t < 9; ++t) row_major_taps = row_major_taps && a.dw[t] == a.dw[t % 3] && a.dh[t] == a.dh[3 * (t / 3)];
+    const bool can14 = row_major_taps && ws14_serves(a);
+    if (cfg == 3 && !can14) cfg = -1;
     if (cfg < 0) {
         // measured per ZF_UNET layer at bs=32 (tools/layer_bench.py --cfg): 64-channel output tiles win on every level
         // from 14x14 to 112x112 -- twice the tiles of a 128-channel form (measured, since removed) on layers that have
@@ -1385,11 +1471,23 @@ int dispatch_fd(FdArgs& a, hipStream_t stream) {
         if (gm < 1) gm = 1;
         const long long it0 = (long long)a.N * ((a.H + 7) / 8) * ((a.W + 31) / 32);
         const long long it1 = (long long)a.N * ((a.H + 15) / 16) * ((a.W + 15) / 16);
-        cfg = (it0 + gm - 1) / gm < (it1 + gm - 1) / gm ? 0 : 1;
+        const long long r0 = (it0 + gm - 1) / gm, r1 = (it1 + gm - 1) / gm;
+        cfg = r0 < r1 ? 0 : 1;
         if (a.bn_y != nullptr) cfg = 1;      // (activation mask: the 16 x 16 tile form has the 2 KB of LDS left for the mask bytes)
+        // 14 x 14 tiles in 224 rows where the image is made of them: the time of a launch is its rounds x the MFMA rows of a
+        // tile, so the choice minimises that product (ties stay where they were) -- at the levels where it was measured to win
+        // A launch that takes statistics keeps them bit for bit only where the two tilings hold the same pixels per tile -- one
+        // tile per 14 x 14 image (conv_fprop_ws_kernel's store rows) -- so at 28^2 and 56^2 the forwards stay on 16 x 16 tiles:
+        // another summation order moves the training step's outputs by per cents
+        const bool same_stats = a.stats == nullptr || a.W == 14;
+        if (can14 && same_stats && a.H == a.W && ((a.W == 14 && (WS14_DEFAULT_LEVELS & 1u)) || (a.W == 28 && (WS14_DEFAULT_LEVELS & 2u)) ||
+                                                  (a.W == 56 && (WS14_DEFAULT_LEVELS & 4u)))) {
+            const long long it3 = (long long)a.N * (a.H / 14) * (a.W / 14);
+            const long long r3 = (it3 + gm - 1) / gm;
+            if (r3 * WsCfg14::BM < (cfg == 0 ? r0 : r1) * 256) cfg = 3;
+        }
     }
-    bool row_major_taps = true;          // the 16x16x32 form indexes its address tables by (t / 3, t % 3)
-    for (int t = 0; t < 9; ++t) row_major_taps = row_major_taps && a.dw[t] == a.dw[t % 3] && a.dh[t] == a.dh[3 * (t / 3)];
+    if (cfg == 3) return launch_ws14(a, stream);
     if (segnb_knob_fprop_mf16() && row_major_taps) {
         switch (cfg) {
             case 0: return launch_ws<WsCfg<64, 8, 32, 4, false, true>>(a, stream);
@@ -1460,7 +1558,7 @@ int segnb_fprop_upf_try(segnb_try_outcome* did, int N, int H, int W, int Ci, int
 
 // 1 when the MASK instantiation serves the data gradient g (segnb_conv_fprop_actmask_ok): what segnb_fprop_dma_try + dispatch_fd accept
 int segnb_fprop_dma_actmask_ok(const segnb_conv_geom* g) {
-    if (!segnb_knob_fprop_dma() || !segnb_knob_fprop_mask() || !segnb_knob_fprop_mf16() || segnb_knob_fprop_dma_cfg() >= 2 ||
+    if (!segnb_knob_fprop_dma() || !segnb_knob_fprop_mask() || !segnb_knob_fprop_mf16() || segnb_knob_fprop_dma_cfg() == 2 ||
         segnb_fprop_general_forced())
         return 0;
     if (!segnb_taps_3x3(g) || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return 0;

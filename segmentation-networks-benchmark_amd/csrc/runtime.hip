@@ -422,7 +422,7 @@ extern "C" int segnb_tune(const char* key, int value) {
         return 0;
     }
     if (strcmp(key, "conv_cu_pct") == 0) {        // CUs the persistent convolution kernels size their grids for (%)
-        g_conv_cu_pct = value < 10 ? 10 : (value > 100 ? 100 : value);
+        g_conv_cu_pct = value < 1 ? 1 : (value > 100 ? 100 : value);
         return 0;
     }
     if (strcmp(key, "plan_profile") == 0) {
