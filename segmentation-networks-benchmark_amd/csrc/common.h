@@ -149,6 +149,29 @@ inline int segnb_try_launched(segnb_try_outcome* did, int rc) {
 inline void segnb_kernel_took(segnb_try_outcome did, const char** served, const char* name) {
     if (did != SEGNB_TRY_DECLINED && *served == nullptr) *served = name;
 }
+// The fused epilogues of a try into its kernel's argument struct (FdArgs, RollArgs, ThinArgs, C8Args: the same field names).
+// take_bn_reduce: false -- the try declines -- when y's extent [N][Ho][Wo][ld_y] passes the 2 GiB of a buffer descriptor.
+// (forced inline: left to the inliner the tries of fprop_dma.hip, fprop_rw.hip and fprop_roll.hip called it)
+template <class Args>
+__attribute__((always_inline)) inline bool take_bn_reduce(Args& a, const segnb_conv_geom* g, const segnb_bn_reduce_epilogue* bn) {
+    const long long yb = (((long long)g->N * g->Ho * g->Wo - 1) * bn->ld_y + g->Co) * 2;
+    if (yb >= (1ll << 31)) return false;
+    a.bn_y = (const bf16_t*)bn->y;
+    a.bn_y_bytes = (unsigned)yb;
+    a.bn_ld = bn->ld_y;
+    a.bn_coef = bn->coef;
+    a.bn_sums = bn->sums;
+    a.bn_act = bn->act;
+    a.bn_slope = bn->slope;
+    return true;
+}
+// ep NULL: no affine + activation epilogue on this launch (ep_act < 0)
+template <class Args>
+__attribute__((always_inline)) inline void take_act_epilogue(Args& a, const segnb_act_epilogue* ep) {
+    a.ep_act = ep != nullptr ? ep->act : -1;
+    a.ep_coef = ep != nullptr ? ep->coef : nullptr;
+    a.ep_slope = ep != nullptr ? ep->slope : 0.f;
+}
 // fprop_thin.hip; bn: the BatchNorm-backward reduction epilogue of segnb_conv_fprop_bnreduce or NULL
 int segnb_fprop_thin_try(segnb_try_outcome* did, const segnb_conv_geom* g, const void* in, const void* wpacked, void* out,
                          hipStream_t stream, const segnb_bn_reduce_epilogue* bn);
@@ -253,6 +276,8 @@ __device__ __forceinline__ unsigned short f32_to_bf16_bits(float f) {
     __bf16 h = (__bf16)f;  // v_cvt_pk_bf16_f32: RNE, NaN stays NaN
     return __builtin_bit_cast(unsigned short, h);
 }
+// value as it reads back from a bf16 store
+__device__ __forceinline__ float round_bf16(float v) { return bf16_bits_to_f32(f32_to_bf16_bits(v)); }
 
 template <typename T>
 struct Elem;
@@ -272,7 +297,7 @@ struct Elem<bf16_t> {
         r.bits = f32_to_bf16_bits(v);
         return r;
     }
-    __device__ static __forceinline__ float round(float v) { return bf16_bits_to_f32(f32_to_bf16_bits(v)); }
+    __device__ static __forceinline__ float round(float v) { return round_bf16(v); }
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -353,9 +378,9 @@ __device__ __forceinline__ void store8(bf16_t* p, const float (&v)[8]) {
 }
 // value as it will read back from a T-typed store
 __device__ __forceinline__ float round_as(float v, const float*) { return v; }
-__device__ __forceinline__ float round_as(float v, const bf16_t*) {
-    return bf16_bits_to_f32(f32_to_bf16_bits(v));
-}
+__device__ __forceinline__ float round_as(float v, const bf16_t*) { return round_bf16(v); }
+
+#include "bn_expr.h"
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

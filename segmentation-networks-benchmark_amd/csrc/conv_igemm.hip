@@ -15,7 +15,7 @@
 // statistics), staged through LDS so global stores are 16-byte, pixel-contiguous.
 #include <stdlib.h>
 
-#include "common.h"
+#include "device.h"
 
 namespace {
 
@@ -73,22 +73,11 @@ struct WgradArgs {
     int M, Ktot, MT, NTL, S, steps_per_split, total_steps;
 };
 
-// buffer descriptor over [base, base + bytes): raw buffer (stride 0), loads beyond `bytes` return zeros
+// (make_rsrc, device.h: loads beyond the descriptor's `bytes` return zeros)
 constexpr unsigned OOB_OFFSET = 0x80000000u;
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
 __device__ __forceinline__ uint4 buf_load16(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0);
+    const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0);
     return make_uint4(v.x, v.y, v.z, v.w);
-}
-
-__device__ __forceinline__ int xcd_remap(int b, int G) {
-    // blocks b, b+8, ... share an XCD (round-robin dispatch): give each XCD a contiguous range of
-    // logical tiles so neighbours (same pixels, different channel tile) hit one L2.  Bijective for any G.
-    const int q = G >> 3, r = G & 7, x = b & 7, j = b >> 3;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + j;
 }
 
 // acc[TM][TN] += A_tile(rows am0.., K step) * B_tile(rows bn0..)^T ; tiles are [rows][LDS_ROW] images
@@ -209,7 +198,7 @@ __global__ __launch_bounds__(NT) void conv_fprop_kernel(const FpropArgs a) {
         }
 #pragma unroll
         for (int e = 0; e < 8; ++e) bs1[e] = bs2[e] = 0.f;
-        bneg = a.bn_act == SEGNB_ACT_RELU ? 0.f : (a.bn_act == SEGNB_ACT_LEAKY ? a.bn_slope : 1.f);
+        bneg = act_neg_scale(a.bn_act, a.bn_slope);
         if constexpr (BNM == 2) {
             // the fused finalize of bn_bwd_apply_kernel (norm_act.hip: bn_bwd_coef): every block derives (a, c1, c2) of its
             // channels from the completed sums; the blocks of pixel tile 0 publish them and add dgamma / dbeta
@@ -385,7 +374,7 @@ __global__ __launch_bounds__(NT) void conv_fprop_kernel(const FpropArgs a) {
                     sv = a.ep_coef[co];
                     bv = (bv - a.ep_coef[2 * a.g.Co + co]) * sv + a.ep_coef[a.g.Co + co];
                 }
-                ep_neg = a.ep_act == SEGNB_ACT_RELU ? 0.f : (a.ep_act == SEGNB_ACT_LEAKY ? a.ep_slope : 1.f);
+                ep_neg = act_neg_scale(a.ep_act, a.ep_slope);
             }
             float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -395,8 +384,7 @@ __global__ __launch_bounds__(NT) void conv_fprop_kernel(const FpropArgs a) {
                     const int row = wr * WM + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * h;
                     float ev = acc[i][j][e] + bv;
                     if constexpr (EP) {
-                        ev = acc[i][j][e] * sv + bv;
-                        if (ev < 0.f) ev = ev * ep_neg + 0.f;
+                        ev = act_fwd_neg(acc[i][j][e] * sv + bv, ep_neg);
                     }
                     const T tv = Elem<T>::from_f32(ev);
                     *reinterpret_cast<T*>(sOut + row * OUT_ROW + col * (int)sizeof(T)) = tv;
@@ -457,7 +445,7 @@ __global__ __launch_bounds__(NT) void conv_fprop_kernel(const FpropArgs a) {
                     load8(sStat + BN + cc * 8, bsc);
                     load8(sStat + 2 * BN + cc * 8, bsh);
                     if constexpr (BNM == 2) {
-                        // bn_bwd_apply_kernel's arithmetic (norm_act.hip: bn_dz_elem, bn_apply_elem, the ACC form's rounded add)
+                        // bn_bwd_apply_kernel's arithmetic (bn_expr.h: bn_dz_elem, bn_apply_elem; the ACC form's rounded add)
                         float aa[8], ac1[8], ac2[8], ais[8], old[8], o8[8];
                         load8(sApp + cc * 8, aa);
                         load8(sApp + BN + cc * 8, ac1);
@@ -470,10 +458,8 @@ __global__ __launch_bounds__(NT) void conv_fprop_kernel(const FpropArgs a) {
                         old[6] = __uint_as_float(xv.w << 16); old[7] = __uint_as_float(xv.w & 0xffff0000u);
 #pragma unroll
                         for (int e = 0; e < 8; ++e) {
-                            const float z = (yf[e] - bmu[e]) * bsc[e] + bsh[e] + 0.f;
-                            const float dv = bf16_bits_to_f32(f32_to_bf16_bits(gq8[e] * 1.f * (z > 0.f ? 1.f : bneg)));
-                            const float yh = (yf[e] - bmu[e]) * ais[e];
-                            const float dy = bf16_bits_to_f32(f32_to_bf16_bits(aa[e] * (dv - ac1[e] - yh * ac2[e])));
+                            const float dv = round_bf16(bn_dz_elem(gq8[e], yf[e], bmu[e], bsc[e], bsh[e], bneg));
+                            const float dy = round_bf16(bn_apply_elem(yf[e], dv, bmu[e], ais[e], aa[e], ac1[e], ac2[e]));
                             o8[e] = a.bn_accumulate ? __fadd_rn(old[e], dy) : dy;
                         }
                         uint4 ov;
@@ -485,7 +471,7 @@ __global__ __launch_bounds__(NT) void conv_fprop_kernel(const FpropArgs a) {
                     for (int e = 0; e < 8; ++e) {
                         const float yc = yf[e] - bmu[e];
                         const float z = yc * bsc[e] + bsh[e];
-                        const float dv = bf16_bits_to_f32(f32_to_bf16_bits(gq8[e] * (z > 0.f ? 1.f : bneg)));
+                        const float dv = round_bf16(gq8[e] * act_grad_neg(z, bneg));
                         bs1[e] += dv;
                         bs2[e] += dv * yc;
                     }

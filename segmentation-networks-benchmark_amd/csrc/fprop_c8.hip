@@ -97,11 +97,10 @@ __global__ __launch_bounds__(256) void conv_fprop_c8_kernel(const C8Args a) {
         bias4[g] = make_float4(b[0], b[1], b[2], b[3]);
         scale4[g] = make_float4(sc[0], sc[1], sc[2], sc[3]);
     }
-    const float ep_neg = a.ep_act == SEGNB_ACT_RELU ? 0.f : (a.ep_act == SEGNB_ACT_LEAKY ? a.ep_slope : 1.f);
+    const float ep_neg = act_neg_scale(a.ep_act, a.ep_slope);
     auto ep = [&](float acc, float sc, float sh) {
         if constexpr (EP) {
-            const float v = acc * sc + sh;
-            return v < 0.f ? v * ep_neg + 0.f : v;
+            return act_fwd_neg(acc * sc + sh, ep_neg);
         } else {
             return acc + sh;
         }
@@ -203,10 +202,7 @@ __global__ __launch_bounds__(256) void conv_fprop_c8_kernel(const C8Args a) {
             if (a.stats != nullptr) {
                 const float m = ok ? 1.f : 0.f;
                 float f[8];
-                f[0] = __uint_as_float(v[k].x << 16); f[1] = __uint_as_float(v[k].x & 0xffff0000u);
-                f[2] = __uint_as_float(v[k].y << 16); f[3] = __uint_as_float(v[k].y & 0xffff0000u);
-                f[4] = __uint_as_float(v[k].z << 16); f[5] = __uint_as_float(v[k].z & 0xffff0000u);
-                f[6] = __uint_as_float(v[k].w << 16); f[7] = __uint_as_float(v[k].w & 0xffff0000u);
+                unpack8(v[k], f);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const float fm = f[e] * m;
@@ -273,9 +269,7 @@ static bool c8_launch(const segnb_conv_geom* g, const void* in, const C8Norm* u8
         dwmin = g->dw[t] < dwmin ? g->dw[t] : dwmin;
     }
     C8Args a;
-    a.ep_act = ep != nullptr ? ep->act : -1;
-    a.ep_coef = ep != nullptr ? ep->coef : nullptr;
-    a.ep_slope = ep != nullptr ? ep->slope : 0.f;
+    take_act_epilogue(a, ep);
     if (u8 != nullptr) a.u8 = *u8;
     a.x = (const bf16_t*)in;
     a.w = (const bf16_t*)wpacked;

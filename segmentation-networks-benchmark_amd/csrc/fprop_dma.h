@@ -1,13 +1,11 @@
 // Shared pieces of the direct-to-LDS convolution pipelines (fprop_dma.hip, fprop_rw.hip): LDS-DMA issue, raw barriers
 // with counted waits, order-pinned fragment reads / MFMAs.  See fprop_dma.hip for the scheme.
 #pragma once
-#include "common.h"
+#include "device.h"
 
 #include <utility>
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) int i32x4_t;
 
 template <class F, int... Is>
 __device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, Is...>) {
@@ -80,18 +78,15 @@ struct FdArgs {
 
 constexpr unsigned OOB = 0x80000000u;
 
-__device__ __forceinline__ int xcd_remap_fd(int b, int G) {
-    const int q = G >> 3, r = G & 7, x = b & 7, j = b >> 3;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + j;
-}
-
+// the same descriptor as make_rsrc (device.h), as the four SGPRs that the inline-assembly DMA (dma16) names as one operand: the
+// builtin's __amdgpu_buffer_rsrc_t cannot be passed to an asm statement
 __device__ __forceinline__ i32x4_t make_rsrc4(const void* base, unsigned bytes) {
     const unsigned long long pa = (unsigned long long)base;
     i32x4_t r;
     r[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)pa);
     r[1] = __builtin_amdgcn_readfirstlane((int)((unsigned)(pa >> 32) & 0xffffu));
     r[2] = __builtin_amdgcn_readfirstlane((int)bytes);
-    r[3] = 0x00020000;
+    r[3] = RSRC_WORD3;
     return r;
 }
 
@@ -114,7 +109,6 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 #define FD_MFMA0(acc, a, b) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=v"(acc) : "v"(a), "v"(b))
 // 16 x 16 x 32 form (4 accumulator registers per 16-channel x 16-pixel tile): at equal cycles per FLOP the chip holds a
 // higher clock under this shape than under 32x32x16 (MI355X_MICROARCH.md, DVFS give-back item 7: 1.12-1.15x FLOP/s)
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 #define FD_MFMA16(acc, a, b) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b))
 #define FD_MFMA16_0(acc, a, b) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=v"(acc) : "v"(a), "v"(b))
 // counted LDS wait that names the fragment registers it completes

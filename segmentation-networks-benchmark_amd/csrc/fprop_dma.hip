@@ -180,7 +180,7 @@ __global__ __launch_bounds__(512) void conv_fprop_ws_kernel(const FdArgs a) {
     // read the same halo tiles).  ntmajor (tall tiles of the 7 x 7 level, where the weights are 6 x the activations and every
     // XCD would pull ALL of them through the fabric -- 151 MB per 1024 -> 1024 launch, which bounded it): the GM pixel tiles
     // of one (channel tile, slice) are neighbours, and so are the slices of a tile
-    int L_ = xcd_remap_fd(blockIdx.x, gridDim.x);
+    int L_ = xcd_remap(blockIdx.x, gridDim.x);
     int ks_ = 0, nt_, gq_;
     if (C::TALL && a.ntmajor) {
         gq_ = L_ % a.GM;
@@ -230,13 +230,12 @@ __global__ __launch_bounds__(512) void conv_fprop_ws_kernel(const FdArgs a) {
         }
         sBias[c] = sh;
     }
-    const float ep_neg = a.ep_act == SEGNB_ACT_RELU ? 0.f : (a.ep_act == SEGNB_ACT_LEAKY ? a.ep_slope : 1.f);
+    const float ep_neg = act_neg_scale(a.ep_act, a.ep_slope);
     const float upf_neg = ep_neg;
-    const float mask_neg = a.bn_act == SEGNB_ACT_RELU ? 0.f : (a.bn_act == SEGNB_ACT_LEAKY ? a.bn_slope : 1.f);
+    const float mask_neg = act_neg_scale(a.bn_act, a.bn_slope);
     auto ep = [&](float acc, float sc, float sh) {
         if constexpr (EP) {
-            const float v = acc * sc + sh;
-            return v < 0.f ? v * ep_neg + 0.f : v;
+            return act_fwd_neg(acc * sc + sh, ep_neg);
         } else {
             return acc + sh;
         }
@@ -487,10 +486,8 @@ __global__ __launch_bounds__(512) void conv_fprop_ws_kernel(const FdArgs a) {
                 }
             };
             // MASK: thread t128 of the 128 halo-wave threads owns channel chunk t128 & 7 of the staged rows (t128 >> 3) + 16 k
-            typedef __attribute__((ext_vector_type(4))) unsigned mu32x4_t;
-            mu32x4_t mreg[MASK ? 16 : 1];
-            const __amdgpu_buffer_rsrc_t rs_y =
-                __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(MASK ? a.bn_y : a.x), 0, MASK ? (int)a.bn_y_bytes : 0, 0x00020000);
+            u32x4_t mreg[MASK ? 16 : 1];
+            const __amdgpu_buffer_rsrc_t rs_y = make_rsrc(MASK ? a.bn_y : a.x, MASK ? a.bn_y_bytes : 0);
             auto mask_request = [&](int table) {
                 const int t128 = (lw & 1) * 64 + lane;
                 const int ch = n_base + (t128 & 7) * 8;
@@ -506,7 +503,7 @@ __global__ __launch_bounds__(512) void conv_fprop_ws_kernel(const FdArgs a) {
                 unsigned char* const dst = smem + C::SMEM + (t128 >> 3) * 8 + (t128 & 7);
 #pragma unroll
                 for (int k = 0; k < 16; ++k) {
-                    const mu32x4_t v = mreg[k];
+                    const u32x4_t v = mreg[k];
                     unsigned b = 0u;
                     b |= __uint_as_float(v.x << 16) > 0.f ? 1u : 0u;
                     b |= __uint_as_float(v.x & 0xffff0000u) > 0.f ? 2u : 0u;
@@ -648,9 +645,8 @@ __global__ __launch_bounds__(512) void conv_fprop_ws_kernel(const FdArgs a) {
 
         }
         lds_barrier();                                         // pipeline prologue: first operands have landed
-        typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
         unsigned char* const sOut = smem + C::OFF_STG;
-        const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(a.out, 0, (int)a.out_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_out = make_rsrc(a.out, a.out_bytes);
         const int cc = tid % OC, row0 = tid / OC;              // store pass: channel chunk, first staged row
         const bool cok = n_base + cc * 8 < a.Co;
         float s1[8], s2[8];                                    // statistics of the stored values of chunk cc
@@ -691,10 +687,7 @@ __global__ __launch_bounds__(512) void conv_fprop_ws_kernel(const FdArgs a) {
             if constexpr (STATS) {
                 const float m = ok ? 1.f : 0.f;
                 float f[8];
-                f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
-                f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
-                f[4] = __uint_as_float(v.z << 16); f[5] = __uint_as_float(v.z & 0xffff0000u);
-                f[6] = __uint_as_float(v.w << 16); f[7] = __uint_as_float(v.w & 0xffff0000u);
+                unpack8(v, f);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const float fm = f[e] * m;
@@ -709,8 +702,7 @@ __global__ __launch_bounds__(512) void conv_fprop_ws_kernel(const FdArgs a) {
         // came last reads every slab with sc1 loads).  The sum runs over the slabs in slice order, the reducer's own included,
         // so the result does not depend on which block arrives last.
         bool ks_last = true;
-        const __amdgpu_buffer_rsrc_t rs_slab =
-            __builtin_amdgcn_make_buffer_rsrc(SPLITK ? a.ks_slab : nullptr, 0, SPLITK ? (int)a.ks_slab_bytes : 0, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_slab = make_rsrc(SPLITK ? a.ks_slab : nullptr, SPLITK ? a.ks_slab_bytes : 0);
         const unsigned ks_tile = (unsigned)(gq * a.NTL + nt);
         const unsigned slab0 = ((ks_tile * (unsigned)a.KS) * 4u + (unsigned)(wave & 3)) * 16384u + (unsigned)lane * 16u;   // slice 0, piece 0
         auto ks_publish = [&](auto&& piece) {              // piece(p): accumulator registers 4 p .. 4 p + 3 of this lane
@@ -1683,20 +1675,11 @@ int segnb_fprop_dma_try(segnb_try_outcome* did, const segnb_conv_geom* g, const 
     a.bn_act = SEGNB_ACT_NONE;
     a.bn_slope = 0.f;
     if (bn != nullptr) {
-        const long long yb = (((long long)g->N * g->Ho * g->Wo - 1) * bn->ld_y + g->Co) * 2;
-        if (bn->ld_y % 8 != 0 || yb >= (1ll << 31)) return 0;      // (16-byte loads of 8-channel chunks)
-        a.bn_y = (const bf16_t*)bn->y;
-        a.bn_y_bytes = (unsigned)yb;
-        a.bn_ld = bn->ld_y;
-        a.bn_coef = nullptr;
-        a.bn_sums = bn->sums;
-        a.bn_act = bn->act;
-        a.bn_slope = bn->slope;
+        // (16-byte loads of 8-channel chunks; bn->coef is NULL here -- the gate at the top -- and so is a.bn_coef)
+        if (bn->ld_y % 8 != 0 || !take_bn_reduce(a, g, bn)) return 0;
         a.stats = bn->sums;          // [REPL][2][Co]: slot 0 = sum dz (the bias gradient's source), slot 1 = sum dz^2 (cleared with it)
     }
-    a.ep_act = ep != nullptr ? ep->act : -1;
-    a.ep_coef = ep != nullptr ? ep->coef : nullptr;
-    a.ep_slope = ep != nullptr ? ep->slope : 0.f;
+    take_act_epilogue(a, ep);
     const int rc = dispatch_fd(a, stream);
     if (rc == NOT_HANDLED) return 0;
     return segnb_try_launched(did, rc);

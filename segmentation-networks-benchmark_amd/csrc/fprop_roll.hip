@@ -27,8 +27,6 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
-
 struct RollArgs {
     const bf16_t* x;
     const bf16_t* w;
@@ -72,30 +70,6 @@ __device__ __forceinline__ int roll_sw(int j) {
     else return (((j >> 1) & 1) << 1) | (((j >> 2) & 1) << 2);
 }
 
-__device__ __forceinline__ void unpack8(const u32x4_t& v, float (&f)[8]) {
-    f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
-    f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
-    f[4] = __uint_as_float(v.z << 16); f[5] = __uint_as_float(v.z & 0xffff0000u);
-    f[6] = __uint_as_float(v.w << 16); f[7] = __uint_as_float(v.w & 0xffff0000u);
-}
-
-// 8 per-channel constants from an LDS table, re-read at every use: the index is laundered through an empty asm so that the
-// loop-invariant loads are not hoisted back into (40-56) registers
-__device__ __forceinline__ void lds_const8(const float* table, int idx, float (&v)[8]) {
-    asm volatile("" : "+v"(idx));
-    const float4 a = *reinterpret_cast<const float4*>(table + idx);
-    const float4 b = *reinterpret_cast<const float4*>(table + idx + 4);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-    v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-
-typedef short s16x2_t __attribute__((ext_vector_type(2)));
-// ReLU of two packed bf16 values: a negative bf16 is a negative int16 (v_pk_max_i16; -0 -> +0)
-__device__ __forceinline__ unsigned relu_pk2bf(unsigned pk) {
-    const s16x2_t z = {0, 0};
-    return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2_t, pk), z));
-}
-
 // KS: 32-channel K steps of the input (Ci = 32 * KS); COF: 16-channel output fragments (Co <= 16 * COF, COF even);
 // NF: 16-pixel fragments per strip row; EPI: 0 plain, 1 BatchNorm statistics of the output, 2 BatchNorm-backward reduction
 // of the producing layer, 3 the activation mask of a producing layer WITHOUT BatchNorm (bn_coef NULL: bn_y is the activated
@@ -131,13 +105,11 @@ __global__ __launch_bounds__((KSP * CSP == 1 ? 4 : KSP * CSP) * 64, WPS) void co
     const int sub = wave % WST, kpart = sub % KSP, cpart = sub / KSP, sidx = wave / WST;
     const int co0 = cpart * 16 * COF;                   // first output channel of this wave
 
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(a.x), 0, (int)a.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_x2 = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<bf16_t*>(TF == 2 ? a.x2 : a.x), 0, TF == 2 ? (int)a.x2_bytes : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(a.w), 0, (int)a.w_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_o = __builtin_amdgcn_make_buffer_rsrc(a.out, 0, (int)a.out_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<bf16_t*>(BNRED ? a.bn_y : a.x), 0, BNRED ? (int)a.bn_y_bytes : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = make_rsrc(a.x, a.x_bytes);
+    const __amdgpu_buffer_rsrc_t rs_x2 = make_rsrc(TF == 2 ? a.x2 : a.x, TF == 2 ? a.x2_bytes : 0);
+    const __amdgpu_buffer_rsrc_t rs_w = make_rsrc(a.w, a.w_bytes);
+    const __amdgpu_buffer_rsrc_t rs_o = make_rsrc(a.out, a.out_bytes);
+    const __amdgpu_buffer_rsrc_t rs_y = make_rsrc(BNRED ? a.bn_y : a.x, BNRED ? a.bn_y_bytes : 0);
 
     if (STATS || BNRED) {
         for (int i = threadIdx.x; i < 2 * 16 * COF * CSP; i += NTHR) (&red[0][0])[i] = 0.0;
@@ -181,7 +153,7 @@ __global__ __launch_bounds__((KSP * CSP == 1 ? 4 : KSP * CSP) * 64, WPS) void co
                 bnc[1][c] = in ? a.bn_coef[a.Co + c] - a.bn_coef[2 * a.Co + c] * a.bn_coef[c] : 0.f;
             }
         }
-        bneg = a.bn_act == SEGNB_ACT_RELU ? 0.f : (a.bn_act == SEGNB_ACT_LEAKY ? a.bn_slope : 1.f);
+        bneg = act_neg_scale(a.bn_act, a.bn_slope);
     }
     float s1[NP][8], s2[NP][8];
 #pragma unroll
@@ -190,30 +162,23 @@ __global__ __launch_bounds__((KSP * CSP == 1 ? 4 : KSP * CSP) * 64, WPS) void co
         for (int e = 0; e < 8; ++e) s1[p][e] = s2[p][e] = 0.f;
 
     // ---- input transform: per-channel constants of THIS lane's chunk (lane & (CPP - 1): the same for every load)
-    // TF = 1: exactly bn_act_fwd_kernel's expression.  TF = 2 in a folded form (5 constants per channel instead of 7; the
-    // registers are the budget here): with z = y * sc + shh (shh = shift - mean * scale), sel = act'(z),
-    //   dy = a * (g * drop * sel) + (B * y + C),   B = -a * c2 * invstd,  C = a * (c2 * invstd * mean - c1)
+    // TF = 1: exactly bn_act_fwd_kernel's expression.  TF = 2 in the folded form of bn_expr.h (bn_fold5_row: 5 constants per
+    // channel instead of 7), dy = a * (g * drop * sel) + (B * y + C)
     // = a * (dz - c1 - yhat * c2) of bn_bwd_apply_kernel up to fp32 rounding (dz is not rounded to bf16 in between: it is
     // exact for ReLU without dropout, the timed configuration's direct layers, and for dz inputs with act = NONE).
     float tneg = 0.f;
     const int tc0 = (lane % CPP) * 8;
     if constexpr (TF != 0) {
         for (int c = threadIdx.x; c < CI; c += NTHR) {
-            const float sc = a.tf_coef[c], sh = a.tf_coef[a.tf_Cp + c], mu = a.tf_coef[2 * a.tf_Cp + c];
-            tfc[0][c] = sc;
             if constexpr (TF == 1) {
-                tfc[1][c] = sh;
-                tfc[2][c] = mu;
+                tfc[0][c] = a.tf_coef[c];
+                tfc[1][c] = a.tf_coef[a.tf_Cp + c];
+                tfc[2][c] = a.tf_coef[2 * a.tf_Cp + c];
             } else {
-                const float is = a.tf_coef[3 * a.tf_Cp + c];
-                const float ba = a.tf_bcoef[c], c1 = a.tf_bcoef[a.tf_Cp + c], c2 = a.tf_bcoef[2 * a.tf_Cp + c];
-                tfc[1][c] = sh - mu * sc;
-                tfc[2][c] = ba;
-                tfc[3][c] = -ba * c2 * is;
-                tfc[4][c] = ba * (c2 * is * mu - c1);
+                bn_fold5_row(&tfc[0][0], CI, c, bn_bwd_consts(a.tf_coef, a.tf_bcoef, a.tf_Cp, c));
             }
         }
-        tneg = a.tf_act == SEGNB_ACT_RELU ? 0.f : (a.tf_act == SEGNB_ACT_LEAKY ? a.tf_slope : 1.f);
+        tneg = act_neg_scale(a.tf_act, a.tf_slope);
     }
     if (TF != 0 || BNRED) __syncthreads();
 
@@ -332,7 +297,7 @@ __global__ __launch_bounds__((KSP * CSP == 1 ? 4 : KSP * CSP) * 64, WPS) void co
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
                         const float z = yq[e] * tsc[e] + tsh[e];
-                        const float dzf = gq[e] * (z > 0.f ? 1.f : tneg);
+                        const float dzf = gq[e] * act_grad_neg(z, tneg);
                         gq[e] = tmu[e] * dzf + (tB[e] * yq[e] + tC[e]);
                     }
                     const bool ok = rv && colv[m];
@@ -511,7 +476,7 @@ __global__ __launch_bounds__((KSP * CSP == 1 ? 4 : KSP * CSP) * 64, WPS) void co
                                 unsigned pk[4];
 #pragma unroll
                                 for (int e = 0; e < 8; e += 2) {
-                                    const float d0 = v[e] * (yq[e] > 0.f ? 1.f : bneg), d1 = v[e + 1] * (yq[e + 1] > 0.f ? 1.f : bneg);
+                                    const float d0 = v[e] * act_grad_neg(yq[e], bneg), d1 = v[e + 1] * act_grad_neg(yq[e + 1], bneg);
                                     pk[e >> 1] = pack2bf(d0, d1);
                                     s1[p][e] += __uint_as_float(pk[e >> 1] << 16) * m;
                                     s1[p][e + 1] += __uint_as_float(pk[e >> 1] & 0xffff0000u) * m;
@@ -530,7 +495,7 @@ __global__ __launch_bounds__((KSP * CSP == 1 ? 4 : KSP * CSP) * 64, WPS) void co
 #pragma unroll
                             for (int e = 0; e < 8; ++e) {
                                 const float z = yq[e] * bsc[e] + bsh[e];
-                                const float dv = bf16_bits_to_f32(f32_to_bf16_bits(v[e] * (z > 0.f ? 1.f : bneg))) * m;
+                                const float dv = round_bf16(v[e] * act_grad_neg(z, bneg)) * m;
                                 s1[p][e] += dv;
                                 s2[p][e] += dv * yq[e];
                             }
@@ -705,15 +670,7 @@ int segnb_fprop_roll_try(segnb_try_outcome* did, const segnb_conv_geom* g, const
     }
     if (bn != nullptr) {
         if (stats != nullptr) return 0;
-        const long long yb = (((long long)g->N * g->Ho * g->Wo - 1) * bn->ld_y + g->Co) * 2;
-        if (yb >= (1ll << 31)) return 0;
-        a.bn_y = (const bf16_t*)bn->y;
-        a.bn_y_bytes = (unsigned)yb;
-        a.bn_ld = bn->ld_y;
-        a.bn_coef = bn->coef;
-        a.bn_sums = bn->sums;
-        a.bn_act = bn->act;
-        a.bn_slope = bn->slope;
+        if (!take_bn_reduce(a, g, bn)) return 0;
     }
     int rc;
     if (tf != nullptr) {

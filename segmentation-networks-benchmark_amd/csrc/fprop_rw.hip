@@ -67,7 +67,7 @@ __global__ __launch_bounds__(C::NT) void conv_fprop_rw_kernel(const FdArgs a) {
     const bool matrix = wave < C::NCW;
     const bool fetcher = !matrix && wave < C::NCW + NLW;
     const int lw = wave - C::NCW;                  // fetch wave index
-    const int gq = xcd_remap_fd(blockIdx.x, gridDim.x);      // one channel tile: block = pixel-tile queue
+    const int gq = xcd_remap(blockIdx.x, gridDim.x);      // one channel tile: block = pixel-tile queue
 
     const i32x4_t rs_x = make_rsrc4(a.x, a.x_bytes);
     const i32x4_t rs_w = make_rsrc4(a.w, a.w_bytes);
@@ -86,11 +86,10 @@ __global__ __launch_bounds__(C::NT) void conv_fprop_rw_kernel(const FdArgs a) {
         }
         sBias[c] = sh;
     }
-    const float ep_neg = a.ep_act == SEGNB_ACT_RELU ? 0.f : (a.ep_act == SEGNB_ACT_LEAKY ? a.ep_slope : 1.f);
+    const float ep_neg = act_neg_scale(a.ep_act, a.ep_slope);
     auto ep = [&](float acc, float sc, float sh) {
         if constexpr (EP) {
-            const float v = acc * sc + sh;
-            return v < 0.f ? v * ep_neg + 0.f : v;
+            return act_fwd_neg(acc * sc + sh, ep_neg);
         } else {
             return acc + sh;
         }
@@ -202,11 +201,10 @@ __global__ __launch_bounds__(C::NT) void conv_fprop_rw_kernel(const FdArgs a) {
         // coalesced store pass of one staged tile + statistics of the stored values (pixel table `tab`).  Branch-free:
         // all table and staging reads of a thread go out first, pixels outside the image are dropped by the output
         // descriptor's range check (a per-row `if` serialised two LDS round trips per row: ~2100 cycles per tile).
-        const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(a.out, 0, (int)a.out_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_out = make_rsrc(a.out, a.out_bytes);
         // fused BatchNorm-backward reduction (a.bn_y != NULL): per-thread constants of its channel chunk
         const bool bnred = C::STATS_OK && a.bn_y != nullptr;
-        const __amdgpu_buffer_rsrc_t rs_y =
-            __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(bnred ? a.bn_y : a.out), 0, bnred ? (int)a.bn_y_bytes : 0, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_y = make_rsrc(bnred ? a.bn_y : a.out, bnred ? a.bn_y_bytes : 0);
         float bsc[8], bsh[8], bmu[8];
         float bneg = 0.f;
         if (bnred) {
@@ -218,11 +216,10 @@ __global__ __launch_bounds__(C::NT) void conv_fprop_rw_kernel(const FdArgs a) {
                 bsh[e] = in ? a.bn_coef[a.Co + c0 + e] : 0.f;
                 bmu[e] = in ? a.bn_coef[2 * a.Co + c0 + e] : 0.f;
             }
-            bneg = a.bn_act == SEGNB_ACT_RELU ? 0.f : (a.bn_act == SEGNB_ACT_LEAKY ? a.bn_slope : 1.f);
+            bneg = act_neg_scale(a.bn_act, a.bn_slope);
         }
         auto store_pass = [&](const int* tab) {
             if (DBG && (a.dbg & 8)) return;
-            typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
             const int cc = ltid % OC, row0 = ltid / OC;
             const int ocu = a.up_out != nullptr ? a.up_C / 8 : 0;      // leading chunks that leave through the 2 x 2 sums below
             const bool cok = cc * 8 < a.Co && row0 < C::RG && cc >= ocu;      // (12 chunks per row: 120 of the 128 threads)
@@ -286,10 +283,7 @@ __global__ __launch_bounds__(C::NT) void conv_fprop_rw_kernel(const FdArgs a) {
                     if (C::STATS_OK && a.stats != nullptr) {
                         const float m = ok ? 1.f : 0.f;
                         float f[8];
-                        f[0] = __uint_as_float(v[k].x << 16); f[1] = __uint_as_float(v[k].x & 0xffff0000u);
-                        f[2] = __uint_as_float(v[k].y << 16); f[3] = __uint_as_float(v[k].y & 0xffff0000u);
-                        f[4] = __uint_as_float(v[k].z << 16); f[5] = __uint_as_float(v[k].z & 0xffff0000u);
-                        f[6] = __uint_as_float(v[k].w << 16); f[7] = __uint_as_float(v[k].w & 0xffff0000u);
+                        unpack8(v[k], f);
 #pragma unroll
                         for (int e = 0; e < 8; ++e) {
                             const float fm = f[e] * m;
@@ -300,19 +294,13 @@ __global__ __launch_bounds__(C::NT) void conv_fprop_rw_kernel(const FdArgs a) {
                         // dz = round(g * act'(z)), z = (y - mean) * scale + shift: the arithmetic of bn_act_bwd_reduce_kernel
                         const float m = ok ? 1.f : 0.f;
                         float gq[8], yq[8];
-                        gq[0] = __uint_as_float(v[k].x << 16); gq[1] = __uint_as_float(v[k].x & 0xffff0000u);
-                        gq[2] = __uint_as_float(v[k].y << 16); gq[3] = __uint_as_float(v[k].y & 0xffff0000u);
-                        gq[4] = __uint_as_float(v[k].z << 16); gq[5] = __uint_as_float(v[k].z & 0xffff0000u);
-                        gq[6] = __uint_as_float(v[k].w << 16); gq[7] = __uint_as_float(v[k].w & 0xffff0000u);
-                        yq[0] = __uint_as_float(yv[k].x << 16); yq[1] = __uint_as_float(yv[k].x & 0xffff0000u);
-                        yq[2] = __uint_as_float(yv[k].y << 16); yq[3] = __uint_as_float(yv[k].y & 0xffff0000u);
-                        yq[4] = __uint_as_float(yv[k].z << 16); yq[5] = __uint_as_float(yv[k].z & 0xffff0000u);
-                        yq[6] = __uint_as_float(yv[k].w << 16); yq[7] = __uint_as_float(yv[k].w & 0xffff0000u);
+                        unpack8(v[k], gq);
+                        unpack8(yv[k], yq);
 #pragma unroll
                         for (int e = 0; e < 8; ++e) {
                             const float yc = yq[e] - bmu[e];
                             const float z = yc * bsc[e] + bsh[e];
-                            const float dv = bf16_bits_to_f32(f32_to_bf16_bits(gq[e] * (z > 0.f ? 1.f : bneg))) * m;
+                            const float dv = round_bf16(gq[e] * act_grad_neg(z, bneg)) * m;
                             s1[e] += dv;
                             s2[e] += dv * yc;
                         }
@@ -569,20 +557,10 @@ int segnb_fprop_rw_try(segnb_try_outcome* did, const segnb_conv_geom* g, const v
         a.u_bytes = (unsigned)ub;
     }
     a.bn_y = nullptr;
-    a.ep_act = ep != nullptr ? ep->act : -1;
-    a.ep_coef = ep != nullptr ? ep->coef : nullptr;
-    a.ep_slope = ep != nullptr ? ep->slope : 0.f;
+    take_act_epilogue(a, ep);
     if (bn != nullptr) {
         if (stats != nullptr || g->Co > 64) return 0;                 // one accumulator set per launch; 96-wide: no statistics threads
-        const long long yb = (((long long)g->N * g->Ho * g->Wo - 1) * bn->ld_y + g->Co) * 2;
-        if (yb >= (1ll << 31)) return 0;
-        a.bn_y = (const bf16_t*)bn->y;
-        a.bn_y_bytes = (unsigned)yb;
-        a.bn_ld = bn->ld_y;
-        a.bn_coef = bn->coef;
-        a.bn_sums = bn->sums;
-        a.bn_act = bn->act;
-        a.bn_slope = bn->slope;
+        if (!take_bn_reduce(a, g, bn)) return 0;
     }
     int rc;
     // ring depth by what the resident weights leave of the 160 KiB.  96-channel outputs (the data gradient of the

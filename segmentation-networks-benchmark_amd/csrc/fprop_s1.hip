@@ -12,7 +12,7 @@
 // Rows are padded by 16 B (conflict-free ds_read_b128).  Epilogue as in conv_igemm.hip: +bias, round to bf16,
 // per-channel sum / sum^2 of the stored values (BatchNorm statistics), LDS-staged 16-byte stores.
 // Blocks are persistent over pixel tiles for a fixed channel tile so the statistics stay in registers.
-#include "common.h"
+#include "device.h"
 
 namespace {
 
@@ -34,11 +34,6 @@ struct FpS1Args {
     const float* drop;
     int ld_drop, stats_ld;
 };
-
-__device__ __forceinline__ int xcd_remap_s1(int b, int G) {
-    const int q = G >> 3, r = G & 7, x = b & 7, j = b >> 3;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + j;
-}
 
 template <int BN, int R, int WT, int WAVES_M, int BKC, int TPS>
 struct FpS1Cfg {
@@ -86,7 +81,7 @@ __global__ __launch_bounds__(256) void conv_fprop_s1x9_kernel(const FpS1Args a) 
     const int r = lane & 31, h = lane >> 5;
     const int wm = wave / C::WAVES_N, wn = wave % C::WAVES_N;
 
-    const int L = xcd_remap_s1(blockIdx.x, gridDim.x);
+    const int L = xcd_remap(blockIdx.x, gridDim.x);
     const int nt = L % a.NTL, gq = L / a.NTL;
     const int n_base = nt * BN;
 

@@ -21,9 +21,6 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2_t;
-
 struct ThinArgs {
     const bf16_t* x;
     const bf16_t* w;          // [Co][9][Ci]
@@ -60,16 +57,15 @@ __global__ __launch_bounds__(256, 2) void conv_thin_kernel(const ThinArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r16 = lane & 15, g = lane >> 4;
     const int cidx = ((g & 1) << 1) | (g >> 1);      // after the swap a lane owns the 16-byte chunk cidx of every 32-channel pair
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(a.x), 0, (int)a.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(a.w), 0, (int)a.w_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_o = __builtin_amdgcn_make_buffer_rsrc(a.out, 0, (int)a.out_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_y =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(BNR ? a.bn_y : a.x), 0, BNR ? (int)a.bn_y_bytes : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = make_rsrc(a.x, a.x_bytes);
+    const __amdgpu_buffer_rsrc_t rs_w = make_rsrc(a.w, a.w_bytes);
+    const __amdgpu_buffer_rsrc_t rs_o = make_rsrc(a.out, a.out_bytes);
+    const __amdgpu_buffer_rsrc_t rs_y = make_rsrc(BNR ? a.bn_y : a.x, BNR ? a.bn_y_bytes : 0);
 
     if constexpr (BNR) {
         for (int c = tid; c < 2 * TH_MAXC; c += 256) sAcc[c] = 0.0;
     }
-    const float bneg = !BNR ? 0.f : (a.bn_act == SEGNB_ACT_RELU ? 0.f : (a.bn_act == SEGNB_ACT_LEAKY ? a.bn_slope : 1.f));
+    const float bneg = !BNR ? 0.f : act_neg_scale(a.bn_act, a.bn_slope);
     const bool round_dz = bneg != 0.f && bneg != 1.f;
 
     // weight image of channel tile ct: thread t copies 16-byte chunks q = t, t + 256, ... of the [64][20] chunk grid; chunk (row, c):
@@ -204,8 +200,8 @@ __global__ __launch_bounds__(256, 2) void conv_thin_kernel(const ThinArgs a) {
                             const int cl = 32 * jp + 8 * cidx + e;
                             const float yc = yf - cf[cl];
                             const float z = yc * cf[64 + cl] + cf[128 + cl];
-                            float dv = z > 0.f ? gv : gv * bneg;
-                            if (round_dz) dv = bf16_bits_to_f32(f32_to_bf16_bits(dv));
+                            float dv = act_bwd_neg(gv, z, bneg);
+                            if (round_dz) dv = round_bf16(dv);
                             s1[e] += dv;
                             s2[e] += dv * yc;
                         }
@@ -295,16 +291,7 @@ int segnb_fprop_thin_try(segnb_try_outcome* did, const segnb_conv_geom* g, const
     a.NCT = (g->Co + (bn != nullptr ? 31 : 63)) / (bn != nullptr ? 32 : 64);
     a.bn_y = nullptr;
     if (bn != nullptr) {
-        if (bn->coef == nullptr) return 0;
-        const long long yb = (((long long)g->N * g->Ho * g->Wo - 1) * bn->ld_y + g->Co) * 2;
-        if (yb >= (1ll << 31) || bn->ld_y % 8 != 0) return 0;
-        a.bn_y = (const bf16_t*)bn->y;
-        a.bn_y_bytes = (unsigned)yb;
-        a.bn_ld = bn->ld_y;
-        a.bn_coef = bn->coef;
-        a.bn_sums = bn->sums;
-        a.bn_act = bn->act;
-        a.bn_slope = bn->slope;
+        if (bn->coef == nullptr || bn->ld_y % 8 != 0 || !take_bn_reduce(a, g, bn)) return 0;
     }
     const int slots = segnb_knob_conv_cus() * 2;
     a.NCS = 1;

@@ -459,11 +459,11 @@ __global__ __launch_bounds__(256) void head_conv_bwd_kernel(const T* __restrict_
                         }
                     }
                 if (act >= 0) {
-                    const float neg = act == SEGNB_ACT_RELU ? 0.f : (act == SEGNB_ACT_LEAKY ? slope : 1.f);
+                    const float neg = act_neg_scale(act, slope);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
                         const float gr = round_as(d[e], da);
-                        d[e] = round_as(av[u][e] > 0.f ? gr : gr * neg, da);
+                        d[e] = round_as(act_bwd_neg(gr, av[u][e], neg), da);
                         sz[e] += d[e];
                     }
                 }

@@ -20,18 +20,7 @@ namespace {
 
 constexpr int REPL = SEGNB_STAT_REPLICAS;
 
-// Branch-free activations: none / ReLU / LeakyReLU are all "negative side scaled by s" with s = 1 / 0 / slope (a
-// switch on `act` per element compiled to two scalar branches per element -- 153 branches in the pooled backward
-// kernel -- with the loads fenced between them).  "+ 0.f" turns ReLU's -0.0 into torch's +0.0.
-__device__ __forceinline__ float act_neg_scale(int act, float slope) {
-    return act == SEGNB_ACT_RELU ? 0.f : (act == SEGNB_ACT_LEAKY ? slope : 1.f);
-}
-__device__ __forceinline__ float act_fwd(float z, int act, float slope) {
-    return (z > 0.f ? z : z * act_neg_scale(act, slope)) + 0.f;
-}
-__device__ __forceinline__ float act_grad(float z, int act, float slope) {
-    return z > 0.f ? 1.f : act_neg_scale(act, slope);
-}
+// (the activations act_fwd / act_grad and the per-element expressions of the apply pass: bn_expr.h)
 
 // ------------------------------------------------------------------------------------------------
 // per-channel forward coefficients from the replicated statistics (training) or the running statistics (eval);
@@ -1096,15 +1085,8 @@ __global__ void bn_bwd_finalize_kernel(const BnBwdParams p, const float* __restr
     }
 }
 
-// The two per-element expressions of the apply pass, shared by both forms of the kernel (one expression tree = one contraction
-// decision of the compiler: the lean form stays bit-identical to this one, and to conv_wgrad_c8roll_kernel's recomputed dy)
-__device__ __forceinline__ float bn_dz_elem(float d, float yv, float mu, float sc, float sh, int act, float slope) {
-    return d * 1.f * act_grad((yv - mu) * sc + sh + 0.f, act, slope);
-}
-__device__ __forceinline__ float bn_apply_elem(float yv, float d, float mu, float is, float a, float c1, float c2) {
-    const float yh = (yv - mu) * is;
-    return a * (d - c1 - yh * c2);
-}
+// Both forms of the apply pass below take their two per-element expressions from bn_expr.h (bn_dz_elem, bn_apply_elem), and so does
+// every convolution kernel that recomputes this pass: the results stay bit-identical
 
 template <typename T, bool ACC = false>       // ACC: dy += result (gradient of a multi-consumer tensor: no separate segnb_add pass)
 __global__ __launch_bounds__(NTHR) void bn_bwd_apply_kernel(const T* __restrict__ y, int ld_y, EwShape s,

@@ -22,10 +22,6 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4_t;
-typedef __attribute__((address_space(3))) bf16x4_t lds_bf16x4_t;
-
 struct WRollArgs {
     const bf16_t* x;
     const bf16_t* d;
@@ -46,27 +42,6 @@ struct WRollArgs {
     int tfd_Cp, tfd_act;
     float tfd_slope;
 };
-
-__device__ __forceinline__ void unpack8w(const u32x4_t& v, float (&f)[8]) {
-    f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
-    f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
-    f[4] = __uint_as_float(v.z << 16); f[5] = __uint_as_float(v.z & 0xffff0000u);
-    f[6] = __uint_as_float(v.w << 16); f[7] = __uint_as_float(v.w & 0xffff0000u);
-}
-
-typedef short s16x2w_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned relu_pk2bfw(unsigned pk) {
-    const s16x2w_t z = {0, 0};
-    return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2w_t, pk), z));
-}
-
-__device__ __forceinline__ void lds_const8w(const float* table, int idx, float (&v)[8]) {
-    asm volatile("" : "+v"(idx));
-    const float4 a = *reinterpret_cast<const float4*>(table + idx);
-    const float4 b = *reinterpret_cast<const float4*>(table + idx + 4);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-    v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
 
 constexpr int WR_WAVES = 8;
 constexpr int WR_XPX = 34, WR_XROWB = WR_XPX * 64, WR_DROWB = 32 * 32;
@@ -99,10 +74,9 @@ __global__ __launch_bounds__(WR_WAVES * 64, 2) void conv_wgrad_roll_kernel(const
     const int wps = a.NCOH;                              // waves per strip
     const int coh = wave % wps, pair = wave / wps, npair = WR_WAVES / wps;
 
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(a.x), 0, (int)a.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_d = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(a.d), 0, (int)a.d_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_d2 = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<bf16_t*>(TFD == 2 ? a.d2 : a.d), 0, TFD == 2 ? (int)a.d2_bytes : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = make_rsrc(a.x, a.x_bytes);
+    const __amdgpu_buffer_rsrc_t rs_d = make_rsrc(a.d, a.d_bytes);
+    const __amdgpu_buffer_rsrc_t rs_d2 = make_rsrc(TFD == 2 ? a.d2 : a.d, TFD == 2 ? a.d2_bytes : 0);
 
     for (int i = threadIdx.x; i < WR_SLAB_FLOATS; i += WR_WAVES * 64) slab[i] = 0.f;
     float xneg = 0.f, dneg = 0.f;
@@ -112,7 +86,7 @@ __global__ __launch_bounds__(WR_WAVES * 64, 2) void conv_wgrad_roll_kernel(const
             cx[32 + c] = a.tfx_coef[a.tfx_Cp + c];
             cx[64 + c] = a.tfx_coef[2 * a.tfx_Cp + c];
         }
-        xneg = a.tfx_act == SEGNB_ACT_RELU ? 0.f : (a.tfx_act == SEGNB_ACT_LEAKY ? a.tfx_slope : 1.f);
+        xneg = act_neg_scale(a.tfx_act, a.tfx_slope);
     }
     if constexpr (TFD == 2) {
         for (int c = threadIdx.x; c < 32; c += WR_WAVES * 64) {
@@ -121,13 +95,9 @@ __global__ __launch_bounds__(WR_WAVES * 64, 2) void conv_wgrad_roll_kernel(const
             const float mu = in ? a.tfd_coef[2 * a.tfd_Cp + c] : 0.f, is = in ? a.tfd_coef[3 * a.tfd_Cp + c] : 0.f;
             const float ba = in ? a.tfd_bcoef[c] : 0.f, c1 = in ? a.tfd_bcoef[a.tfd_Cp + c] : 0.f;
             const float c2 = in ? a.tfd_bcoef[2 * a.tfd_Cp + c] : 0.f;
-            cd[c] = sc;
-            cd[32 + c] = sh - mu * sc;
-            cd[64 + c] = ba;
-            cd[96 + c] = -ba * c2 * is;
-            cd[128 + c] = ba * (c2 * is * mu - c1);
+            bn_fold5_row(cd, 32, c, {sc, sh, mu, is, ba, c1, c2});
         }
-        dneg = a.tfd_act == SEGNB_ACT_RELU ? 0.f : (a.tfd_act == SEGNB_ACT_LEAKY ? a.tfd_slope : 1.f);
+        dneg = act_neg_scale(a.tfd_act, a.tfd_slope);
     }
     __syncthreads();
 
@@ -188,9 +158,9 @@ __global__ __launch_bounds__(WR_WAVES * 64, 2) void conv_wgrad_roll_kernel(const
         float q1[8], q0[8];
         if constexpr (TFX == 1) {
             float tsc[8], tsh[8], tmu[8];
-            lds_const8w(cx, xc0, tsc);
-            lds_const8w(cx + 32, xc0, tsh);
-            lds_const8w(cx + 64, xc0, tmu);
+            lds_const8(cx, xc0, tsc);
+            lds_const8(cx + 32, xc0, tsh);
+            lds_const8(cx + 64, xc0, tmu);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const float dm = a.tfx_drop != nullptr ? a.tfx_drop[n * a.tfx_Cp + xc0 + e] : 1.f;
@@ -226,15 +196,15 @@ __global__ __launch_bounds__(WR_WAVES * 64, 2) void conv_wgrad_roll_kernel(const
                 u32x4_t v = lx[set][m];
                 if constexpr (TFX == 1) {
                     float f[8];
-                    unpack8w(v, f);
+                    unpack8(v, f);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) f[e] = f[e] * q1[e] + q0[e];
                     const bool ok = rv && xcolv[m];
                     if (xneg == 0.f) {
-                        v.x = ok ? relu_pk2bfw(pack2bf(f[0], f[1])) : 0u;
-                        v.y = ok ? relu_pk2bfw(pack2bf(f[2], f[3])) : 0u;
-                        v.z = ok ? relu_pk2bfw(pack2bf(f[4], f[5])) : 0u;
-                        v.w = ok ? relu_pk2bfw(pack2bf(f[6], f[7])) : 0u;
+                        v.x = ok ? relu_pk2bf(pack2bf(f[0], f[1])) : 0u;
+                        v.y = ok ? relu_pk2bf(pack2bf(f[2], f[3])) : 0u;
+                        v.z = ok ? relu_pk2bf(pack2bf(f[4], f[5])) : 0u;
+                        v.w = ok ? relu_pk2bf(pack2bf(f[6], f[7])) : 0u;
                     } else {
 #pragma unroll
                         for (int e = 0; e < 8; ++e) f[e] = f[e] > 0.f ? f[e] : f[e] * xneg;
@@ -252,17 +222,17 @@ __global__ __launch_bounds__(WR_WAVES * 64, 2) void conv_wgrad_roll_kernel(const
             u32x4_t v = ldd[set];
             if constexpr (TFD == 2) {
                 float gq[8], yq[8], tsc[8], tsh[8], tba[8], tB[8], tC[8];
-                unpack8w(v, gq);
-                unpack8w(ld2[set], yq);
-                lds_const8w(cd, dc0, tsc);
-                lds_const8w(cd + 32, dc0, tsh);
-                lds_const8w(cd + 64, dc0, tba);
-                lds_const8w(cd + 96, dc0, tB);
-                lds_const8w(cd + 128, dc0, tC);
+                unpack8(v, gq);
+                unpack8(ld2[set], yq);
+                lds_const8(cd, dc0, tsc);
+                lds_const8(cd + 32, dc0, tsh);
+                lds_const8(cd + 64, dc0, tba);
+                lds_const8(cd + 96, dc0, tB);
+                lds_const8(cd + 128, dc0, tC);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const float z = yq[e] * tsc[e] + tsh[e];
-                    const float dzf = gq[e] * (z > 0.f ? 1.f : dneg);
+                    const float dzf = gq[e] * act_grad_neg(z, dneg);
                     gq[e] = tba[e] * dzf + (tB[e] * yq[e] + tC[e]);
                 }
                 const bool ok = i < rows && dcolv;
@@ -299,15 +269,15 @@ __global__ __launch_bounds__(WR_WAVES * 64, 2) void conv_wgrad_roll_kernel(const
                 for (int dx = 0; dx < 3; ++dx)
 #pragma unroll
                     for (int cf = 0; cf < 2; ++cf) {
-                        const bf16x4_t b0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_t*)(uintptr_t)(xro[dx][cf] + xs));
-                        const bf16x4_t b1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_t*)(uintptr_t)(xro[dx][cf] + xs + 16 * 64));
+                        const bf16x4_t b0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(uintptr_t)(xro[dx][cf] + xs));
+                        const bf16x4_t b1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(uintptr_t)(xro[dx][cf] + xs + 16 * 64));
                         Bf[dx * 2 + cf] = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
                     }
             };
             // A operand: dy^T, 16 channels x 32 pixels; the fragment reads run one kernel row ahead of their MFMAs (the
             // compiler otherwise sinks every read next to its MFMA and the LDS latency is paid 18 times per row)
-            const bf16x4_t a0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_t*)(uintptr_t)(dro + DS * WR_DROWB));
-            const bf16x4_t a1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_t*)(uintptr_t)(dro + DS * WR_DROWB + 16 * 32));
+            const bf16x4_t a0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(uintptr_t)(dro + DS * WR_DROWB));
+            const bf16x4_t a1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(uintptr_t)(dro + DS * WR_DROWB + 16 * 32));
             const bf16x8_t A = __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7);
             bf16x8_t B0[6], B1[6], B2[6];
             read_group(std::integral_constant<int, 0>{}, B0);
@@ -429,10 +399,9 @@ __global__ __launch_bounds__(NW * 64, 1) void conv_wgrad_c8roll_kernel(const WRo
     const int n16 = lane & 15, kg = lane >> 4, q4 = n16 >> 2, p4 = n16 & 3;
     const bool hi = (p4 >> 1) != 0;                      // second tap of a pair
 
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(a.x), 0, (int)a.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_d = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(a.d), 0, (int)a.d_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_d2 = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<bf16_t*>(TFD == 3 ? a.d2 : a.d), 0, TFD == 3 ? (int)a.d2_bytes : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = make_rsrc(a.x, a.x_bytes);
+    const __amdgpu_buffer_rsrc_t rs_d = make_rsrc(a.d, a.d_bytes);
+    const __amdgpu_buffer_rsrc_t rs_d2 = make_rsrc(TFD == 3 ? a.d2 : a.d, TFD == 3 ? a.d2_bytes : 0);
 
     for (int i = threadIdx.x; i < W8_SLAB_FLOATS; i += NW * 64) slab[i] = 0.f;
 
@@ -443,8 +412,10 @@ __global__ __launch_bounds__(NW * 64, 1) void conv_wgrad_c8roll_kernel(const WRo
     float k_sc[8], k_sh[8], k_mu[8], k_is[8], k_a[8], k_c1[8], k_c2[8], k_neg = 0.f;
     bool k_round = false;
     if constexpr (TFD == 3) {
-        k_neg = a.tfd_act == SEGNB_ACT_RELU ? 0.f : (a.tfd_act == SEGNB_ACT_LEAKY ? a.tfd_slope : 1.f);
+        k_neg = act_neg_scale(a.tfd_act, a.tfd_slope);
         k_round = k_neg != 0.f && k_neg != 1.f;
+        // (spelled out, as in conv_wgrad_s1x9_kernel BNA: through a shared loader -- by value, by reference or as a struct --
+        // the compiler orders the kernel's packed operands differently)
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const int c = dc0 + e < a.tfd_Cp ? dc0 + e : 0;
@@ -528,15 +499,13 @@ __global__ __launch_bounds__(NW * 64, 1) void conv_wgrad_c8roll_kernel(const WRo
                 u32x4_t v = ldd[set][m];
                 if constexpr (TFD == 3) {
                     float gq[8], yq[8];
-                    unpack8w(v, gq);
-                    unpack8w(ld2[set][m], yq);
+                    unpack8(v, gq);
+                    unpack8(ld2[set][m], yq);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
-                        const float z = (yq[e] - k_mu[e]) * k_sc[e] + k_sh[e] + 0.f;
-                        float d = gq[e] * 1.f * (z > 0.f ? 1.f : k_neg);
-                        if (k_round) d = __uint_as_float(pack2bf(d, 0.f) << 16);
-                        const float yh = (yq[e] - k_mu[e]) * k_is[e];
-                        gq[e] = k_a[e] * (d - k_c1[e] - yh * k_c2[e]);
+                        float d = bn_dz_elem(gq[e], yq[e], k_mu[e], k_sc[e], k_sh[e], k_neg);
+                        if (k_round) d = __uint_as_float(pack2bf(d, 0.f) << 16);      // (= round_bf16, which compiles to other code here)
+                        gq[e] = bn_apply_elem(yq[e], d, k_mu[e], k_is[e], k_a[e], k_c1[e], k_c2[e]);
                     }
                     const bool ok = i < rows && dcolv[m];
                     v.x = ok ? pack2bf(gq[0], gq[1]) : 0u;
@@ -568,8 +537,8 @@ __global__ __launch_bounds__(NW * 64, 1) void conv_wgrad_c8roll_kernel(const WRo
             bf16x8_t A[COH];
 #pragma unroll
             for (int h = 0; h < COH; ++h) {
-                const bf16x4_t a0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_t*)(uintptr_t)(dro + DS * DROWB + h * 32));
-                const bf16x4_t a1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_t*)(uintptr_t)(dro + DS * DROWB + h * 32 + 16 * DPXB));
+                const bf16x4_t a0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(uintptr_t)(dro + DS * DROWB + h * 32));
+                const bf16x4_t a1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(uintptr_t)(dro + DS * DROWB + h * 32 + 16 * DPXB));
                 A[h] = __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7);
             }
             bf16x8_t B[5];
@@ -578,8 +547,8 @@ __global__ __launch_bounds__(NW * 64, 1) void conv_wgrad_c8roll_kernel(const WRo
                 constexpr int kA = 2 * nb, kB = nb == 4 ? 8 : 2 * nb + 1;
                 constexpr unsigned sA = ((UI + kA / 3) % 4) * W8_XROWB, sB = ((UI + kB / 3) % 4) * W8_XROWB;
                 const unsigned ad = xro[nb] + (sA == sB ? sA : (hi ? sB : sA));
-                const bf16x4_t b0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_t*)(uintptr_t)ad);
-                const bf16x4_t b1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_t*)(uintptr_t)(ad + 16 * 16));
+                const bf16x4_t b0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(uintptr_t)ad);
+                const bf16x4_t b1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(uintptr_t)(ad + 16 * 16));
                 B[nb] = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
             });
 #pragma unroll

@@ -18,15 +18,12 @@
 // Row strides are = 64 or 192 (mod 256) bytes so the four pixel rows a half-wave reads hit disjoint banks.
 // Single LDS buffer + register prefetch of the next iteration; iterations of a block are a contiguous
 // range (split over blocks), results merged with fp32 atomics into the packed [Co][9*Ci] workspace.
-#include "common.h"
+#include "device.h"
 
 #include <cstdlib>
 #include <type_traits>
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4_t;
-typedef __attribute__((address_space(3))) bf16x4_t* lds_bf16x4_ptr;
 
 // 8 consecutive reduction-index (pixel) values of one channel per lane = one MFMA operand fragment:
 // two transposing reads of 4 pixel rows each.  (Keep the bf16-typed builtin + shufflevector: assembling the
@@ -37,7 +34,6 @@ __device__ __forceinline__ bf16x8_t tr_frag(const unsigned char* p, int row4_byt
     return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
-typedef __attribute__((address_space(3))) unsigned char* lds_u8_ptr;
 __device__ __forceinline__ unsigned lds_addr(const void* p) { return (unsigned)(uintptr_t)(lds_u8_ptr)p; }
 
 // The slab loop is written as volatile asm so that the issue order is exactly the program order: the fragments
@@ -100,8 +96,6 @@ struct WgS1Args {
     int gw_s_in, gw_ci_off, gw_Ci, gw_Co, gw_acc;
     int gw_kpos[9];
 };
-
-__device__ __forceinline__ float wg_round_bf16(float v) { return bf16_bits_to_f32(f32_to_bf16_bits(v)); }
 
 // one tap of one slab: wait for B_t of the current fragment set, MFMA, request B_t of the next set
 template <int T, int WAITN, bool MORE, int OB, int SXB>
@@ -339,8 +333,10 @@ __global__ __launch_bounds__((wg_specialised<BCO, BCI, R, WT, FLAT>() ? 512 : 25
     float k_mu[8], k_sc[8], k_sh[8], k_is[8], k_a[8], k_c1[8], k_c2[8], k_neg = 0.f;
     if constexpr (BNA) {
         static_assert(256 % (BCO / 8) == 0, "fixed chunk per thread");
+        k_neg = act_neg_scale(a.bna.act, a.bna.slope);
         const int chk = co0 + (tid % (BCO / 8)) * 8;
-        k_neg = a.bna.act == SEGNB_ACT_RELU ? 0.f : (a.bna.act == SEGNB_ACT_LEAKY ? a.bna.slope : 1.f);
+        // (spelled out, as in conv_wgrad_c8roll_kernel TFD = 3: through a shared loader -- by value, by reference or as a struct --
+        // the compiler orders the kernel's packed operands differently)
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const int cch = chk + e < a.bna.Cp ? chk + e : 0;
@@ -420,18 +416,16 @@ __global__ __launch_bounds__((wg_specialised<BCO, BCI, R, WT, FLAT>() ? 512 : 25
             if (c < YCH && ch < a.Co && ho < a.H && wo < a.W) {
                 if constexpr (BNA) {
                     // dy = BatchNorm-backward apply of (g, y), bit for bit what bn_bwd_apply_kernel (direct form) would have
-                    // stored: round(g act'(z)), then round(a (. - c1 - yhat c2)); the per-channel constants of the thread's
-                    // (fixed) channel chunk were loaded once, before the pixel loop
+                    // stored -- its two expressions, bn_expr.h: round(g act'(z)), then round(a (. - c1 - yhat c2)); the
+                    // per-channel constants of the thread's (fixed) channel chunk were loaded once, before the pixel loop
                     const long long pix = (long long)(n * a.H + ho) * a.W + wo;
                     float gv[8], yv[8], o[8];
                     load8(reinterpret_cast<const bf16_t*>(a.bna.g) + pix * a.bna.ld_g + ch, gv);
                     load8(reinterpret_cast<const bf16_t*>(a.bna.y) + pix * a.bna.ld_y + ch, yv);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
-                        const float z = (yv[e] - k_mu[e]) * k_sc[e] + k_sh[e] + 0.f;
-                        const float d = wg_round_bf16(gv[e] * 1.f * (z > 0.f ? 1.f : k_neg));
-                        const float yh = (yv[e] - k_mu[e]) * k_is[e];
-                        o[e] = k_a[e] * (d - k_c1[e] - yh * k_c2[e]);
+                        const float d = round_bf16(bn_dz_elem(gv[e], yv[e], k_mu[e], k_sc[e], k_sh[e], k_neg));
+                        o[e] = bn_apply_elem(yv[e], d, k_mu[e], k_is[e], k_a[e], k_c1[e], k_c2[e]);
                     }
                     bf16_t packed[8];
                     store8(packed, o);

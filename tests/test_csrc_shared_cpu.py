@@ -1,0 +1,106 @@
+"""The shared expressions and device pieces of csrc/ are written once (csrc/bn_expr.h, csrc/device.h).
+
+Reads only the sources; no GPU, no build.  A kernel that recomputes a BatchNorm or activation pass calls the helpers of bn_expr.h:
+several fusions rest on different kernels computing the same bits for the same expression, and a second spelling of one of
+them is the start of two kernels that disagree.
+
+A site that has to stay spelled out -- routed through the helper the kernel's device code differs from the parent build's
+(tools/devcode_ab.py) -- is an entry of SPELLED_OUT with its reason, and carries a comment in the source.
+"""
+import glob
+import os
+import re
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, 'segmentation-networks-benchmark_amd', 'csrc')
+
+# (file, text of the site) -> why it is not routed through the shared helper
+SPELLED_OUT = {
+    ('wgrad_s1.hip', 'k_c2[e] = a.bna.bcoef[2 * a.bna.Cp + cch];'):
+        'seven-constant load of conv_wgrad_s1x9_kernel BNA: through a shared loader (struct, by value, by reference) the '
+        'compiler swaps the operands of the packed multiplies of the recompute',
+    ('wgrad_roll.hip', 'k_c2[e] = a.tfd_bcoef[2 * a.tfd_Cp + c];'):
+        'seven-constant load of conv_wgrad_c8roll_kernel TFD = 3: the same loader changes its register allocation',
+    ('wgrad_roll.hip', 'd = __uint_as_float(pack2bf(d, 0.f) << 16);'):
+        'bf16 rounding of conv_wgrad_c8roll_kernel TFD = 3 through the packed conversion: round_bf16 compiles to other code there',
+}
+
+
+def sources():
+    out = {}
+    for p in sorted(glob.glob(os.path.join(CSRC, '*.hip')) + glob.glob(os.path.join(CSRC, '*.h'))):
+        with open(p) as f:
+            out[os.path.basename(p)] = f.read()
+    assert len(out) > 20, 'csrc/ not found'
+    return out
+
+
+def files_with(pattern, src=None):
+    src = src or sources()
+    return {n: len(re.findall(pattern, t)) for n, t in src.items() if re.search(pattern, t)}
+
+
+def test_negative_scale_ternary_is_written_once():
+    # act == RELU ? 0 : (act == LEAKY ? slope : 1), under any operand names
+    hits = files_with(r'==\s*SEGNB_ACT_RELU\s*\?\s*0\.f\s*:\s*\(?\s*[\w.\->]+\s*==\s*SEGNB_ACT_LEAKY')
+    assert hits == {'bn_expr.h': 1}, hits
+
+
+def test_dependent_one_liners_are_written_once():
+    src = sources()
+    # the scaled-negative forward of the activation epilogues: v < 0 ? v * neg + 0 : v
+    assert files_with(r'<\s*0\.f\s*\?\s*\w+\s*\*\s*\w+\s*\+\s*0\.f\s*:', src) == {'bn_expr.h': 1}
+    assert files_with(r'if\s*\(\w+\s*<\s*0\.f\)\s*\w+\s*=\s*\w+\s*\*\s*\w+\s*\+\s*0\.f', src) == {}
+    # act'(z) with the hoisted scale: z > 0 ? 1 : neg
+    assert files_with(r'>\s*0\.f\s*\?\s*1\.f\s*:\s*\w*neg\b', src) == {'bn_expr.h': 1}
+    # the written-out bf16 rounding beside round_bf16
+    assert files_with(r'bf16_bits_to_f32\(\s*f32_to_bf16_bits\(', src) == {'common.h': 1}
+
+
+def test_helpers_are_defined_once():
+    src = sources()
+    for name in ('act_neg_scale', 'act_fwd', 'act_grad', 'act_fwd_neg', 'act_grad_neg', 'act_bwd_neg', 'bn_apply_elem',
+                 'bn_fold5_row', 'round_bf16', 'xcd_remap', 'make_rsrc', 'make_rsrc4', 'unpack8', 'relu_pk2bf', 'lds_const8'):
+        hits = files_with(r'__forceinline__\s+[\w:<>]+\s+%s\s*\(' % name, src)
+        assert sum(hits.values()) == 1, (name, hits)
+    # bn_dz_elem: the (act, slope) form and the form with the scale taken once, both in the header
+    assert files_with(r'__forceinline__\s+float\s+bn_dz_elem\s*\(', src) == {'bn_expr.h': 2}
+    for name in ('u32x4_t', 'u32x2_t', 'bf16x4_t', 'f32x4_t', 's16x2_t', 'i32x4_t', 'lds_bf16x4_ptr', 'lds_u8_ptr'):
+        hits = files_with(r'typedef[^;\n]*\b%s;' % name, src)
+        assert hits == {'device.h': 1}, (name, hits)
+
+
+def test_suffixed_copies_are_gone():
+    for name in ('xcd_remap_s1', 'xcd_remap_fd', 'unpack8w', 'relu_pk2bfw', 'lds_const8w', 's16x2w_t', 'wg_round_bf16',
+                 'mu32x4_t', 'lds_bf16x4_t'):
+        assert files_with(r'\b%s\b' % name) == {}, name
+
+
+def test_descriptor_word_is_named_once():
+    assert files_with(r'0x00020000') == {'device.h': 1}
+    # ... and the builtin is wrapped once
+    assert files_with(r'__builtin_amdgcn_make_buffer_rsrc') == {'device.h': 1}
+
+
+def test_host_epilogue_setup_is_written_once():
+    src = sources()
+    # the y extent check with the seven field copies (conv_igemm.hip's general kernel has no descriptor over y: not this block)
+    assert files_with(r'\.bn_y_bytes\s*=', src) == {'common.h': 1}
+    assert files_with(r'\.ep_slope\s*=\s*ep\s*!=', src) == {'common.h': 1}
+    for name in ('take_bn_reduce', 'take_act_epilogue'):
+        assert sum(files_with(r'inline\s+\w+\s+%s\s*\(' % name, src).values()) == 1, name
+
+
+def test_spelled_out_sites_are_the_listed_ones():
+    src = sources()
+    for (name, text), reason in SPELLED_OUT.items():
+        assert reason
+        assert src[name].count(text) == 1, (name, text)
+        # the site says so itself: a comment in front of its loop or on its own line
+        at = src[name].index(text)
+        before = src[name][:at].split('\n')[-13:] + [src[name][at:].split('\n')[0]]
+        assert any('//' in l and ('spelled out' in l or 'round_bf16' in l) for l in before), (name, text)
+    # nothing else restates them: the seven-constant chunk load, and a bf16 rounding through pack2bf
+    loads = files_with(r'\[e\]\s*=\s*[\w.\->]*bcoef\[2\s*\*', src)
+    assert loads == {'wgrad_s1.hip': 1, 'wgrad_roll.hip': 1}, loads
+    assert files_with(r'pack2bf\(\w+,\s*0\.f\)\s*<<\s*16', src) == {'wgrad_roll.hip': 1}
