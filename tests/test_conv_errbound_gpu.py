@@ -10,7 +10,11 @@ compared with `==`: the only check that sees a lost product behind thousands of 
 The shapes are the case tables of test_hip_ops.py (each the smallest that reaches its kernel), with the kernel families forced
 the way the tests there force them.  The head kernels and the element-wise passes round more than once: they are held to a
 float64 oracle in tests/test_ew_oracle_gpu.py (exact operands, `==`) and tests/test_ew_errbound_gpu.py (dense operands, derived
-bound).  The BatchNorm-fused variants of the convolutions (bnapply, bnreduce, tf, upcat, drop) keep the tests of test_hip_ops.py."""
+bound).  The convolutions with an element-wise pass fused into them -- the thin data gradient and its BatchNorm-reduce epilogue,
+the operands recomputed on load (tf), the virtual concat and the segmented / upsum forms of the decoder's first convolution, the
+activation epilogues -- are held to derived bounds and exact probes of their own in tests/test_conv_fused_errbound_gpu.py
+(tests/fused_errbound.py).  Four variants stay covered by bit-equality to a composition whose parts are under an oracle, in
+test_hip_ops.py: the drop epilogue, the activation mask, wgrad_bnapply and the never-stored data gradient (bnsums / bnapply)."""
 import os
 
 import pytest
