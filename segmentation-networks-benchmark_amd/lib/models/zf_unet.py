@@ -21,8 +21,9 @@ from torch import nn
 
 from segnb import _native as nv
 from segnb import convplan as cp
-from segnb.launchlist import Recorder
-from segnb.engine import ConvOp, FlatParams, InputNorm, PackTable, Runtime, Stage, UpCatConvOp, View, pack_input
+from segnb import engine
+from segnb import step
+from segnb.engine import ConvOp, FlatParams, InputNorm, PackTable, ReplayGuard, Runtime, Stage, UpCatConvOp, View, pack_input
 
 ENCODER = ('conv_224', 'conv_112', 'conv_56', 'conv_28', 'conv_14', 'conv_7')
 DECODER = ('up_conv_14', 'up_conv_28', 'up_conv_56', 'up_conv_112', 'up_conv_224')
@@ -71,25 +72,13 @@ class ZF_UNET(nn.Module):
         self.conv_final = nn.Conv2d(f, num_classes, 1)
         self._cfg = dict(dropout=float(dropout_val), bn=bool(batch_norm), cin=input_channels, widths=widths)
         # engine state (not part of state_dict)
-        self.compute_dtype = 'bf16'     # 'bf16' = throughput path, 'f32' = exact-fp32 MFMA parity path
+        self.compute_dtype = 'bf16'     # (step.set_compute_dtype)
         self._engine = None
         self.dropout_override = None    # {block name: fp32 [N, C] multiplier table} -- Dropout2d replay
         self.input_norm = InputNorm()   # applied on the device when forward() is given a uint8 NHWC batch
 
     def set_compute_dtype(self, dtype):
-        if dtype not in ('bf16', 'f32'):
-            raise ValueError("compute dtype must be 'bf16' or 'f32'")
-        if dtype != self.compute_dtype:
-            self.compute_dtype = dtype
-            self._engine = None
-        return self
-
-    def _get_engine(self, device):
-        e = self._engine
-        if e is None or e.rt.device != device:
-            e = _ZFUnetPlan(self, device)
-            self._engine = e
-        return e
+        return step.set_compute_dtype(self, dtype, '_engine')
 
     def forward(self, x):
         """x: float32 [N, C, H, W] (already normalised: what torch_train.py:177 hands the model), or the batch as the
@@ -97,14 +86,11 @@ class ZF_UNET(nn.Module):
         convolution (lib/augmentations.py:452-460 + lib/common.py:70 fused into the kernel)."""
         u8 = x.dtype == torch.uint8
         cdim, hdim, wdim = (3, 1, 2) if u8 else (1, 2, 3)
-        if x.dim() != 4 or x.shape[cdim] != self._cfg['cin']:
-            raise ValueError('expected input [N, %d, H, W] (float) or [N, H, W, %d] (uint8), got %s %s'
-                             % (self._cfg['cin'], self._cfg['cin'], x.dtype, tuple(x.shape)))
+        step.check_channels(x, self._cfg['cin'], cdim)
         if x.shape[hdim] % 32 or x.shape[wdim] % 32:
             raise ValueError('ZF_UNET needs H and W divisible by 32 (five 2x poolings), got %dx%d'
                              % (x.shape[hdim], x.shape[wdim]))
-        eng = self._get_engine(x.device)
-        x = x.detach().contiguous() if u8 else x.detach().contiguous().float()
+        eng, x = step.enter(self, '_engine', x, lambda device: _ZFUnetPlan(self, device))
         if torch.is_grad_enabled():
             # ONE parameter ties the output to the autograd graph (the backward plan writes every .grad itself, as views
             # of the flat gradient buffer, and returns no gradients): 70 fewer edges for autograd to set up and check
@@ -161,14 +147,12 @@ class _ZFUnetPlan(object):
             blk = getattr(module, name)
             seg1 = [(widths[lvl + 1], self.wp[lvl + 1]), (widths[lvl], self.wp[lvl])]
             self._add(name, blk, seg1, True, upcat=self.subpixel)
-        from segnb.engine import ReplayGuard
         self._guard_f, self._guard_b = ReplayGuard('ZF_UNET forward'), ReplayGuard('ZF_UNET backward')
-        self._guard_mode = (None, None)
         self._bufs = {}
         self._pack_tables = {}
         self._retired_tables = []
         self._packed_key = None
-        self._cplans = {}
+        self._cplans = step.StepCache()      # one entry per forward key and per backward key (bench.py reads p[0] of each)
         self.generation = 0
         self.K = module.num_classes
 
@@ -304,7 +288,7 @@ class _ZFUnetPlan(object):
                 unpacks[gi].run()
         else:
             unpacks[gi].run()
-        hook = getattr(self.module, '_grad_ready_hook', None)
+        hook = step.ready_hook(self.module)
         if hook is not None and gi < 2:
             # a recorded launch list is cut where the hook runs, and the hook itself runs OUTSIDE the recording: what it
             # launches (the optimizer update of a bucket behind its all-reduce, DataParallel.fuse_optimizer) is issued by the
@@ -316,7 +300,7 @@ class _ZFUnetPlan(object):
     _last_N = None
 
     def _pack_key(self, H, W, N):
-        return (sum(p._version for p in self.flat.param_list()), self.flat.version, N, H, W, self.flat.flat_p.data_ptr())
+        return step.values_stamp(self.flat) + (N, H, W)
 
     # ---- optimizer.step() of plain SGD fused with this pack (segnb.optim.SGD -> FlatParams.sgd_pack_hook) --------------------------
     _pairs_key = None          # the pack key under which the PAIRED matrices are already those of the current parameters
@@ -404,62 +388,44 @@ class _ZFUnetPlan(object):
             out[n] = t
         return out
 
-    # ---- launch plans (segnb_plan_*): the forward / backward launch lists replayed from C ----------------------------
-    # The first step of a configuration runs eagerly WHILE the library records the ABI calls; later steps replay the list
-    # with one call (the Python launcher needs 10-14 us per launch: 3.6-4.4 ms for the ~300 launches of a step).  Valid
-    # only while every pointer in the list is: same buffers (geometry, flat parameter / gradient storage), same streams,
-    # same mode.  Anything a replay cannot express -- the data-parallel hooks between gradient groups, the bench's
-    # per-launch timer, a uint8 input (host normalisation constants), CPU -- runs the eager path.
-    use_cplan = os.environ.get('SEGNB_CPLAN', '1') != '0'
+    # ---- recorded launch lists (segnb.step) ---------------------------------------------------------------------------
+    # This owner's policy: the FIRST step of a key records, under separate forward and backward keys; a uint8 input (host
+    # normalisation constants) runs the eager path; the bench's per-launch timer is part of the key.  The data-parallel
+    # "gradients ready" hook is host code that must run BETWEEN launches (it starts an all-reduce behind what has been issued
+    # so far), so the recording is cut there (_unpack_group) and the replay calls the hook after the segment that ends there.
+    use_cplan = step.USE_LISTS
 
     def _cplan_key(self, kind, N, H, W, train, need_grad, drop):
-        from segnb import engine
-        rt = self.rt
-        if not self.use_cplan or rt.device.type != 'cuda':
-            return None
-        side = rt.side_stream()
-        return (kind, N, H, W, bool(train), bool(need_grad), tuple(n for n in ENCODER + DECODER if drop[n] is not None),
-                getattr(self.module, '_grad_ready_hook', None) is not None,
-                id(engine.TIMER),                     # (its event records are part of the list recorded under it)
-                rt.stream, side.cuda_stream if side is not None else 0, self.flat.flat_p.data_ptr(),
-                self.flat.flat_g.data_ptr(), tuple(p.data_ptr() for p in self.flat.buffer_list()))
+        shared = step.list_key(self.rt, self.flat, step.ready_hook(self.module), self.use_cplan)
+        return shared and (kind, N, H, W, bool(train), bool(need_grad), tuple(n for n in ENCODER + DECODER if drop[n] is not None),
+                           id(engine.TIMER)) + shared     # (the timer's event records are part of the list recorded under it)
 
-    # ---- recorded launch lists (segnb.launchlist) -------------------------------------------------------------------
-    # The data-parallel "gradients ready" hook is host code that must run BETWEEN launches (it starts an all-reduce behind
-    # what has been issued so far), so the recording is cut there (_unpack_group) and the replay calls the hook after the
-    # segment that ends at the cut.
     _rec = None           # the Recorder of the step being recorded
 
     @contextlib.contextmanager
-    def _recording(self, ckey):
-        """Record the launches of the body as the list of configuration ckey (None: the body runs eagerly).  A body that
-        raises (e.g. an allocation failure the caller catches) or makes a call that cannot be replayed leaves the
-        configuration remembered as eager: never recorded again."""
-        if ckey is None:
-            yield
-            return
-        from segnb import engine
-        if engine.TIMER is not None:
-            engine.TIMER.persistent = True
-        with Recorder() as rec:
-            self._rec, lst = rec, None       # (_unpack_group pauses it around the data-parallel hook)
+    def _recording(self, ent, kind, guarded, ckey):
+        """Record the launches of the body as the `kind` list of entry ent (None, or eager for good: the body just runs)."""
+        with self._cplans.recording(ent, kind) as self._rec:      # (_unpack_group pauses it around the data-parallel hook)
+            rec = self._rec
+            if rec is not None and engine.TIMER is not None:
+                engine.TIMER.persistent = True
             try:
                 yield
-                lst = rec.finish()
+                lst = rec.finish() if rec is not None else None
+                if lst:
+                    ent.update({kind: lst, 'stages': self._stage_state(), 'launches': lst.launches, 'state': 'ready'})
+                    guarded.key, guarded.mode = ckey, 'record'
             finally:
                 self._rec = None
-                self._cplans[ckey] = (lst, self._stage_state(), lst.launches if lst else 0)
-        if lst:
-            self._guard_mode = (ckey, 'record')
 
     def _plan_replay(self, plan, H=None, W=None):
         def ready(mark):
-            hook = getattr(self.module, '_grad_ready_hook', None)
+            hook = step.ready_hook(self.module)
             if hook is not None:
                 gi, on_side = mark
                 hook(self.flat, self._tables(H, W)[3][gi], (self.rt.side_stream(),) if on_side else ())
         plan[0].replay(ready)
-        self._restore_stage_state(plan[1])
+        self._restore_stage_state(plan['stages'])
 
     def _stage_state(self):
         return [(st, st.bnl.stats_left, st.bnl.fused_fwd, getattr(st, '_saved', None))
@@ -472,15 +438,10 @@ class _ZFUnetPlan(object):
 
     # ---- forward ---------------------------------------------------------------------------------------
     def forward(self, x, train, need_grad):
-        # (SEGNB_REPLAY_GUARD=1: a replayed forward must execute the launches of the forward that recorded its lists)
-        # The census starts where the two paths part (the list look-up): what precedes it -- Dropout2d tables, the weight pack when
-        # the parameters changed, the gradient-buffer clear, the input pack -- is the same host code either way
-        self._guard_mode, self._guard_active = (None, None), False
-        out = self._forward(x, train, need_grad)
-        self._guard_f.end(self._guard_active, *self._guard_mode)
-        return out
+        with self._guard_f.step() as guarded:      # (SEGNB_REPLAY_GUARD=1)
+            return self._forward(x, train, need_grad, guarded)
 
-    def _forward(self, x, train, need_grad):
+    def _forward(self, x, train, need_grad, guarded):
         rt = self.rt
         self.flat.ensure(rt.device)
         u8 = x.dtype == torch.uint8
@@ -499,7 +460,7 @@ class _ZFUnetPlan(object):
         hf = self._head_fusable(train, need_grad)
         self._last_head_fused = hf
         ckey = None if u8 else self._cplan_key('fwd', N, H, W, train, need_grad, drop)
-        first = None
+        ent = first = None
         if u8 and self.stages[ENCODER[0]][0].conv.u8_direct_ok(N, H, W, self.wp[0]):
             first = (x, self.module.input_norm)          # the first convolution reads the image itself
         else:
@@ -513,18 +474,16 @@ class _ZFUnetPlan(object):
                     if st.bn is not None and train and st.bnl.stats_left:
                         st.bnl.stats.zero_()
                         st.bnl.stats_left = False
-            plan = self._cplans.get(ckey)
-            self._guard_active = self._guard_f.begin()
-            if plan is not None and plan[0] is not None:
-                self._guard_mode = (ckey, 'replay')
-                self._plan_replay(plan)
+            ent = self._cplans.entry(ckey)
+            guarded.begin()
+            if ent['state'] == 'ready':
+                guarded.key, guarded.mode = ckey, 'replay'
+                self._plan_replay(ent)
                 self._last = (N, H, W) if need_grad else None
                 self._last_train = bool(train)
                 self.generation += 1
                 return self._head(b, N, H, W, hf)
-            if plan is not None:
-                ckey = None                               # recorded before and found not replayable: eager
-        with self._recording(ckey):
+        with self._recording(ent, 'fwd', guarded, ckey):
             wp = self.wp
             cur = b['x']
             for i, name in enumerate(ENCODER):
@@ -601,49 +560,29 @@ class _ZFUnetPlan(object):
 
     # ---- backward --------------------------------------------------------------------------------------
     def backward(self, dlogits):
-        self._guard_mode, self._guard_active = (None, None), False
-        out = self._backward(dlogits)
-        self._guard_b.end(self._guard_active, *self._guard_mode)
-        return out
-
-    def _backward(self, dlogits):
-        rt, flat, wp = self.rt, self.flat, self.wp
         if self._last is None:
             raise RuntimeError('backward without a grad-enabled forward')
-        if not self._last_train and self.module._cfg['bn']:
-            # the backward plan implements the TRAINING-mode BatchNorm gradient (batch statistics); through an eval-mode
-            # forward (running statistics) BatchNorm is a plain affine map and that formula is wrong
-            raise RuntimeError('backward through an eval-mode forward is not supported: BatchNorm gradients are '
-                               'implemented for training mode (call model.train(), or run the forward under no_grad)')
         N, H, W = self._last
-        b = self.buffers(N, H, W)
-        accumulate_in_place = flat.begin_backward()
-        with rt.weight_grads(store=not accumulate_in_place):     # (stored or added: ConvOp._arm_target; part of the list's key)
-            return self._backward_lists(dlogits, b, N, H, W, accumulate_in_place)
+        with self._guard_b.step() as guarded:
+            step.run_backward(self.module, self.rt, self.flat, self._last_train, lambda: self.module._cfg['bn'],
+                              lambda acc: self._backward_lists(dlogits, self.buffers(N, H, W), N, H, W, acc, guarded))
 
-    def _backward_lists(self, dlogits, b, N, H, W, accumulate_in_place):
+    def _backward_lists(self, dlogits, b, N, H, W, accumulate_in_place, guarded):
         rt, flat, wp = self.rt, self.flat, self.wp
         drop_now = {n: self.stages[n][1]._saved[2] if self.stages[n][1]._saved is not None else None for n in ENCODER + DECODER}
-        ckey = self._cplan_key('bwd', N, H, W, True, True, drop_now)
+        ckey, ent = self._cplan_key('bwd', N, H, W, True, True, drop_now), None
         if ckey is not None:
+            # (weight gradients stored or added: ConvOp._arm_target)
             ckey = ckey + (bool(getattr(self, '_last_head_fused', False)), bool(accumulate_in_place))
-        if ckey is not None:
-            din = b['dlogits_in']
-            if dlogits.data_ptr() != din.data_ptr():
-                din.copy_(dlogits)                        # (a loss that did not write into the registered buffer)
-            dlogits = din
-            plan = self._cplans.get(ckey)
-            self._guard_active = self._guard_b.begin()
-            if plan is not None and plan[0] is not None:
-                self._guard_mode = (ckey, 'replay')
-                self._plan_replay(plan, H, W)
+            dlogits = step.stage_dlogits(dlogits, b['dlogits_in'])
+            ent = self._cplans.entry(ckey)
+            guarded.begin()
+            if ent['state'] == 'ready':
+                guarded.key, guarded.mode = ckey, 'replay'
+                self._plan_replay(ent, H, W)
                 rt._side_busy = False
-                self._after_backward()
-                flat.publish_grads(accumulate_in_place)
-                return [None] * len(flat._off)
-            if plan is not None:
-                ckey = None
-        with self._recording(ckey):
+                return
+        with self._recording(ent, 'bwd', guarded, ckey):
             if self._dg_pack_on_side and rt.side_stream() is not None:
                 # the data gradients' matrices were packed on the side stream (recorded: a replayed list waits too)
                 nv.call('segnb_stream_join', rt.stream, rt.side_stream().cuda_stream)
@@ -691,13 +630,3 @@ class _ZFUnetPlan(object):
                 s1.backward(flat, g_direct=b['da1_%d' % i], dx=(b['dp_%d' % i] if i > 0 else None), reduced=red)
             rt.join_side()                        # the weight gradients ran on the side stream
             self._tables(H, W)[2][2].run()       # the remaining packed weight-gradient workspaces -> flat gradient buffer
-        self._after_backward()
-        # gradients live in ONE flat buffer; parameter.grad tensors are views of it (installed here, not
-        # returned through autograd, so they never get cloned and a flat optimizer / all-reduce can run)
-        flat.publish_grads(accumulate_in_place)
-        return [None] * len(flat._off)
-
-    def _after_backward(self):
-        hook = getattr(self.module, '_grad_sync_hook', None)
-        if hook is not None:
-            hook(self.flat)

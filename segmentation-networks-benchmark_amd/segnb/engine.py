@@ -17,7 +17,6 @@ from . import convplan as cp
 from .bnpass import BN_EPS, BN_MOMENTUM, FUSE_FINALIZE, BnLayer, module_params
 
 
-
 class KernelTimer(object):
     """Optional per-launch timing of the convolution kernels with HIP events on the launch stream
     (bench.py's live roofline measurement).  Off unless bench.py installs one in ``engine.TIMER``."""
@@ -96,23 +95,31 @@ class ReplayGuard(object):
         self.ref = {}
         self.checked = 0
 
-    def begin(self):
+    @contextlib.contextmanager
+    def step(self):
+        """Brackets one forward / backward (they do not nest): the body calls begin() where the recording and the replaying path
+        part (the list look-up: what precedes it is the same host code either way), then sets .key and .mode = 'record' (this
+        step recorded the lists of key) or 'replay' (it ran from them).  A step that says neither, or raises, is not compared."""
+        self.active, self.key, self.mode = False, None, None
+        yield self
+        if self.active:
+            self._end()
+
+    def begin(self):          # (the census starts here)
         if not self.enabled or nv.has_test_backend():
-            return False
+            return
         if not ReplayGuard._on:
             nv.call('segnb_tune', b'call_census', 1)       # (process-wide switch: never inside a recording -- segnb_tune is refused there)
             ReplayGuard._on = True
         nv.census_read()
-        return True
+        self.active = True
 
-    def end(self, active, key, mode):
-        """mode: 'record' (this step recorded the lists of `key`), 'replay' (it ran from them) or anything else (eager: ignored)"""
-        if not active:
-            return
+    def _end(self):
+        key = self.key
         c = {k: v for k, v in nv.census_read().items() if k not in self.IGNORE}
-        if mode == 'record':
+        if self.mode == 'record':
             self.ref[key] = c
-        elif mode == 'replay' and key in self.ref:
+        elif self.mode == 'replay' and key in self.ref:
             ref = self.ref[key]
             if c != ref:
                 diff = ['%s: recorded step %d, replayed step %d' % (k, ref.get(k, 0), c.get(k, 0))

@@ -21,9 +21,10 @@ from torch import nn
 
 from . import _native as nv
 from . import convplan as cp
+from . import engine
+from . import step
 from .bnpass import FUSE_FINALIZE, BnLayer, module_params, stats_into
-from .engine import ConvOp, FlatParams, InputNorm, PackTable, Runtime, View, pack_input, vld, vptr
-from .launchlist import Recorder
+from .engine import ConvOp, FlatParams, InputNorm, PackTable, ReplayGuard, Runtime, View, pack_input, vld, vptr
 
 
 class Act(object):
@@ -116,7 +117,7 @@ class Tape(object):
         self._zero_each_step = {}      # key -> tensor cleared by begin() (statistics tables several layers read: nobody's backward owns them)
         self._cuts = {}
         self._drop_sites, self._drop_pools = {}, {}
-        self.plans = {}            # recorded launch lists (HipNet._run / _run_backward)
+        self.plans = step.StepCache()      # recorded launch lists (HipNet._run / _run_backward; bench.py reads .get('state'))
         # forward statistics that segnb_bn_fwd_fused left for this step's backward to clear (segnb_bn_bwd_apply_fused*):
         # if that backward never runs, begin() clears them before the next forward accumulates on top
         self.fused_stats, self.stats_pending = [], False
@@ -155,7 +156,7 @@ class Tape(object):
         self.generation = getattr(self, 'generation', 0) + 1
         # weight-packing generation: every ConvOp plan (one per input size) remembers the generation it was packed at,
         # so a plan first used -- or last used -- under other parameter values is (re)packed on its next use
-        key = (sum(p._version for p in self.flat.param_list()), self.flat.version, self.flat.flat_p.data_ptr())
+        key = step.values_stamp(self.flat)
         if key != self.pack_key and self.convs:
             # parameters changed since the last pack: all known plans in one launch (plans first met later in this
             # forward pack themselves in conv_unit and join the table for the next step)
@@ -316,10 +317,7 @@ class Tape(object):
     CUT_FRACTIONS = (2.0 / 3.0, 1.0 / 3.0)
 
     def _ready_hook(self):
-        hook = getattr(self.module, '_grad_ready_hook', None)
-        if hook is None or not getattr(getattr(hook, '__self__', None), 'active', True):
-            return None
-        return hook
+        return step.ready_hook(self.module, only_active=True)
 
     def _learn_cuts(self, nback, frontiers):
         cuts, k = {}, 0
@@ -1127,183 +1125,110 @@ class HipNet(nn.Module):
         self._tape = None
         self._in_channels = in_channels
         self.input_norm = InputNorm()           # for uint8 NHWC batches (lib/augmentations.py:452-460 on the device)
+        self._replay_guards = tuple(ReplayGuard('%s %s' % (type(self).__name__, w)) for w in ('forward', 'backward'))
 
     def set_compute_dtype(self, dtype):
-        if dtype not in ('bf16', 'f32'):
-            raise ValueError("compute dtype must be 'bf16' or 'f32'")
-        if dtype != self.compute_dtype:
-            self.compute_dtype = dtype
-            self._tape = None
-        return self
+        return step.set_compute_dtype(self, dtype, '_tape')
 
     def _check_input(self, x):
-        cdim = 3 if x.dtype == torch.uint8 else 1
-        if x.dim() != 4 or x.shape[cdim] != self._in_channels:
-            raise ValueError('expected input [N, %d, H, W] (float) or [N, H, W, %d] (uint8), got %s %s'
-                             % (self._in_channels, self._in_channels, x.dtype, tuple(x.shape)))
+        step.check_channels(x, self._in_channels, 3 if x.dtype == torch.uint8 else 1)
 
     def forward(self, x):
         """x: float32 [N, C, H, W], or uint8 [N, H, W, C] normalised on the device with ``self.input_norm``."""
         if x.dtype == torch.uint8:              # the shape checks of the subclasses speak NCHW
             self._check_input(torch.empty((x.shape[0], x.shape[3], x.shape[1], x.shape[2]), device='meta'))
-            x = x.detach().contiguous()
         else:
             self._check_input(x)
-            x = x.detach().contiguous().float()
-        if self._tape is None or self._tape.rt.device != x.device:
-            self._tape = Tape(self, x.device, self.compute_dtype)
+        tape, x = step.enter(self, '_tape', x, lambda device: Tape(self, device, self.compute_dtype))
         if torch.is_grad_enabled():
-            flat = getattr(getattr(self, '_tape', None), 'flat', None)
-            params = flat.param_list() if flat is not None else list(self.parameters())
+            params = tape.flat.param_list()
             if any(p.requires_grad for p in params):
                 return _NetFn.apply(self, x, *params)
         return self._run(x, False)
 
-    # ---- recorded launch lists (segnb_plan_*: include/segnb_hip.h) --------------------------------------------------------
-    # The graphs are static: the SECOND step of a (geometry, mode) runs the Python build once more while the library records
-    # every ABI call it makes (the first one allocated buffers and packed weights with calls that are not replayable); from
-    # the third step on the forward and the backward are one replayed list each -- 3-4 us of host time per launch instead
-    # of the 10-14 us of a ctypes call, which is what bounds FCDenseNet103's ~2250 launches of ~10 us.  Whatever varies
-    # between steps enters through persistent buffers: the input batch and the logits gradient are copied into them, the
-    # dropout pools are redrawn in Tape.begin, BatchNorm statistics are cleared by the kernels that consume them.
-    use_cplan = os.environ.get('SEGNB_CPLAN', '1') != '0'
+    # ---- recorded launch lists (segnb.step) ---------------------------------------------------------------------------------
+    # This owner's policy: the graphs are static, and the SECOND step of a (geometry, mode) records (the first one allocated
+    # buffers and packed weights with calls that are not replayable); from the third step on the forward and the backward are
+    # one replayed list each (what bounds FCDenseNet103's ~2250 launches of ~10 us).  The dropout pools are redrawn in
+    # Tape.begin, BatchNorm statistics are cleared by the kernels that consume them.  No lists under a KernelTimer.
+    use_cplan = step.USE_LISTS
 
     def _plan_key(self, x, need_grad, grads_alias):
         """grads_alias: FlatParams.grads_alias() at this forward (None without grad).  A backward may only meet it turned False
         (.grad re-aliases flat_g in publish_grads, at the end of a backward), so a list recorded storing its weight gradients
         (Runtime.weight_grads) always replays on a cleared buffer; one recorded adding them is right either way."""
-        from . import engine
         tape = self._tape
-        rt = tape.rt
-        if not self.use_cplan or rt.device.type != 'cuda' or engine.TIMER is not None:
-            return None
-        side = rt.side_stream()
-        return (tuple(x.shape), x.dtype, bool(self.training), bool(need_grad), grads_alias, rt.stream,
-                side.cuda_stream if side is not None else 0,
-                tape.flat.flat_p.data_ptr(), tape.flat.flat_g.data_ptr(), tuple(b.data_ptr() for b in tape.flat.buffer_list()),
-                tuple(sorted((p, pool['used']) for p, pool in tape._drop_pools.items())) if self.training else (),
-                tape._ready_hook() is not None)
-
-    @staticmethod
-    def _plan_drop(ent):
-        for k in ('fwd', 'bwd'):
-            lst = ent.pop(k, None)
-            if lst is not None:
-                lst.destroy()
-
-    @staticmethod
-    @contextlib.contextmanager
-    def _recording(ent, kind):
-        """Record the launches of the body (yields the Recorder), which stores its list as ent[kind].  A step that raises, or
-        whose list cannot be replayed, stores none: the entry is then 'eager' for good and its lists are freed."""
-        with Recorder() as rec:
-            try:
-                yield rec
-            finally:
-                if ent.get(kind) is None:
-                    HipNet._plan_drop(ent)
-                    ent['state'] = 'eager'
+        shared = step.list_key(tape.rt, tape.flat, tape._ready_hook(), self.use_cplan and engine.TIMER is None)
+        pools = tuple(sorted((p, pool['used']) for p, pool in tape._drop_pools.items())) if self.training else ()
+        return shared and (tuple(x.shape), x.dtype, bool(self.training), bool(need_grad), grads_alias, pools) + shared
 
     def _guards(self):
-        g = getattr(self, '_replay_guards', None)
-        if g is None:
-            from .engine import ReplayGuard
-            g = self._replay_guards = (ReplayGuard(type(self).__name__ + ' forward'), ReplayGuard(type(self).__name__ + ' backward'))
-        return g
+        return self._replay_guards
 
     def _run(self, x, need_grad):
-        # (SEGNB_REPLAY_GUARD=1: a replayed forward must execute the launches of the forward that recorded its list)
-        # the census starts where the two paths part (the list look-up): Tape.begin -- dropout pools, the weight pack when the
-        # parameters changed -- the gradient-buffer clear and the input pack are the same host code either way
-        self._guard_mode, self._guard_active = (None, None), False
-        out = self._run_(x, need_grad)
-        self._guards()[0].end(self._guard_active, *self._guard_mode)
-        return out
-
-    def _run_(self, x, need_grad):
-        tape = self._tape
-        tape.begin(self.training, need_grad)
-        self._grads_alias = tape.flat.grads_alias() if need_grad else None
-        if self.training and need_grad:
-            # the coming backward's gradient-buffer clear, on the side stream beside the forward
-            tape.flat.prezero(tape.rt, aliased=self._grads_alias)
-        if x.dtype == torch.uint8:
-            N, H, W, C = x.shape
-        else:
-            N, C, H, W = x.shape
-        key = self._plan_key(x, need_grad, self._grads_alias)
-        ent, recording = None, contextlib.nullcontext()
-        self._plan_live = None
-        # the batch enters through ONE launch outside the recorded list (it reads the caller's tensor, whatever its address):
-        # NCHW fp32 / NHWC uint8 -> the padded NHWC buffer the list's first convolution reads
-        cin_p = cp.pad8(C)
-        xin = tape.view('input', N, H, W, cin_p)
-        pack_input(tape.rt, x, xin, getattr(self, 'input_norm', None))
-        if key is not None:
-            ent = tape.plans.get(key)
-            self._guard_active = self._guards()[0].begin()
-            if ent is None:
-                ent = tape.plans[key] = {'state': 'seen'}                  # first step of this key: eager
+        with self._guards()[0].step() as guarded:      # (SEGNB_REPLAY_GUARD=1)
+            tape = self._tape
+            tape.begin(self.training, need_grad)
+            self._grads_alias = tape.flat.grads_alias() if need_grad else None
+            if self.training and need_grad:
+                # the coming backward's gradient-buffer clear, on the side stream beside the forward
+                tape.flat.prezero(tape.rt, aliased=self._grads_alias)
+            if x.dtype == torch.uint8:
+                N, H, W, C = x.shape
             else:
+                N, C, H, W = x.shape
+            key = self._plan_key(x, need_grad, self._grads_alias)
+            ent = rec_ent = self._plan_live = None
+            # the batch enters through ONE launch outside the recorded list (it reads the caller's tensor, whatever its address):
+            # NCHW fp32 / NHWC uint8 -> the padded NHWC buffer the list's first convolution reads
+            xin = tape.view('input', N, H, W, cp.pad8(C))
+            pack_input(tape.rt, x, xin, getattr(self, 'input_norm', None))
+            if key is not None:
+                ent = tape.plans.entry(key)
+                guarded.begin()
                 if ent['state'] == 'ready':
-                    self._guard_mode = (key, 'replay')
+                    guarded.key, guarded.mode = key, 'replay'
                     ent['fwd'].replay()
                     tape.back = []
                     tape.fused_stats = ent['fused_stats']
                     tape.stats_pending = bool(tape.fused_stats)
                     self._plan_live = ent if need_grad else None
                     return ent['logits'].clone()
-                if ent['state'] == 'seen' or (ent['state'] == 'fwd' and need_grad):
-                    self._plan_drop(ent)                                    # (a recorded forward whose backward never ran)
-                    recording = self._recording(ent, 'fwd')
-        self._dlogits = [None]
-        tape.unplannable = False
-        with recording as rec:
-            logits = self._build(tape, Act(xin, needs_grad=False), self._dlogits)
-            tape.stats_pending = bool(tape.fused_stats)
-            lst = rec.finish() if rec is not None else None
-            if lst:
-                ent.update(fwd=lst, logits=logits, nfwd=lst.launches, state='fwd' if need_grad else 'ready',
-                           fused_stats=list(tape.fused_stats))
-                self._guard_mode = (key, 'record')
-                self._plan_live = ent if need_grad else None
-        return logits.clone()
+                if ent['state'] == 'new':
+                    ent['state'] = 'seen'                                       # first step of this key: eager
+                elif ent['state'] == 'seen' or (ent['state'] == 'fwd' and need_grad):
+                    ent.drop()                                                  # (a recorded forward whose backward never ran)
+                    rec_ent = ent
+            self._dlogits = [None]
+            tape.unplannable = False
+            with tape.plans.recording(rec_ent, 'fwd') as rec:
+                logits = self._build(tape, Act(xin, needs_grad=False), self._dlogits)
+                tape.stats_pending = bool(tape.fused_stats)
+                lst = rec.finish() if rec is not None else None
+                if lst:
+                    ent.update(fwd=lst, logits=logits, nfwd=lst.launches, state='fwd' if need_grad else 'ready',
+                               fused_stats=list(tape.fused_stats))
+                    guarded.key, guarded.mode = key, 'record'
+                    self._plan_live = ent if need_grad else None
+            return logits.clone()
 
     def _run_backward(self, dlogits):
-        self._guard_mode, self._guard_active = (None, None), False
-        out = self._run_backward_(dlogits)
-        self._guards()[1].end(self._guard_active, *self._guard_mode)
-        return out
-
-    def _run_backward_(self, dlogits):
         tape = self._tape
-        if not tape.train and any(isinstance(m, nn.modules.batchnorm._BatchNorm) or type(m).__name__ == 'InPlaceABN'
-                                  for m in tape.flat.module_list()):
-            raise RuntimeError('backward through an eval-mode forward is not supported: BatchNorm gradients are '
-                               'implemented for training mode (call model.train(), or run the forward under no_grad)')
-        ent = getattr(self, '_plan_live', None)
-        self._plan_live = None
-        acc = tape.flat.begin_backward()
-        # directly delivered weight gradients are STORED when the gradient buffer was just cleared, ADDED when gradients accumulate in
-        # place -- and added when the forward saw .grad aliasing flat_g, so that the list this backward may record matches its key
-        # (_plan_key)
-        with tape.rt.weight_grads(store=not acc and not self._grads_alias):
-            self._backward_lists(tape, ent, dlogits)
-        hook = getattr(self, '_grad_sync_hook', None)
-        if hook is not None:
-            hook(tape.flat)
-        tape.flat.publish_grads(acc)
+        ent, self._plan_live = getattr(self, '_plan_live', None), None
+        with self._guards()[1].step() as guarded:
+            # (weight gradients are also added when the forward saw .grad aliasing flat_g, so that the list this backward may
+            # record matches its key: _plan_key)
+            step.run_backward(self, tape.rt, tape.flat, tape.train,
+                              lambda: any(isinstance(m, nn.modules.batchnorm._BatchNorm) or type(m).__name__ == 'InPlaceABN'
+                                          for m in tape.flat.module_list()),
+                              lambda acc: self._backward_lists(tape, ent, dlogits, guarded), aliased=self._grads_alias)
 
-    def _backward_lists(self, tape, ent, dlogits):
+    def _backward_lists(self, tape, ent, dlogits, guarded):
         if ent is not None:
-            din = ent.get('dlogits_in')
-            if din is None:
-                din = ent['dlogits_in'] = torch.empty_like(dlogits)
-            din.copy_(dlogits)                                              # (autograd hands over a new tensor every step)
-            dlogits = din
-        self._guard_active = self._guards()[1].begin() if ent is not None else False
+            dlogits = ent['dlogits_in'] = step.stage_dlogits(dlogits, ent.get('dlogits_in'))
+            guarded.begin()
         if ent is not None and ent['state'] == 'ready':
-            self._guard_mode = (id(ent), 'replay')
+            guarded.key, guarded.mode = id(ent), 'replay'
             ent['bwd'].replay(lambda cut: tape.cut_host(*cut))      # host work between two segments, as recorded
             tape.rt._side_busy = False
             tape.stats_pending = False
@@ -1312,7 +1237,7 @@ class HipNet(nn.Module):
         else:
             self._dlogits[0] = dlogits
             if ent is not None and ent['state'] == 'fwd':
-                with self._recording(ent, 'bwd') as rec:
+                with tape.plans.recording(ent, 'bwd') as rec:
                     def cut(do):             # the partial unpack and the hook run OUTSIDE the recording; the replay repeats them
                         with rec.pause() as seg:
                             seg.mark = do()
@@ -1322,7 +1247,7 @@ class HipNet(nn.Module):
                         lst.destroy()
                     elif lst:
                         ent.update(bwd=lst, nbwd=lst.launches, state='ready')
-                        self._guard_mode = (id(ent), 'record')
+                        guarded.key, guarded.mode = id(ent), 'record'
             else:
                 tape.run_closures(join=False)
             table = tape.finish()                                           # (7x7 / strided jobs take host tap arrays: eager)

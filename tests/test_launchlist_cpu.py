@@ -7,48 +7,7 @@ import pytest
 from segnb import _native as nv
 from segnb.launchlist import LaunchList, Recorder
 
-
-class FakePlans(object):
-    """Hands out numbered handles; answers NULL for the segments (0-based, in the order they end) listed in `refuse`."""
-
-    def __init__(self, refuse=()):
-        self.refuse = set(refuse)
-        self.open, self.ended, self.stray_ends, self.live, self.runs = 0, 0, 0, set(), []
-
-    def segnb_plan_begin(self):
-        assert self.open == 0, 'segnb_plan_begin while a recording is open'
-        self.open += 1
-        return 0
-
-    def segnb_plan_end(self, handle_out, nops_out):
-        if self.open == 0:
-            self.stray_ends += 1              # (nv.plan_record_abort swallows this error: counted, _clean is the judge)
-            return 1                          # "no plan is being recorded"
-        self.open -= 1
-        k, self.ended = self.ended, self.ended + 1
-        nops_out._obj.value = 10 + k
-        if k in self.refuse:
-            handle_out._obj.value = None
-        else:
-            handle_out._obj.value = 100 + k
-            self.live.add(100 + k)
-        return 0
-
-    def segnb_plan_run(self, handle):
-        if handle not in self.live or self.open:
-            return 1
-        self.runs.append(handle)
-        return 0
-
-    def segnb_plan_destroy(self, handle):
-        if handle not in self.live:
-            return 1                          # freed twice, or never handed out
-        self.live.remove(handle)
-        return 0
-
-    def launch(self):
-        """stands for any recordable ABI call of the step"""
-        return 0
+from fake_plans import FakePlans, on_emulator
 
 
 @pytest.fixture
@@ -174,10 +133,7 @@ def _zf_unet_on_fake_lists(hook):
     import torch
     from oracle import abi_emulator
     from lib.models.zf_unet import ZF_UNET
-    be, fake = abi_emulator.AbiEmulator(), FakePlans()
-    for name in ('segnb_plan_begin', 'segnb_plan_end', 'segnb_plan_run', 'segnb_plan_destroy'):
-        setattr(be, name, getattr(fake, name))
-    nv.set_backend_for_testing(be)
+    fake = on_emulator(abi_emulator.AbiEmulator())
     torch.manual_seed(0)
     m = ZF_UNET(dropout_val=0.0, filters=4).set_compute_dtype('f32').train()
     m._grad_ready_hook = lambda flat, lo, producers: hook(fake, lo, producers)
@@ -200,7 +156,7 @@ def test_zf_unet_cuts_its_backward_list_at_the_hook_and_replays_it():
         m(x).sum().backward()                 # recorded
         assert eng._rec is None and len(calls) == 2 and all(c[0] == 0 for c in calls)    # the hook ran outside the recording
         bwd = [p for k, p in eng._cplans.items() if k[1] == 'bwd']
-        assert len(bwd) == 1 and bwd[0][0] and len(bwd[0][0]._segments) == 3 and bwd[0][2] == bwd[0][0].launches
+        assert len(bwd) == 1 and bwd[0][0] and len(bwd[0][0]._segments) == 3 and bwd[0]['launches'] == bwd[0][0].launches
         assert _clean(fake, _live_of(eng)) and len(fake.live) == 4
         recorded, fake.runs = list(calls), []
         del calls[:]
@@ -233,10 +189,7 @@ def _unet16_on_fake_lists(hook):
     import torch
     from oracle import abi_emulator
     from lib.models.unet16 import UNet16
-    be, fake = abi_emulator.AbiEmulator(), FakePlans()
-    for name in ('segnb_plan_begin', 'segnb_plan_end', 'segnb_plan_run', 'segnb_plan_destroy'):
-        setattr(be, name, getattr(fake, name))
-    nv.set_backend_for_testing(be)
+    fake = on_emulator(abi_emulator.AbiEmulator())
     torch.manual_seed(0)
     m = UNet16(num_filters=4).set_compute_dtype('f32').train()
     m._grad_ready_hook = lambda flat, lo, producers: hook(fake, lo, producers)

@@ -1,11 +1,14 @@
 """debug tool: the ABI traffic of one training step on the ABI emulator (CPU), as text that two checkouts can diff.
 
     python tools/abi_call_trace.py CASE [CHECKOUT]      CASE: zf_f32 zf_f32_segw zf_bf16 zf_bf16_segw zf_bf16_segf
-                                                              linknet tiramisu unet16 gcn34 (bf16), or all
+                                                              linknet tiramisu unet16 gcn34 squeezenet (bf16), or all
     further cases (the BatchNorm branches a default training step never takes): zf_bf16_drop (Dropout2d 0.2), zf_bf16_src
     (Stage.recompute_dz_min_mb tiny), zf_bf16_headdz (Stage.head_dz_recompute off), tiramisu_nocache (cache_prefix_stats off),
     every case above + _nofuse (BatchNorm finalize not fused), zf_bf16_eval / linknet_eval (eval-mode forward under no_grad),
-    abn (InPlaceABN on its own: forward + backward, training and eval mode, both affine forms)
+    abn (InPlaceABN on its own: forward + backward, training and eval mode, both affine forms),
+    zf_bf16_lists / unet16_lists / linknet_lists: three consecutive training steps with the recording path forced on (the plan
+    entry points are tests/fake_plans.py's; segnb_plan_* calls are printed too, and a `--- step N` line between steps): what
+    the recording step and the replayed step execute NEXT TO the lists
 
 CHECKOUT is the repository root whose segnb.engine is traced (default: this one), so the same file traces a parent's
 checkout.  Every nv.call / nv.query is printed in order; a tensor address becomes (ordinal of its storage by first
@@ -17,9 +20,9 @@ import gc
 import os
 import sys
 
-BASE = ('zf_f32', 'zf_f32_segw', 'zf_bf16', 'zf_bf16_segw', 'zf_bf16_segf', 'linknet', 'tiramisu', 'unet16', 'gcn34')
+BASE = ('zf_f32', 'zf_f32_segw', 'zf_bf16', 'zf_bf16_segw', 'zf_bf16_segf', 'linknet', 'tiramisu', 'unet16', 'gcn34', 'squeezenet')
 CASES = (BASE + ('zf_bf16_drop', 'zf_bf16_src', 'zf_bf16_headdz', 'tiramisu_nocache') + tuple(c + '_nofuse' for c in BASE)
-         + ('zf_bf16_eval', 'linknet_eval', 'abn'))
+         + ('zf_bf16_eval', 'linknet_eval', 'abn', 'zf_bf16_lists', 'unet16_lists', 'linknet_lists'))
 root = os.path.abspath(sys.argv[2]) if len(sys.argv) > 2 else os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [root, os.path.join(root, 'segmentation-networks-benchmark_amd'), os.path.join(root, 'tests')]
 os.environ['SEGNB_TEST_HARNESS'] = '1'       # a tool, not the product: allowed to install the emulator
@@ -75,6 +78,9 @@ def norm(a):
     return type(a).__name__
 
 
+OUT = []
+
+
 def install(out):
     orig_ptr, orig_call, orig_query, orig_vptr, orig_init = nv.ptr, nv.call, nv.query, E.View.ptr.fget, E.PackTable.__init__
 
@@ -120,6 +126,10 @@ def make(case, nocache=False):
         import test_gcn_cpu as tg
         g = tg.load_case('k1')
         return tg.make_gcn('k1', g), torch.from_numpy(g['x']), torch.from_numpy(g['y']), 'bf16'
+    if case == 'squeezenet':
+        import test_squeezenet_cpu as ts
+        g = ts.load_case('sq')
+        return ts.make_squeezenet(g), torch.from_numpy(g['x']), torch.from_numpy(g['y']), 'bf16'
     if case == 'tiramisu':
         from lib.models.tiramisu import FCDenseNet
         FCDenseNet.cache_prefix_stats = not nocache
@@ -143,11 +153,18 @@ def trace_abn():
 def trace(case):
     from lib.losses import BCEWithLogitsLossAndSmoothJaccard
     base = case
-    for suffix in ('_nofuse', '_eval', '_drop', '_src', '_headdz', '_nocache'):
+    for suffix in ('_nofuse', '_eval', '_drop', '_src', '_headdz', '_nocache', '_lists'):
         base = base[:-len(suffix)] if base.endswith(suffix) else base
     if base == 'gcn34':
         import gcn_ref
         nv.set_backend_for_testing(gcn_ref.GcnAbiEmulator())
+    elif base == 'squeezenet':
+        import squeezenet_ref
+        nv.set_backend_for_testing(squeezenet_ref.EluAbiEmulator())
+    elif case.endswith('_lists'):
+        from oracle import abi_emulator
+        import fake_plans
+        fake_plans.on_emulator(abi_emulator.AbiEmulator())
     else:
         from oracle import abi_emulator
         nv.set_backend_for_testing(abi_emulator.AbiEmulator())
@@ -170,12 +187,22 @@ def trace(case):
         return
     model.train()
     torch.manual_seed(13)            # (the Dropout2d multipliers: only the call text is compared, but keep it repeatable)
-    loss = BCEWithLogitsLossAndSmoothJaccard()(model(x), y)
-    (x.shape[0] * loss).backward()
+    for k in range(3 if case.endswith('_lists') else 1):
+        if case.endswith('_lists'):
+            OUT.append('--- step %d' % k)
+            model.zero_grad()
+            if k == 0 and not base.startswith('zf_'):
+                # (the list key is only defined on a GPU: force one)
+                model._plan_key = lambda x, need_grad, grads_alias: ('forced', tuple(x.shape), need_grad)
+        loss = BCEWithLogitsLossAndSmoothJaccard()(model(x), y)
+        if case.endswith('_lists') and k == 0 and base.startswith('zf_'):
+            # (the engine exists behind the first forward, which therefore runs eagerly; its backward records)
+            model._engine._cplan_key = lambda kind, *a: ('forced', kind) + tuple(str(v) for v in a[:5])
+        (x.shape[0] * loss).backward()
 
 
 if __name__ == '__main__':
-    lines = []
+    lines = OUT
     install(lines)
     for case in (CASES if sys.argv[1] == 'all' else sys.argv[1:2]):
         del starts[:], keep[:], lines[:]

@@ -95,7 +95,7 @@ def main():
             saved = []
             for owner, name in ((E.FlatParams, 'ensure'), (E.FlatParams, 'begin_backward'), (E.FlatParams, 'publish_grads'),
                                 (type(eng), '_pack_if_needed'), (type(eng), '_dropout_tables'), (type(eng), '_cplan_key'),
-                                (type(eng), '_after_backward'), (type(eng), 'forward'),
+                                (type(eng), 'forward'),
                                 (type(eng), 'backward'), (type(eng), 'buffers'), (zf.ZF_UNET, 'forward')):
                 if hasattr(owner, name):
                     lab = owner.__name__ + '.' + name

@@ -23,13 +23,12 @@ def main():
     args = ap.parse_args()
     from lib.models.zf_unet import ZF_UNET
     m = ZF_UNET().cuda().train()
-    eng = m._get_engine(torch.device('cuda', 0))
-    eng.rt.set_dtype('bf16') if hasattr(eng.rt, 'set_dtype') else None
     N, H, W = args.batch, args.size, args.size
     x = torch.randn(N, 3, H, W, device='cuda')
     with torch.autocast('cuda', dtype=torch.bfloat16):
         m(x)
     torch.cuda.synchronize()
+    eng = m._engine
     jobs = []
     for conv, h, w in eng._conv_sizes(H, W):
         jobs += conv.pack_jobs(h, w, N) if hasattr(conv, 'segmented') else conv.pack_jobs(h, w)
