@@ -694,6 +694,8 @@ int segnb_head_bn_bwd_apply(int dtype, const void* y, int ld_y, int N, int H, in
  * Per-pixel binary losses and metrics (lib/losses.py:7-101, lib/metrics.py:9-43).
  *   loss = (w_bce*bce2 + w_focal*focal + w_jaccard*jaccard + w_sjaccard*smooth_jaccard + w_dice*dice)/norm
  * bce2 is the reference's double-sigmoid BCE (losses.py:51-53).
+ * The focal element is (1 - pt)^gamma e with pt = exp(-e); at pt == 1 it and its derivative are their limits: 0 for gamma > 0
+ * (also for gamma < 1, where (1 - pt)^(gamma - 1) is unbounded), e and de for gamma == 0.
  * ------------------------------------------------------------------------------------------- */
 typedef struct {
     float w_bce, w_focal, w_jaccard, w_sjaccard, w_dice;

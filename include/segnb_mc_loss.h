@@ -19,6 +19,11 @@
  *   0 loss   1 focal coefficient  2 NLL coefficient  3 valid pixels  4 all pixels  5 bad labels
  *   6 focal term  7 NLL term   [8, 8+C) weighted per-class Jaccard losses w_c L_c (the reduce=0 output)
  *   [8+C, 8+2C) dloss/dI_c   [8+2C, 8+3C) dloss/dP_c
+ * log_softmax is shift invariant: logp = (x - max) - log(sum exp(x - max)), so a common offset of the logits changes nothing.
+ * pt == 1 (logp_t rounds to 0: the target's logit leads by ~17 or more): the focal derivative is its limit, 0 for gamma > 0,
+ * also for gamma < 1 where (1 - pt)^(gamma - 1) is unbounded.
+ * All pixels ignored: every sum but the pixel count is 0, the focal term, the Jaccard terms and dlogits are exactly 0; the NLL
+ * term is 0 / 0: fin[7], and the loss when w_nll != 0, are NaN -- what torch.nn.NLLLoss returns when every target is ignored.
  * Reductions are bitwise reproducible: every workgroup writes one row of partial sums, the last one to finish
  * adds the rows in a fixed order (no floating-point atomics).
  */

@@ -1209,22 +1209,46 @@ class AbiEmulator(object):
         return 0
 
     # ------------------------------------------------------------------------------------------ loss
+    # (the expressions a kernel could get wrong in one place, one method each: tests/loss_mutants.py overrides them)
     @staticmethod
-    def _terms(x, t, gamma=2.0):
+    def _de(p, t):
+        return (1 - p) * (p / (1 + p) - t)
+
+    @staticmethod
+    def _gm1(gamma):
+        return gamma - 1.0
+
+    @staticmethod
+    def _below_one(om):
+        return om > 0
+
+    @staticmethod
+    def _above_half(p):
+        return p > 0.5
+
+    @staticmethod
+    def _gi_smooth(sm):
+        return 2 * sm
+
+    def _terms(self, x, t, gamma=2.0):
         ls = torch.nn.functional.logsigmoid(x)
         p = torch.exp(ls)
         e = -t * ls + torch.log1p(p)
-        de = (1 - p) * (p / (1 + p) - t)
+        de = self._de(p, t)
         pt = torch.exp(-e)
         om = 1 - pt
         if gamma == 2.0:
             f = om * om * e
             df = (2 * om * pt * e + om * om) * de
+        elif gamma == 0.0:
+            f, df = e, de
         else:
-            pg1 = om.clamp_min(1e-38).pow(gamma - 1.0)
+            # pt == 1 (om == 0): the limits, 0 for gamma > 0 (include/segnb_hip.h) -- not (1e-38)^(gamma - 1) times e
+            pos = self._below_one(om)
+            pg1 = torch.where(pos, om, torch.ones_like(om)).pow(self._gm1(gamma))
             pg = pg1 * om
-            f = pg * e
-            df = (gamma * pg1 * pt * e + pg) * de
+            f = torch.where(pos, pg * e, torch.zeros_like(e))
+            df = torch.where(pos, (gamma * pg1 * pt * e + pg) * de, torch.zeros_like(e))
         return p, e, de, f, df
 
     def segnb_seg_loss_reduce(self, logits, target, n, focal_gamma, sums, stream):
@@ -1237,7 +1261,7 @@ class AbiEmulator(object):
         S[2] += (p * t).double().sum()
         S[3] += p.double().sum()
         S[4] += t.double().sum()
-        S[5] += ((p > 0.5) == (t != 0)).double().sum()
+        S[5] += (self._above_half(p) == (t != 0)).double().sum()
         S[6] += float(n)
         return 0
 
@@ -1259,7 +1283,7 @@ class AbiEmulator(object):
         Dj, Ds, Dd = U - I + eps, U - I + sm, U + eps
         loss = (sp.w_bce * bce + sp.w_focal * focal + sp.w_jaccard * (1 - I / Dj) +
                 sp.w_sjaccard * (1 - (I + sm) / Ds) + sp.w_dice * (1 - 2 * I / Dd)) / sp.norm
-        GI = sp.w_jaccard * (-(U + eps) / Dj ** 2) + sp.w_sjaccard * (-(U + 2 * sm) / Ds ** 2) + sp.w_dice * (-2 / Dd)
+        GI = sp.w_jaccard * (-(U + eps) / Dj ** 2) + sp.w_sjaccard * (-(U + self._gi_smooth(sm)) / Ds ** 2) + sp.w_dice * (-2 / Dd)
         GU = sp.w_jaccard * (I / Dj ** 2) + sp.w_sjaccard * ((I + sm) / Ds ** 2) + sp.w_dice * (2 * I / Dd ** 2)
         _mem(out, 8, torch.float32).copy_(torch.tensor([loss, I / (U - I + 1e-7), S[5] / n, GI, GU, bce, n, 0.0]))
         return 0

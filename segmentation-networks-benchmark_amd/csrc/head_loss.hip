@@ -680,8 +680,8 @@ __global__ __launch_bounds__(256) void loss_reduce_kernel(const float* __restric
         //   acquire side  -- the block whose ticket is the last one issues an agent-scope ACQUIRE fence (buffer_inv sc1 + wait)
         //                    before it reads, and reads through coherent (agent-scope atomic) loads.
         // A release FENCE per block instead (what __threadfence() compiles to) writes the XCD's L2 back: 52 us at 512 blocks / 125 us
-        // at 2048 for this launch (profiles/r04_ab.txt); tests/test_hip_ops.py pins the result against the three-launch form at
-        // 512 .. 2048 blocks
+        // at 2048 for this launch (profiles/r04_ab.txt); tests/test_loss_oracle_gpu.py (test_binary_one_launch_against_two_launch)
+        // holds the result to the float64 oracle and to the two-launch form from 2 blocks to the 512-block cap and beyond it
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (threadIdx.x == 0) {

@@ -59,6 +59,8 @@ __device__ __forceinline__ float mc_pow(float om, float g) {
 
 // focal element -(1-pt)^gamma logpt and its derivative w.r.t. logpt:  -(1-pt)^gamma + gamma (1-pt)^(gamma-1) pt logpt
 // (gamma == 0: torch's pow backward masks the exponent-0 term to exactly 0)
+// pt == 1 in fp32 (the winning logit leads by ~17 or more): the derivative is its limit, 0 for gamma > 0, as pix_terms of
+// head_loss.hip returns it -- for gamma < 1, (1-pt)^(gamma-1) * logpt would be inf * 0, or inf * -6e-8
 __device__ __forceinline__ float mc_focal(float logpt, float g) {
     const float pt = expf(logpt);
     return -mc_pow(1.f - pt, g) * logpt;
@@ -66,8 +68,9 @@ __device__ __forceinline__ float mc_focal(float logpt, float g) {
 __device__ __forceinline__ float mc_dfocal(float logpt, float g) {
     const float pt = expf(logpt);
     const float om = 1.f - pt;
-    const float d = -mc_pow(om, g);
-    return g == 0.f ? d : d + g * mc_pow(om, g - 1.f) * pt * logpt;
+    if (g == 0.f) return -1.f;
+    if (!(om > 0.f)) return 0.f;
+    return -mc_pow(om, g) + g * mc_pow(om, g - 1.f) * pt * logpt;
 }
 
 template <int PPT>
@@ -225,9 +228,10 @@ __global__ __launch_bounds__(256) void mc_reduce_kernel(McArgs a, double* __rest
             nvalid += valid[k] ? 1 : 0;
             nbad += (valid[k] && !inr) ? 1 : 0;
         }
-        float sh[PPT], logpt[PPT];
+        float mx[PPT], sh[PPT], logpt[PPT];      // the pixel's max logit and log(sum exp(x - max)): logp = (x - max) - log sum
 #pragma unroll
         for (int k = 0; k < PPT; ++k) {
+            mx[k] = 0.f;
             sh[k] = 0.f;
             logpt[k] = 0.f;
         }
@@ -236,7 +240,7 @@ __global__ __launch_bounds__(256) void mc_reduce_kernel(McArgs a, double* __rest
             float Pv = 0.f, Iv = 0.f, Tv = 0.f;
 #pragma unroll
             for (int k = 0; k < PPT; ++k) {
-                const float lp = xv.v[k] - sh[k];
+                const float lp = (xv.v[k] - mx[k]) - sh[k];
                 const float p = expf(lp);
                 if (valid[k]) Pv += p;
                 if (c == ti[k]) {
@@ -270,7 +274,8 @@ __global__ __launch_bounds__(256) void mc_reduce_kernel(McArgs a, double* __rest
 #pragma unroll
                     for (int c = 0; c < CB; ++c)
                         if (c < C) s += expf(xr[c].v[k] - m);
-                    sh[k] = m + logf(s);
+                    mx[k] = m;
+                    sh[k] = logf(s);
                 }
             }
 #pragma unroll
@@ -295,7 +300,10 @@ __global__ __launch_bounds__(256) void mc_reduce_kernel(McArgs a, double* __rest
                     }
                 }
 #pragma unroll
-                for (int k = 0; k < PPT; ++k) sh[k] = m[k] + logf(s[k]);
+                for (int k = 0; k < PPT; ++k) {
+                    mx[k] = m[k];
+                    sh[k] = logf(s[k]);
+                }
             }
             for (int c = 0; c < C; ++c) klass(c, mc_load<PPT>(xp + (long long)c * a.hw));
         }
@@ -390,11 +398,12 @@ __global__ __launch_bounds__(256) void mc_bwd_kernel(McArgs a, const float* __re
         mc_load_targets<PPT>(a.tg, p0, tv);
         int ti[PPT];
         bool valid[PPT];
-        float sh[PPT], logpt[PPT], S[PPT], av[PPT];
+        float mx[PPT], sh[PPT], logpt[PPT], S[PPT], av[PPT];
 #pragma unroll
         for (int k = 0; k < PPT; ++k) {
             valid[k] = tv[k] != a.ignore;
             ti[k] = (valid[k] && tv[k] >= 0 && tv[k] < C) ? (int)tv[k] : -1;
+            mx[k] = 0.f;
             sh[k] = 0.f;
             logpt[k] = 0.f;
             S[k] = 0.f;
@@ -404,7 +413,7 @@ __global__ __launch_bounds__(256) void mc_bwd_kernel(McArgs a, const float* __re
             const float cp = cP[c], ci = cI[c];
 #pragma unroll
             for (int k = 0; k < PPT; ++k) {
-                const float lp = xv.v[k] - sh[k];
+                const float lp = (xv.v[k] - mx[k]) - sh[k];
                 const float p = expf(lp);
                 xv.v[k] = p;
                 if (valid[k]) S[k] += p * (c == ti[k] ? cp + ci : cp);
@@ -450,7 +459,8 @@ __global__ __launch_bounds__(256) void mc_bwd_kernel(McArgs a, const float* __re
 #pragma unroll
                     for (int c = 0; c < CB; ++c)
                         if (c < C) s += expf(xr[c].v[k] - m);
-                    sh[k] = m + logf(s);
+                    mx[k] = m;
+                    sh[k] = logf(s);
                 }
             }
 #pragma unroll
@@ -479,7 +489,10 @@ __global__ __launch_bounds__(256) void mc_bwd_kernel(McArgs a, const float* __re
                     }
                 }
 #pragma unroll
-                for (int k = 0; k < PPT; ++k) sh[k] = m[k] + logf(s[k]);
+                for (int k = 0; k < PPT; ++k) {
+                    mx[k] = m[k];
+                    sh[k] = logf(s[k]);
+                }
             }
             for (int c = 0; c < C; ++c) {
                 Px<PPT> xv = mc_load<PPT>(xp + (long long)c * a.hw);
@@ -489,7 +502,7 @@ __global__ __launch_bounds__(256) void mc_bwd_kernel(McArgs a, const float* __re
             for (int c = 0; c < C; ++c) {
                 Px<PPT> xv = mc_load<PPT>(xp + (long long)c * a.hw);
 #pragma unroll
-                for (int k = 0; k < PPT; ++k) xv.v[k] = expf(xv.v[k] - sh[k]);
+                for (int k = 0; k < PPT; ++k) xv.v[k] = expf((xv.v[k] - mx[k]) - sh[k]);
                 write(c, xv);
             }
         }
