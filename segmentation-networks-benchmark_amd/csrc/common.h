@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
+#include <limits.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -138,10 +139,36 @@ enum segnb_try_outcome {
     SEGNB_TRY_LAUNCHED,         // launched
     SEGNB_TRY_DELIVERED,        // launched, and the kernel wrote the armed segnb_wgrad_target itself (nothing left to deliver)
 };
-// the tail of a try whose launch helper returned rc (0 or an error): launched unless it failed
+// What a launch_* / dispatch_* helper inside a try returns when its kernel does not serve the arguments after all (no hipError_t,
+// no SEGNB_E_*).  It never leaves a try: segnb_try_launched below is its only reader, and every such result goes through it.
+constexpr int SEGNB_LAUNCH_DECLINED = INT_MIN;
+// the tail of a try whose launch helper returned rc (0, SEGNB_LAUNCH_DECLINED or an error): launched unless it declined or failed
 inline int segnb_try_launched(segnb_try_outcome* did, int rc) {
+    if (rc == SEGNB_LAUNCH_DECLINED) {
+        *did = SEGNB_TRY_DECLINED;
+        return 0;
+    }
     if (rc == 0) *did = SEGNB_TRY_LAUNCHED;
     return rc;
+}
+#define SEGNB_HOST_INLINE static inline __attribute__((always_inline))
+// More than 64 KB of dynamic LDS has to be asked for once per kernel: every kernel a launcher may start, in one call that stops at
+// the first failure, reports it once and returns the status.  A launcher keeps the result:
+//     static const int attr_rc = segnb_opt_in_lds("fprop_rw", C::SMEM, k0, k1, k2);
+template <class... K>
+int segnb_opt_in_lds(const char* who, int bytes, K... kernels) {
+    hipError_t e = hipSuccess;
+    (void)(... && ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernels), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                            bytes)) == hipSuccess));
+    if (e != hipSuccess) segnb_set_error("%s hipFuncSetAttribute(%d bytes): %s", who, bytes, hipGetErrorString(e));
+    return (int)e;
+}
+// The extent in bytes of an NHWC tensor of npix pixels, ld elements apart, up to the C channels of its last pixel, and the one
+// comparison with what a buffer descriptor (32-bit offsets, 2 GiB) addresses; *out (may be NULL) receives the extent.
+SEGNB_HOST_INLINE long long segnb_nhwc_bytes(long long npix, int ld, int C, int esz) { return ((npix - 1) * ld + C) * esz; }
+SEGNB_HOST_INLINE bool segnb_fits_desc(long long bytes, unsigned* out = nullptr) {
+    if (out != nullptr) *out = (unsigned)bytes;
+    return bytes < (1ll << 31);
 }
 // after a try of the plain forward / weight-gradient cascades (segnb_conv_fprop, _act, segnb_conv_wgrad): remember the first
 // selector that launched.  With the call census on, the cascade counts it -- or "kernel:fprop_general" / "kernel:wgrad_general"
@@ -154,8 +181,8 @@ inline void segnb_kernel_took(segnb_try_outcome did, const char** served, const 
 // (forced inline: left to the inliner the tries of fprop_dma.hip, fprop_rw.hip and fprop_roll.hip called it)
 template <class Args>
 __attribute__((always_inline)) inline bool take_bn_reduce(Args& a, const segnb_conv_geom* g, const segnb_bn_reduce_epilogue* bn) {
-    const long long yb = (((long long)g->N * g->Ho * g->Wo - 1) * bn->ld_y + g->Co) * 2;
-    if (yb >= (1ll << 31)) return false;
+    const long long yb = segnb_nhwc_bytes((long long)g->N * g->Ho * g->Wo, bn->ld_y, g->Co, 2);
+    if (!segnb_fits_desc(yb)) return false;
     a.bn_y = (const bf16_t*)bn->y;
     a.bn_y_bytes = (unsigned)yb;
     a.bn_ld = bn->ld_y;
@@ -395,21 +422,57 @@ __device__ __forceinline__ double wave_sum(double v) {
 
 static inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
 
-// a dense 3 x 3 window: 9 taps whose row and column offsets both span exactly 2 (pad 0 or 1, forward or flipped).  Every kernel
-// that assumes +-1 neighbours gates on this; a dilated 3 x 3 (segnb.convplan, dilation > 1) has 9 taps over a wider span and goes
-// to the general gather kernel
-static inline bool segnb_taps_3x3(const segnb_conv_geom* g) {
-    if (g->ntaps != 9) return false;
+// ------------------------------------------------------------------------------------------------
+// what the kernel tries (segnb_*_try, the *_ok / *_applies predicates beside them) say about a geometry, once.  Forced inline:
+// they run per launch, and left to the inliner some of them became calls (as take_bn_reduce above, as the lambdas of 13.20)
+// ------------------------------------------------------------------------------------------------
+// The window of g's taps: its origin (the smallest row and column offset -- every fast path addresses its input from there) and
+// its extent in rows and columns.
+struct segnb_tap_win {
+    int dhmin, dwmin, kh, kw;
+};
+SEGNB_HOST_INLINE segnb_tap_win segnb_tap_window(const segnb_conv_geom* g) {
     int dhmin = g->dh[0], dhmax = g->dh[0], dwmin = g->dw[0], dwmax = g->dw[0];
-    for (int t = 1; t < 9; ++t) {
+    for (int t = 1; t < g->ntaps; ++t) {
         dhmin = g->dh[t] < dhmin ? g->dh[t] : dhmin;
         dhmax = g->dh[t] > dhmax ? g->dh[t] : dhmax;
         dwmin = g->dw[t] < dwmin ? g->dw[t] : dwmin;
         dwmax = g->dw[t] > dwmax ? g->dw[t] : dwmax;
     }
-    return dhmax - dhmin == 2 && dwmax - dwmin == 2;
+    return {dhmin, dwmin, dhmax - dhmin + 1, dwmax - dwmin + 1};
 }
-// one launch of a dense stride-1 3 x 3 that writes every output pixel: what the fused forward entry points serve
-static inline bool whole_output_3x3_s1(const segnb_conv_geom* g) {
-    return segnb_taps_3x3(g) && g->in_step == 1 && g->out_step == 1 && g->oh0 == 0 && g->ow0 == 0 && g->QH == g->Ho && g->QW == g->Wo;
+// a dense 3 x 3 window: 9 taps whose row and column offsets both span exactly 2 (pad 0 or 1, forward or flipped).  Every kernel
+// that assumes +-1 neighbours gates on this; a dilated 3 x 3 (segnb.convplan, dilation > 1) has 9 taps over a wider span and goes
+// to the general gather kernel
+SEGNB_HOST_INLINE bool segnb_taps_3x3(const segnb_conv_geom* g) {
+    if (g->ntaps != 9) return false;
+    const segnb_tap_win win = segnb_tap_window(g);
+    return win.kh == 3 && win.kw == 3;
 }
+// the tap tables of a kernel's argument struct, relative to the window's origin: 0 .. kh - 1 and 0 .. kw - 1 (after segnb_taps_3x3:
+// 0 .. 2); E: int, or signed char in the structs that hold SEGNB_MAX_TAPS of them
+template <class E>
+SEGNB_HOST_INLINE void segnb_rel_taps(const segnb_conv_geom* g, const segnb_tap_win& win, E* dh_out, E* dw_out) {
+    for (int t = 0; t < g->ntaps; ++t) {
+        dh_out[t] = (E)(g->dh[t] - win.dhmin);
+        dw_out[t] = (E)(g->dw[t] - win.dwmin);
+    }
+}
+// after segnb_taps_3x3 (the spans are 2): each of the nine positions of the window is one tap's, none twice; k_of_tap (may be
+// NULL) receives the position row * 3 + column of every tap
+SEGNB_HOST_INLINE bool segnb_window_once_3x3(const segnb_conv_geom* g, const segnb_tap_win& win, int* k_of_tap = nullptr) {
+    bool seen[9] = {false, false, false, false, false, false, false, false, false};
+    for (int t = 0; t < 9; ++t) {
+        const int k = (g->dh[t] - win.dhmin) * 3 + (g->dw[t] - win.dwmin);
+        if (seen[k]) return false;
+        seen[k] = true;
+        if (k_of_tap != nullptr) k_of_tap[t] = k;
+    }
+    return true;
+}
+// one launch that writes every output pixel of its tensor ...
+SEGNB_HOST_INLINE bool whole_output(const segnb_conv_geom* g) {
+    return g->out_step == 1 && g->oh0 == 0 && g->ow0 == 0 && g->QH == g->Ho && g->QW == g->Wo;
+}
+// ... of a dense stride-1 3 x 3: what the fused forward entry points and most of the tries serve
+SEGNB_HOST_INLINE bool whole_output_3x3_s1(const segnb_conv_geom* g) { return segnb_taps_3x3(g) && g->in_step == 1 && whole_output(g); }

@@ -911,29 +911,18 @@ static bool wgrad_co8_applies(const segnb_conv_geom* g) {
     return g->Co == 8 && nslot <= NT && (long long)g->N * g->QH * g->QW >= 1024;
 }
 
-template <typename K>
-int set_smem(K kernel, int bytes) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) {
-        segnb_set_error("hipFuncSetAttribute(%d bytes): %s", bytes, hipGetErrorString(e));
-        return (int)e;
-    }
-    return 0;
-}
-
 template <typename T, int BM, int BN, int WM, int WN>
 int launch_fprop(FpropArgs& a, hipStream_t stream) {
     constexpr int smem = fprop_smem_bytes<BM, BN, T>();
     static_assert(smem >= NT * 16 * 4, "BatchNorm-reduce scratch");
-    static int attr_rc = [] {
-        int rc = set_smem(conv_fprop_kernel<T, BM, BN, WM, WN>, smem);
-        if (rc == 0) rc = set_smem(conv_fprop_kernel<T, BM, BN, WM, WN, true>, smem);
+    static const int attr_rc = [] {
+        int rc = segnb_opt_in_lds("fprop_general", smem, conv_fprop_kernel<T, BM, BN, WM, WN>, conv_fprop_kernel<T, BM, BN, WM, WN, true>);
         if constexpr (sizeof(T) == 2) {
-            if (rc == 0) rc = set_smem(conv_fprop_kernel<T, BM, BN, WM, WN, false, true>, smem);
+            if (rc == 0) rc = segnb_opt_in_lds("fprop_general", smem, conv_fprop_kernel<T, BM, BN, WM, WN, false, true>);
             if constexpr (BN == 64) {         // (the two-launch form of a dense layer's data gradient: 64-channel tiles only)
-                if (rc == 0) rc = set_smem(conv_fprop_kernel<T, BM, BN, WM, WN, false, true, 1>, smem);
-                if (rc == 0) rc = set_smem(conv_fprop_kernel<T, BM, BN, WM, WN, false, true, 2>, smem);
+                if (rc == 0)
+                    rc = segnb_opt_in_lds("fprop_general", smem, conv_fprop_kernel<T, BM, BN, WM, WN, false, true, 1>,
+                                          conv_fprop_kernel<T, BM, BN, WM, WN, false, true, 2>);
             }
         }
         return rc;
@@ -995,7 +984,7 @@ int dispatch_fprop(FpropArgs& a, hipStream_t stream) {
 template <typename T, int BM, int BN, int WM, int WN>
 int launch_wgrad(WgradArgs& a, hipStream_t stream) {
     constexpr int smem = (BM + BN) * LDS_ROW;
-    static int attr_rc = set_smem(conv_wgrad_kernel<T, BM, BN, WM, WN>, smem);
+    static const int attr_rc = segnb_opt_in_lds("wgrad_general", smem, conv_wgrad_kernel<T, BM, BN, WM, WN>);
     if (attr_rc) return attr_rc;
     constexpr int BKP = 8 * Elem<T>::EPC;
     a.MT = ceil_div(a.g.Co, BM);
@@ -1062,21 +1051,18 @@ static int oversize(const char* fn) {
 // The 32-bit buffer extents of a launch's operands: the gathered tensor up to the ci_in channels of its last pixel (g->Ci; the
 // skip tensor's Ci - Cu of a virtual concat) and the packed weights, esz bytes per element.  False when either passes 2 GiB.
 static bool conv_extents_fit(const segnb_conv_geom* g, long long esz, int ci_in, unsigned* inb, unsigned* wb) {
-    const long long i = (((long long)g->N * g->Hi * g->Wi - 1) * g->ld_in + ci_in) * esz;
     const long long w = (long long)g->Co * g->ntaps * g->Ci * esz;
-    *inb = (unsigned)i;
     *wb = (unsigned)w;
-    return i < (1ll << 31) && w < (1ll << 31);
+    return segnb_fits_desc(segnb_nhwc_bytes((long long)g->N * g->Hi * g->Wi, g->ld_in, ci_in, (int)esz), inb) && w < (1ll << 31);
 }
 static int conv_extents(const char* fn, const segnb_conv_geom* g, long long esz, int ci_in, unsigned* inb, unsigned* wb) {
     return conv_extents_fit(g, esz, ci_in, inb, wb) ? 0 : oversize(fn);
 }
 // the same of segnb_upconv_fprop*: a bf16 N x H x W x Ci tensor and the four phase matrices [CoW][4 * Ci]
 static int upconv_extents(const char* fn, int N, int H, int W, int Ci, int ld_in, int CoW, unsigned* inb, unsigned* wb) {
-    const long long i = (((long long)N * H * W - 1) * ld_in + Ci) * 2, w = 4ll * CoW * 4 * Ci * 2;
-    *inb = (unsigned)i;
+    const long long w = 4ll * CoW * 4 * Ci * 2;
     *wb = (unsigned)w;
-    return i < (1ll << 31) && w < (1ll << 31) ? 0 : oversize(fn);
+    return segnb_fits_desc(segnb_nhwc_bytes((long long)N * H * W, ld_in, Ci, 2), inb) && w < (1ll << 31) ? 0 : oversize(fn);
 }
 
 // Arguments of a launch of conv_fprop_kernel / conv_fprop_deepk_kernel without any epilogue: geometry, operands and their extents,
@@ -1283,7 +1269,7 @@ extern "C" int segnb_conv_fprop_drop(const segnb_conv_geom* g, int dtype, const 
 static int upconv_shape_ok(int N, int H, int W, int Ci, int Co, int ld_out, int dtype, int co_floor) {
     if (dtype != SEGNB_BF16 || segnb_fprop_general_forced() || !segnb_knob_fprop_dma() || !segnb_knob_fprop_upd()) return 0;
     if (N <= 0 || H <= 0 || W <= 0 || Ci % 64 != 0 || Ci < 128 || Co <= co_floor || Co % 8 != 0 || W < 12) return 0;
-    return (((long long)N * 4 * H * W - 1) * ld_out + Co) * 2 < (1ll << 31) ? 1 : 0;
+    return segnb_fits_desc(segnb_nhwc_bytes((long long)N * 4 * H * W, ld_out, Co, 2)) ? 1 : 0;
 }
 
 // what the three entry points below do once their arguments are checked: extents, the launch, its tail
@@ -1431,6 +1417,11 @@ extern "C" int segnb_conv_wgrad_upcat(const segnb_conv_geom* g, int dtype, const
     return finish_wgrad(__func__, did, g, dwp, nslab, tgt, false, (hipStream_t)stream);
 }
 
+// a bf16 tensor of the output's pixels and channels, ld apart (the y / dx of an epilogue), within a buffer descriptor's 2 GiB
+static bool out_slice_fits(const segnb_conv_geom* g, int ld) {
+    return segnb_fits_desc(segnb_nhwc_bytes((long long)g->N * g->Ho * g->Wo, ld, g->Co, 2));
+}
+
 // few input channels -> many output channels: the data gradient of a dense layer (tiramisu.py:9-20, growth 16 -> the prefix);
 // the general gather kernel serves it, with the reduction in its store pass (conv_fprop_kernel<..., BNR>)
 static bool bnreduce_general(const segnb_conv_geom* g) { return g->Ci <= 24 && g->Co >= 32 && g->Co % 8 == 0; }
@@ -1468,7 +1459,7 @@ extern "C" int segnb_conv_fprop_bnreduce(const segnb_conv_geom* g, int dtype, co
     } else {
         SEGNB_CHECK_ARG(segnb_conv_fprop_bnreduce_ok(g, dtype), "geometry not served by a fused kernel (segnb_conv_fprop_bnreduce_ok)");
         if (bnreduce_general(g)) {
-            SEGNB_CHECK_ARG(ep->ld_y % 8 == 0 && (((long long)g->N * g->Ho * g->Wo - 1) * ep->ld_y + g->Co) * 2 < (1ll << 31), "bad y");
+            SEGNB_CHECK_ARG(ep->ld_y % 8 == 0 && out_slice_fits(g, ep->ld_y), "bad y");
             return conv_fprop_impl(g, dtype, in, wpacked, nullptr, 0, out, nullptr, stream, nullptr, ep);
         }
         if (g->Ci <= 96) {
@@ -1494,8 +1485,7 @@ extern "C" int segnb_conv_fprop_bnsums(const segnb_conv_geom* g, int dtype, cons
     if (int rc = check_geom(g)) return rc;
     SEGNB_CHECK_ARG(in && wpacked && ep && ep->y && ep->coef && ep->sums, "NULL argument");
     SEGNB_CHECK_ARG(segnb_conv_fprop_bnapply_ok(g, dtype), "geometry not served (segnb_conv_fprop_bnapply_ok)");
-    SEGNB_CHECK_ARG(ep->ld_y >= g->Co && ep->ld_y % 8 == 0 && (((long long)g->N * g->Ho * g->Wo - 1) * ep->ld_y + g->Co) * 2 < (1ll << 31),
-                    "bad y");
+    SEGNB_CHECK_ARG(ep->ld_y >= g->Co && ep->ld_y % 8 == 0 && out_slice_fits(g, ep->ld_y), "bad y");
     return conv_fprop_impl(g, dtype, in, wpacked, nullptr, 0, nullptr, nullptr, stream, nullptr, ep, nullptr, 1);
 }
 
@@ -1506,10 +1496,8 @@ extern "C" int segnb_conv_fprop_bnapply(const segnb_conv_geom* g, int dtype, con
     SEGNB_CHECK_ARG(in && wpacked && ep && ep->y && ep->coef && ep->sums && ep->dx, "NULL argument");
     SEGNB_CHECK_ARG(segnb_conv_fprop_bnapply_ok(g, dtype), "geometry not served (segnb_conv_fprop_bnapply_ok)");
     SEGNB_CHECK_ARG(ep->C > 0 && ep->C <= g->Co && ep->count > 0.0, "bad channel count / pixel count");
-    SEGNB_CHECK_ARG(ep->ld_y >= g->Co && ep->ld_y % 8 == 0 && (((long long)g->N * g->Ho * g->Wo - 1) * ep->ld_y + g->Co) * 2 < (1ll << 31),
-                    "bad y");
-    SEGNB_CHECK_ARG(ep->ld_dx >= g->Co && ep->ld_dx % 8 == 0 && (((long long)g->N * g->Ho * g->Wo - 1) * ep->ld_dx + g->Co) * 2 < (1ll << 31),
-                    "bad dx");
+    SEGNB_CHECK_ARG(ep->ld_y >= g->Co && ep->ld_y % 8 == 0 && out_slice_fits(g, ep->ld_y), "bad y");
+    SEGNB_CHECK_ARG(ep->ld_dx >= g->Co && ep->ld_dx % 8 == 0 && out_slice_fits(g, ep->ld_dx), "bad dx");
     return conv_fprop_impl(g, dtype, in, wpacked, nullptr, 0, nullptr, nullptr, stream, nullptr, nullptr, ep, 2);
 }
 

@@ -249,7 +249,7 @@ int segnb_fprop_c8_try(segnb_try_outcome* did, const segnb_conv_geom* g, const v
 
 static bool c8_launch(const segnb_conv_geom* g, const void* in, const C8Norm* u8, const void* wpacked, const float* bias,
                       int bias_n, void* out, double* stats, hipStream_t stream, const segnb_act_epilogue* ep) {
-    if (!segnb_taps_3x3(g) || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return false;
+    if (!whole_output_3x3_s1(g)) return false;
     if (g->Co > 32 && g->Co <= 64 && g->Co % 8 == 0 && g->Ci == 8 && stats == nullptr && u8 == nullptr &&
         (ep == nullptr || ep->coef == nullptr)) {
         // 33..64 output channels (unet16.py:73: VGG's 3 -> 64 at 1024 x 1024) as two launches over channel halves: the input is
@@ -262,12 +262,8 @@ static bool c8_launch(const segnb_conv_geom* g, const void* in, const C8Norm* u8
         return c8_launch(&h, in, nullptr, (const bf16_t*)wpacked + 32 * 9 * 8, bias != nullptr && bias_n > 32 ? bias + 32 : nullptr,
                          bias_n > 32 ? bias_n - 32 : 0, (bf16_t*)out + 32, nullptr, stream, ep);
     }
-    if (g->QH != g->Ho || g->QW != g->Wo || g->Ci != 8 || g->Co > 32 || g->Wo < 12) return false;
-    int dhmin = g->dh[0], dwmin = g->dw[0];      // (segnb_taps_3x3 above: the spans are 2)
-    for (int t = 1; t < 9; ++t) {
-        dhmin = g->dh[t] < dhmin ? g->dh[t] : dhmin;
-        dwmin = g->dw[t] < dwmin ? g->dw[t] : dwmin;
-    }
+    if (g->Ci != 8 || g->Co > 32 || g->Wo < 12) return false;
+    const segnb_tap_win win = segnb_tap_window(g);
     C8Args a;
     take_act_epilogue(a, ep);
     if (u8 != nullptr) a.u8 = *u8;
@@ -279,11 +275,8 @@ static bool c8_launch(const segnb_conv_geom* g, const void* in, const C8Norm* u8
     a.stats = stats;
     a.N = g->N; a.H = g->Ho; a.W = g->Wo; a.Hi = g->Hi; a.Wi = g->Wi;
     a.Co = g->Co; a.ld_x = g->ld_in; a.ld_out = g->ld_out;
-    a.dhmin = dhmin; a.dwmin = dwmin;
-    for (int t = 0; t < 9; ++t) {
-        a.dh[t] = g->dh[t] - dhmin;
-        a.dw[t] = g->dw[t] - dwmin;
-    }
+    a.dhmin = win.dhmin; a.dwmin = win.dwmin;
+    segnb_rel_taps(g, win, a.dh, a.dw);
     a.HB = (a.H + C8_R - 1) / C8_R;
     a.WB = (a.W + C8_WT - 1) / C8_WT;
     a.IT = a.N * a.HB * a.WB;
@@ -356,8 +349,7 @@ extern "C" int segnb_pack_input_u8(const unsigned char* img, int N, int H, int W
 
 extern "C" int segnb_conv_fprop_u8_ok(const segnb_conv_geom* g, int dtype) {
     if (g == nullptr || dtype != SEGNB_BF16 || !segnb_knob_fprop_dma()) return 0;
-    if (!segnb_taps_3x3(g) || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return 0;
-    if (g->QH != g->Ho || g->QW != g->Wo || g->Ci != 8 || g->Co > 32 || g->Wo < 12 || g->Hi != g->Ho || g->Wi != g->Wo) return 0;
+    if (!whole_output_3x3_s1(g) || g->Ci != 8 || g->Co > 32 || g->Wo < 12 || g->Hi != g->Ho || g->Wi != g->Wo) return 0;
     for (int t = 0; t < 9; ++t)
         if (g->dh[t] < -1 || g->dh[t] > 1 || g->dw[t] < -1 || g->dw[t] > 1) return 0;
     return 1;

@@ -1210,45 +1210,28 @@ int ksplit_factor(const FdArgs& a, int it_total, int ntl, int nch) {
     return ks;
 }
 
-constexpr int NOT_HANDLED = -12345;
-
 template <class C>
 int launch_ws(FdArgs& a, hipStream_t stream) {
-    if (a.bn_y != nullptr && !C::MASK_OK) return NOT_HANDLED;      // (activation mask: 16 x 16 tiles, 16x16x32 form)
-    static int attr_rc = [] {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fprop_ws_kernel<C, false>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fprop_ws_kernel<C, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fprop_ws_kernel<C, false, true, false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fprop_ws_kernel<C, false, false, false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM);
+    if (a.bn_y != nullptr && !C::MASK_OK) return SEGNB_LAUNCH_DECLINED;      // (activation mask: 16 x 16 tiles, 16x16x32 form)
+    static const int attr_rc = [] {
+        int rc = segnb_opt_in_lds("fprop_ws", C::SMEM, conv_fprop_ws_kernel<C, false>, conv_fprop_ws_kernel<C, true>,
+                                  conv_fprop_ws_kernel<C, false, true, false>, conv_fprop_ws_kernel<C, false, false, false>);
         if constexpr (C::MASK_OK) {
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fprop_ws_kernel<C, false, false, true, false, true>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM + 2048);
+            if (rc == 0) rc = segnb_opt_in_lds("fprop_ws", C::SMEM + 2048, conv_fprop_ws_kernel<C, false, false, true, false, true>);
         }
         if constexpr (C::TALL) {
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fprop_ws_kernel<C, false, false, true, true>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM);
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fprop_ws_kernel<C, false, false, false, true>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM);
+            if (rc == 0)
+                rc = segnb_opt_in_lds("fprop_ws", C::SMEM, conv_fprop_ws_kernel<C, false, false, true, true>,
+                                      conv_fprop_ws_kernel<C, false, false, false, true>);
         }
-        if (e != hipSuccess) segnb_set_error("fprop_ws hipFuncSetAttribute: %s", hipGetErrorString(e));
-        return (int)e;
+        return rc;
     }();
     if (attr_rc) return attr_rc;
     a.HB = (a.H + C::R - 1) / C::R;
     a.WB = (a.W + C::WT - 1) / C::WT;
     a.IT = a.N * a.HB * a.WB;
     if (C::TALL) {
-        if (a.W > C::WT || a.Hi != a.H || a.Wi != a.W) return -12345;
+        if (a.W > C::WT || a.Hi != a.H || a.Wi != a.W) return SEGNB_LAUNCH_DECLINED;
         a.IT = (a.N * (a.H + 1) + C::R - 1) / C::R;
     }
     a.NTL = (a.Co + C::BN - 1) / C::BN;
@@ -1281,7 +1264,7 @@ int launch_ws(FdArgs& a, hipStream_t stream) {
                                stream, a);
             return 0;
         } else {
-            return NOT_HANDLED;
+            return SEGNB_LAUNCH_DECLINED;
         }
     }
     if (a.ep_act >= 0)            // (never with statistics: segnb_conv_fprop_act takes none)
@@ -1309,15 +1292,7 @@ bool ws14_serves(const FdArgs& a) {
 
 int launch_ws14(FdArgs& a, hipStream_t stream) {
     using C = WsCfg14;
-    static int attr_rc = [] {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fprop_ws_kernel<C, false>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fprop_ws_kernel<C, false, false, false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM);
-        if (e != hipSuccess) segnb_set_error("fprop_ws hipFuncSetAttribute: %s", hipGetErrorString(e));
-        return (int)e;
-    }();
+    static const int attr_rc = segnb_opt_in_lds("fprop_ws", C::SMEM, conv_fprop_ws_kernel<C, false>, conv_fprop_ws_kernel<C, false, false, false>);
     if (attr_rc) return attr_rc;
     a.HB = a.H / C::R;
     a.WB = a.W / C::WT;
@@ -1341,12 +1316,7 @@ int launch_ws14(FdArgs& a, hipStream_t stream) {
 // the plane gather (data gradient of an upsampled segment): one instantiation (no statistics, no epilogue)
 template <class C>
 int launch_ws_upd(FdArgs& a, hipStream_t stream) {
-    static int attr_rc = [] {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fprop_ws_kernel<C, false, false, false>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM);
-        if (e != hipSuccess) segnb_set_error("fprop_ws hipFuncSetAttribute: %s", hipGetErrorString(e));
-        return (int)e;
-    }();
+    static const int attr_rc = segnb_opt_in_lds("fprop_ws", C::SMEM, conv_fprop_ws_kernel<C, false, false, false>);
     if (attr_rc) return attr_rc;
     a.HB = (a.H + C::R - 1) / C::R;
     a.WB = (a.W + C::WT - 1) / C::WT;
@@ -1356,7 +1326,7 @@ int launch_ws_upd(FdArgs& a, hipStream_t stream) {
     a.NCHP = a.P32 ? 1 : a.Ci / 64;
     a.NCH = a.P32 ? 2 : 4 * a.NCHP;
     a.RPS = a.NCH * C::NTAP - 1 < C::RPT ? 2 : 1;               // the previous tile's store rows ride on steps 1.., one or two each
-    if ((a.NCH * C::NTAP - 1) * a.RPS < C::RPT) return NOT_HANDLED;
+    if ((a.NCH * C::NTAP - 1) * a.RPS < C::RPT) return SEGNB_LAUNCH_DECLINED;
     int gm = segnb_knob_conv_cus() / a.NTL;
     if (gm < 1) gm = 1;
     if (gm > a.IT) gm = a.IT;
@@ -1368,12 +1338,7 @@ int launch_ws_upd(FdArgs& a, hipStream_t stream) {
 // the forward of an up-sampled segment: four phases in one launch, accumulating (WsCfg UP_ = 2)
 template <class C>
 int launch_ws_upf(FdArgs& a, hipStream_t stream) {
-    static int attr_rc = [] {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fprop_ws_kernel<C, false, false, true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM);
-        if (e != hipSuccess) segnb_set_error("fprop_ws hipFuncSetAttribute: %s", hipGetErrorString(e));
-        return (int)e;
-    }();
+    static const int attr_rc = segnb_opt_in_lds("fprop_ws", C::SMEM, conv_fprop_ws_kernel<C, false, false, true>);
     if (attr_rc) return attr_rc;
     a.HB = (a.H + C::R - 1) / C::R;
     a.WB = (a.W + C::WT - 1) / C::WT;
@@ -1384,7 +1349,7 @@ int launch_ws_upf(FdArgs& a, hipStream_t stream) {
     a.NCHP = a.NCH;
     a.P32 = 0;
     a.RPS = a.NCH * C::NTAP - 1 < C::RPT ? 2 : 1;               // store rows per step
-    if ((a.NCH * C::NTAP - 1) * a.RPS < C::RPT) return NOT_HANDLED;
+    if ((a.NCH * C::NTAP - 1) * a.RPS < C::RPT) return SEGNB_LAUNCH_DECLINED;
     int gm = segnb_knob_conv_cus() / a.NTL;
     if (gm < 1) gm = 1;
     if (gm > a.IT) gm = a.IT;
@@ -1396,8 +1361,7 @@ int launch_ws_upf(FdArgs& a, hipStream_t stream) {
 // ntaps 16, in_step 2: out[Y, X] = sum_{a, b < 4} in[2 Y + a - 1, 2 X + b - 1] . W[a * 4 + b]  (segnb.convplan.convt_dgrad of a
 // 4 x 4 / stride-2 / pad-1 transposed convolution -- UpConvOp, unet16.py:38, linknet.py:16)
 bool upd_geometry(const segnb_conv_geom* g) {
-    if (g->ntaps != 16 || g->in_step != 2 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return false;
-    if (g->QH != g->Ho || g->QW != g->Wo || g->Hi != 2 * g->Ho || g->Wi != 2 * g->Wo) return false;
+    if (g->ntaps != 16 || g->in_step != 2 || !whole_output(g) || g->Hi != 2 * g->Ho || g->Wi != 2 * g->Wo) return false;
     if ((g->Ci % 64 != 0 && g->Ci != 32) || g->Co <= 32 || g->Wo < 12) return false;
     for (int t = 0; t < 16; ++t)
         if (g->dh[t] != t / 4 - 1 || g->dw[t] != t % 4 - 1) return false;
@@ -1405,7 +1369,7 @@ bool upd_geometry(const segnb_conv_geom* g) {
 }
 
 int try_upd(const segnb_conv_geom* g, FdArgs& a, hipStream_t stream) {
-    if (!upd_geometry(g)) return NOT_HANDLED;
+    if (!upd_geometry(g)) return SEGNB_LAUNCH_DECLINED;
     a.Ktot = 16 * g->Ci;
     a.dhmin = a.dwmin = 0;
     for (int t = 0; t < 9; ++t) a.dh[t] = a.dw[t] = 0;
@@ -1448,11 +1412,11 @@ int dispatch_fd(FdArgs& a, hipStream_t stream) {
         // only 200-800 of them;
         // 16 x 16 pixel tiles tie or beat 8 x 32 except for the widest data gradients.  Outputs of <= 32 channels
         // (half of every tile padding) and 7x7 images stay with fprop_s1 / the general kernel.
-        if (a.Co <= 32) return NOT_HANDLED;
+        if (a.Co <= 32) return SEGNB_LAUNCH_DECLINED;
         // 7 x 7 images (the deepest ZF_UNET level): tall-image tiles of 36 x 7 virtual pixels -- 8 row tiles x 16 channel
         // tiles = 128 blocks of 144 taps each beat the general kernel's 400 tiles of 64 x 64 (76 -> ~45 us for 1024 -> 1024)
         if (a.W <= 8) {
-            if (a.W != 7 || a.H != 7) return NOT_HANDLED;
+            if (a.W != 7 || a.H != 7) return SEGNB_LAUNCH_DECLINED;
             return launch_ws<WsCfg<64, 36, 7, 4, true, false>>(a, stream);      // odd halo pitch: 32x32x16 form
         }
         // 8 x 32 or 16 x 16 pixel tiles: whichever needs fewer rounds of (equal) tiles on the persistent blocks --
@@ -1485,14 +1449,14 @@ int dispatch_fd(FdArgs& a, hipStream_t stream) {
             case 0: return launch_ws<WsCfg<64, 8, 32, 4, false, true>>(a, stream);
             case 1: return launch_ws<WsCfg<64, 16, 16, 4, false, true>>(a, stream);
             case 2: return launch_ws<WsCfg<64, 36, 7, 4, true, false>>(a, stream);
-            default: return NOT_HANDLED;
+            default: return SEGNB_LAUNCH_DECLINED;
         }
     }
     switch (cfg) {
         case 0: return launch_ws<WsCfg<64, 8, 32, 4, false, false>>(a, stream);
         case 1: return launch_ws<WsCfg<64, 16, 16, 4, false, false>>(a, stream);
         case 2: return launch_ws<WsCfg<64, 36, 7, 4, true, false>>(a, stream);
-        default: return NOT_HANDLED;
+        default: return SEGNB_LAUNCH_DECLINED;
     }
 }
 
@@ -1521,9 +1485,7 @@ int segnb_fprop_upf_try(segnb_try_outcome* did, int N, int H, int W, int Ci, int
     a.Ci = Ci; a.Co = Co; a.ld_x = ld_in; a.ld_out = ld_out;
     a.CoW = CoW;
     a.Ktot = 4 * Ci;
-    const long long ob = (((long long)N * 4 * H * W - 1) * ld_out + Co) * 2;
-    if (ob >= (1ll << 31)) return 0;
-    a.out_bytes = (unsigned)ob;
+    if (!segnb_fits_desc(segnb_nhwc_bytes((long long)N * 4 * H * W, ld_out, Co, 2), &a.out_bytes)) return 0;
     a.dhmin = a.dwmin = 0;
     for (int t = 0; t < 9; ++t) a.dh[t] = a.dw[t] = 0;
     a.dh[2] = a.dh[3] = 1;
@@ -1544,7 +1506,6 @@ int segnb_fprop_upf_try(segnb_try_outcome* did, int N, int H, int W, int Ci, int
     if (cfg < 0) cfg = (it0 + gm - 1) / gm < (it1 + gm - 1) / gm ? 0 : 1;
     const int rc = cfg == 0 ? launch_ws_upf<WsCfg<64, 8, 32, 4, false, true, 4, 2>>(a, stream)
                             : launch_ws_upf<WsCfg<64, 16, 16, 4, false, true, 4, 2>>(a, stream);
-    if (rc == NOT_HANDLED) return 0;
     return segnb_try_launched(did, rc);
 }
 
@@ -1553,33 +1514,20 @@ int segnb_fprop_dma_actmask_ok(const segnb_conv_geom* g) {
     if (!segnb_knob_fprop_dma() || !segnb_knob_fprop_mask() || !segnb_knob_fprop_mf16() || segnb_knob_fprop_dma_cfg() == 2 ||
         segnb_fprop_general_forced())
         return 0;
-    if (!segnb_taps_3x3(g) || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return 0;
-    if (g->QH != g->Ho || g->QW != g->Wo || g->Ci % 64 != 0 || g->Co <= 32 || g->Co % 8 != 0 || g->Wo <= 8) return 0;
-    int dhmin = g->dh[0], dwmin = g->dw[0];
-    for (int t = 1; t < 9; ++t) {
-        dhmin = g->dh[t] < dhmin ? g->dh[t] : dhmin;
-        dwmin = g->dw[t] < dwmin ? g->dw[t] : dwmin;
-    }
-    for (int t = 0; t < 9; ++t) {        // row-major 3 x 3 window (either direction): the 16x16x32 form's address tables
-        if (g->dh[t] - dhmin != g->dh[3 * (t / 3)] - dhmin || g->dw[t] - dwmin != g->dw[t % 3] - dwmin) return 0;
-        if (g->dh[t] - dhmin > 2 || g->dw[t] - dwmin > 2) return 0;
-    }
-    bool seen[9] = {false, false, false, false, false, false, false, false, false};
-    for (int t = 0; t < 9; ++t) {
-        const int k = (g->dh[t] - dhmin) * 3 + (g->dw[t] - dwmin);
-        if (seen[k]) return 0;
-        seen[k] = true;
-    }
-    const long long inb = (((long long)g->N * g->Hi * g->Wi - 1) * g->ld_in + g->Ci) * 2;
-    const long long ob = (((long long)g->N * g->Ho * g->Wo - 1) * g->ld_out + g->Co) * 2;
-    return inb < (1ll << 31) && ob < (1ll << 31) ? 1 : 0;
+    if (!whole_output_3x3_s1(g) || g->Ci % 64 != 0 || g->Co <= 32 || g->Co % 8 != 0 || g->Wo <= 8) return 0;
+    for (int t = 0; t < 9; ++t)          // row-major 3 x 3 window (either direction): the 16x16x32 form's address tables
+        if (g->dh[t] != g->dh[3 * (t / 3)] || g->dw[t] != g->dw[t % 3]) return 0;
+    if (!segnb_window_once_3x3(g, segnb_tap_window(g))) return 0;
+    return segnb_fits_desc(segnb_nhwc_bytes((long long)g->N * g->Hi * g->Wi, g->ld_in, g->Ci, 2)) &&
+                   segnb_fits_desc(segnb_nhwc_bytes((long long)g->N * g->Ho * g->Wo, g->ld_out, g->Co, 2))
+               ? 1
+               : 0;
 }
 
 extern "C" int segnb_conv_fprop_upd_ok(const segnb_conv_geom* g, int dtype) {
     if (g == nullptr || dtype != SEGNB_BF16) return 0;
     if (!segnb_knob_fprop_dma() || !segnb_knob_fprop_upd() || segnb_fprop_general_forced()) return 0;
-    const long long ob = (((long long)g->N * g->Ho * g->Wo - 1) * g->ld_out + g->Co) * 2;
-    return upd_geometry(g) && ob < (1ll << 31) ? 1 : 0;
+    return upd_geometry(g) && segnb_fits_desc(segnb_nhwc_bytes((long long)g->N * g->Ho * g->Wo, g->ld_out, g->Co, 2)) ? 1 : 0;
 }
 
 // timing builds: copy the stamps of the last stamped launch to the host (3 roles x 256 steps x 4 clocks)
@@ -1611,9 +1559,7 @@ int segnb_fprop_dma_try(segnb_try_outcome* did, const segnb_conv_geom* g, const 
         a.stats = nullptr;
         a.N = g->N; a.H = g->Ho; a.W = g->Wo; a.Hi = g->Hi; a.Wi = g->Wi;
         a.Ci = g->Ci; a.Co = g->Co; a.ld_x = g->ld_in; a.ld_out = g->ld_out;
-        const long long ob = (((long long)g->N * g->Ho * g->Wo - 1) * g->ld_out + g->Co) * 2;
-        if (ob >= (1ll << 31)) return 0;
-        a.out_bytes = (unsigned)ob;
+        if (!segnb_fits_desc(segnb_nhwc_bytes((long long)g->N * g->Ho * g->Wo, g->ld_out, g->Co, 2), &a.out_bytes)) return 0;
         a.dbg = 0;
         a.u = nullptr;
         a.up_out = nullptr;
@@ -1623,16 +1569,10 @@ int segnb_fprop_dma_try(segnb_try_outcome* did, const segnb_conv_geom* g, const 
         a.ep_coef = nullptr;
         a.ep_slope = 0.f;
         const int rc = try_upd(g, a, stream);
-        if (rc == NOT_HANDLED) return 0;
         return segnb_try_launched(did, rc);
     }
-    if (!segnb_taps_3x3(g) || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return 0;
-    if (g->QH != g->Ho || g->QW != g->Wo || g->Ci % 64 != 0) return 0;
-    int dhmin = g->dh[0], dwmin = g->dw[0];      // (segnb_taps_3x3 above: the spans are 2)
-    for (int t = 1; t < 9; ++t) {
-        dhmin = g->dh[t] < dhmin ? g->dh[t] : dhmin;
-        dwmin = g->dw[t] < dwmin ? g->dw[t] : dwmin;
-    }
+    if (!whole_output_3x3_s1(g) || g->Ci % 64 != 0) return 0;
+    const segnb_tap_win win = segnb_tap_window(g);
     FdArgs a;
     a.x = (const bf16_t*)in;
     a.w = (const bf16_t*)wpacked;
@@ -1645,16 +1585,9 @@ int segnb_fprop_dma_try(segnb_try_outcome* did, const segnb_conv_geom* g, const 
     a.N = g->N; a.H = g->Ho; a.W = g->Wo; a.Hi = g->Hi; a.Wi = g->Wi;
     a.Ci = g->Ci; a.Co = g->Co; a.ld_x = g->ld_in; a.ld_out = g->ld_out;
     a.Ktot = 9 * g->Ci;
-    {
-        const long long ob = (((long long)g->N * g->Ho * g->Wo - 1) * g->ld_out + g->Co) * 2;
-        if (ob >= (1ll << 31)) return 0;
-        a.out_bytes = (unsigned)ob;
-    }
-    a.dhmin = dhmin; a.dwmin = dwmin;
-    for (int t = 0; t < 9; ++t) {
-        a.dh[t] = g->dh[t] - dhmin;
-        a.dw[t] = g->dw[t] - dwmin;
-    }
+    if (!segnb_fits_desc(segnb_nhwc_bytes((long long)g->N * g->Ho * g->Wo, g->ld_out, g->Co, 2), &a.out_bytes)) return 0;
+    a.dhmin = win.dhmin; a.dwmin = win.dwmin;
+    segnb_rel_taps(g, win, a.dh, a.dw);
     a.dbg = segnb_knob_fprop_dma_dbg();
     a.up_out = nullptr;
     a.no_prev = 0;
@@ -1667,9 +1600,7 @@ int segnb_fprop_dma_try(segnb_try_outcome* did, const segnb_conv_geom* g, const 
         a.NCHU = uc->Cu / 64;
         a.Hu = g->Hi / 2;
         a.Wu = g->Wi / 2;
-        const long long ub = (((long long)g->N * a.Hu * a.Wu - 1) * uc->ld_u + uc->Cu) * 2;
-        if (ub >= (1ll << 31)) return 0;
-        a.u_bytes = (unsigned)ub;
+        if (!segnb_fits_desc(segnb_nhwc_bytes((long long)g->N * a.Hu * a.Wu, uc->ld_u, uc->Cu, 2), &a.u_bytes)) return 0;
     }
     a.bn_y = nullptr;
     a.bn_act = SEGNB_ACT_NONE;
@@ -1681,6 +1612,5 @@ int segnb_fprop_dma_try(segnb_try_outcome* did, const segnb_conv_geom* g, const 
     }
     take_act_epilogue(a, ep);
     const int rc = dispatch_fd(a, stream);
-    if (rc == NOT_HANDLED) return 0;
     return segnb_try_launched(did, rc);
 }

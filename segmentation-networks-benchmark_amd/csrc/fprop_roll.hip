@@ -607,17 +607,12 @@ int segnb_fprop_roll_try(segnb_try_outcome* did, const segnb_conv_geom* g, const
     *did = SEGNB_TRY_DECLINED;
     const int knob = segnb_knob_fprop_roll();
     if (!knob) return 0;
-    if (!segnb_taps_3x3(g) || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return 0;
-    if (g->QH != g->Ho || g->QW != g->Wo) return 0;
+    if (!whole_output_3x3_s1(g)) return 0;
     if (g->Co % 8 != 0 || g->Wo < 32 || g->ld_in % 8 != 0 || g->ld_out % 8 != 0) return 0;
-    int dhmin = g->dh[0], dwmin = g->dw[0];      // (segnb_taps_3x3 above: the spans are 2)
-    for (int t = 1; t < 9; ++t) {
-        dhmin = g->dh[t] < dhmin ? g->dh[t] : dhmin;
-        dwmin = g->dw[t] < dwmin ? g->dw[t] : dwmin;
-    }
+    const segnb_tap_win win = segnb_tap_window(g);
     // same-size (padding 1) everywhere; another padding (the valid 3 x 3 convolution of lib/models/linknet.py:60 and its data
     // gradient: input and output grids differ) only for the plain one-wave form
-    const bool same = g->Hi == g->Ho && g->Wi == g->Wo && dhmin == -1 && dwmin == -1;
+    const bool same = g->Hi == g->Ho && g->Wi == g->Wo && win.dhmin == -1 && win.dwmin == -1;
     // (the epilogues address y by OUTPUT pixel: they do not care about the input grid)
     if (!same && (tf != nullptr || uc != nullptr || g->Ci != 32 || g->Co > 32)) return 0;
     if (bn != nullptr && bn->coef == nullptr && (tf != nullptr || g->Ci != 32 || g->Co > 32)) return 0;      // (activation mask: plain form)
@@ -633,14 +628,10 @@ int segnb_fprop_roll_try(segnb_try_outcome* did, const segnb_conv_geom* g, const
     const bool csplit = g->Ci == 32 && g->Co == 64 && bn == nullptr && tf == nullptr && knob >= 2;
     if (!plain1 && !ksplit && !csplit) return 0;
     RollArgs a;
-    bool seen[9] = {false, false, false, false, false, false, false, false, false};
-    for (int t = 0; t < 9; ++t) {
-        const int k = (g->dh[t] - dhmin) * 3 + (g->dw[t] - dwmin);
-        if (seen[k]) return 0;
-        seen[k] = true;
-        a.tap[k] = t;
-    }
-    a.Hi = g->Hi; a.Wi = g->Wi; a.dhmin = dhmin; a.dwmin = dwmin;
+    int k_of_tap[9];
+    if (!segnb_window_once_3x3(g, win, k_of_tap)) return 0;
+    for (int t = 0; t < 9; ++t) a.tap[k_of_tap[t]] = t;
+    a.Hi = g->Hi; a.Wi = g->Wi; a.dhmin = win.dhmin; a.dwmin = win.dwmin;
     a.x = (const bf16_t*)in;
     a.w = (const bf16_t*)wpacked;
     a.bias = bias;
@@ -649,11 +640,7 @@ int segnb_fprop_roll_try(segnb_try_outcome* did, const segnb_conv_geom* g, const
     a.stats = stats;
     a.x_bytes = in_bytes;
     a.w_bytes = w_bytes;
-    {
-        const long long ob = (((long long)g->N * g->Ho * g->Wo - 1) * g->ld_out + g->Co) * 2;
-        if (ob >= (1ll << 31)) return 0;
-        a.out_bytes = (unsigned)ob;
-    }
+    if (!segnb_fits_desc(segnb_nhwc_bytes((long long)g->N * g->Ho * g->Wo, g->ld_out, g->Co, 2), &a.out_bytes)) return 0;
     a.N = g->N; a.H = g->Ho; a.W = g->Wo;
     a.Ci = g->Ci; a.Co = g->Co; a.ld_x = g->ld_in; a.ld_out = g->ld_out;
     a.Ktot = 9 * g->Ci;
@@ -686,10 +673,8 @@ int segnb_fprop_roll_try(segnb_try_outcome* did, const segnb_conv_geom* g, const
             rc = launch_roll<1, 2, 1, 1, 3, 2>(a, stream);
         } else if (tf->kind == SEGNB_TF_BNBWD) {
             if (tf->y == nullptr || tf->bcoef == nullptr || stats != nullptr || tf->ld_y % 8 != 0) return 0;
-            const long long yb = (((long long)g->N * g->Hi * g->Wi - 1) * tf->ld_y + g->Ci) * 2;
-            if (yb >= (1ll << 31)) return 0;
+            if (!segnb_fits_desc(segnb_nhwc_bytes((long long)g->N * g->Hi * g->Wi, tf->ld_y, g->Ci, 2), &a.x2_bytes)) return 0;
             a.x2 = (const bf16_t*)tf->y;
-            a.x2_bytes = (unsigned)yb;
             a.ld_x2 = tf->ld_y;
             rc = launch_roll<1, 2, 1, 2, 3, 2>(a, stream);
         } else {
@@ -712,31 +697,19 @@ extern "C" int segnb_conv_fprop_actmask_ok(const segnb_conv_geom* g, int dtype) 
 // conv_roll_kernel, EPI = 3 (32 -> <= 32 channels)
 int segnb_fprop_roll_actmask_ok(const segnb_conv_geom* g) {
     if (!segnb_knob_fprop_roll() || segnb_fprop_general_forced()) return 0;
-    if (!segnb_taps_3x3(g) || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return 0;
-    if (g->QH != g->Ho || g->QW != g->Wo || g->Ci != 32 || g->Co > 32 || g->Co % 8 != 0 || g->Wo < 32) return 0;
+    if (!whole_output_3x3_s1(g) || g->Ci != 32 || g->Co > 32 || g->Co % 8 != 0 || g->Wo < 32) return 0;
     if (g->ld_in % 8 != 0 || g->ld_out % 8 != 0) return 0;
-    int dhmin = g->dh[0], dwmin = g->dw[0];      // (segnb_taps_3x3 above: the spans are 2)
-    bool seen[9] = {false, false, false, false, false, false, false, false, false};
-    for (int t = 1; t < 9; ++t) {
-        dhmin = g->dh[t] < dhmin ? g->dh[t] : dhmin;
-        dwmin = g->dw[t] < dwmin ? g->dw[t] : dwmin;
-    }
-    for (int t = 0; t < 9; ++t) {
-        const int k = (g->dh[t] - dhmin) * 3 + (g->dw[t] - dwmin);
-        if (seen[k]) return 0;
-        seen[k] = true;
-    }
-    return (((long long)g->N * g->Ho * g->Wo - 1) * g->ld_out + g->Co) * 2 < (1ll << 31) ? 1 : 0;
+    if (!segnb_window_once_3x3(g, segnb_tap_window(g))) return 0;
+    return segnb_fits_desc(segnb_nhwc_bytes((long long)g->N * g->Ho * g->Wo, g->ld_out, g->Co, 2)) ? 1 : 0;
 }
 
 static bool roll_tf_geom_ok(const segnb_conv_geom* g, int dtype) {
     if (g == nullptr || dtype != SEGNB_BF16 || !segnb_knob_fprop_roll() || segnb_fprop_general_forced()) return false;
-    if (!segnb_taps_3x3(g) || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return false;
-    if (g->QH != g->Ho || g->QW != g->Wo || g->Hi != g->Ho || g->Wi != g->Wo) return false;
+    if (!whole_output_3x3_s1(g) || g->Hi != g->Ho || g->Wi != g->Wo) return false;
     if (g->Ci != 32 || g->Co > 32 || g->Co % 8 != 0 || g->Wo < 32 || g->ld_in % 8 != 0 || g->ld_out % 8 != 0) return false;
     for (int t = 0; t < 9; ++t)
         if (g->dh[t] < -1 || g->dh[t] > 1 || g->dw[t] < -1 || g->dw[t] > 1) return false;
-    return (((long long)g->N * g->Ho * g->Wo - 1) * g->ld_out + g->Co) * 2 < (1ll << 31);
+    return segnb_fits_desc(segnb_nhwc_bytes((long long)g->N * g->Ho * g->Wo, g->ld_out, g->Co, 2));
 }
 
 // include/segnb_hip.h: convolution whose input operand is recomputed from what the producing layer left in memory
@@ -755,11 +728,12 @@ extern "C" int segnb_conv_fprop_tf(const segnb_conv_geom* g, int dtype, const vo
                     "bad BNBWD transform (a dropout layer hands over dz with act = NONE)");
     SEGNB_CHECK_ARG(tf->kind != SEGNB_TF_ACT || bn == nullptr, "a forward launch has no BatchNorm-reduce epilogue");
     SEGNB_CHECK_ARG(bn == nullptr || (bn->y && bn->coef && bn->sums && bn->ld_y >= g->Co && bn->ld_y % 8 == 0), "bad epilogue");
-    const long long inb = (((long long)g->N * g->Hi * g->Wi - 1) * g->ld_in + g->Ci) * 2;
-    const long long wb = (long long)g->Co * g->ntaps * g->Ci * 2;
-    SEGNB_CHECK_ARG(inb < (1ll << 31) && wb < (1ll << 31), "tensor larger than 2 GiB (32-bit buffer offsets)");
+    unsigned inb;
+    const long long wb = (long long)g->Co * g->ntaps * g->Ci * 2;      // (the weight matrix: another statement than an NHWC extent)
+    SEGNB_CHECK_ARG(segnb_fits_desc(segnb_nhwc_bytes((long long)g->N * g->Hi * g->Wi, g->ld_in, g->Ci, 2), &inb) && wb < (1ll << 31),
+                    "tensor larger than 2 GiB (32-bit buffer offsets)");
     segnb_try_outcome did;
-    if (int rc = segnb_fprop_roll_try(&did, g, in, (unsigned)inb, wpacked, (unsigned)wb, bias, bias_n, out, stats, (hipStream_t)stream,
+    if (int rc = segnb_fprop_roll_try(&did, g, in, inb, wpacked, (unsigned)wb, bias, bias_n, out, stats, (hipStream_t)stream,
                                       bn, tf))
         return rc;
     if (did == SEGNB_TRY_DECLINED) {

@@ -463,20 +463,10 @@ __global__ __launch_bounds__(C::NT) void conv_fprop_rw_kernel(const FdArgs a) {
 
 template <class C>
 int launch_rw(FdArgs& a, hipStream_t stream) {
-    static int attr_rc = [] {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fprop_rw_kernel<C, false>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fprop_rw_kernel<C, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fprop_rw_kernel<C, false, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM);
-        if (e != hipSuccess) segnb_set_error("fprop_rw hipFuncSetAttribute: %s", hipGetErrorString(e));
-        return (int)e;
-    }();
+    static const int attr_rc = segnb_opt_in_lds("fprop_rw", C::SMEM, conv_fprop_rw_kernel<C, false>, conv_fprop_rw_kernel<C, true>,
+                                                conv_fprop_rw_kernel<C, false, true>);
     if (attr_rc) return attr_rc;
-    if (a.NCH * 9 * C::BN * 64 > C::W_MAX) return -12345;
+    if (a.NCH * 9 * C::BN * 64 > C::W_MAX) return SEGNB_LAUNCH_DECLINED;
     a.HB = (a.H + C::R - 1) / C::R;
     a.WB = (a.W + C::WT - 1) / C::WT;
     a.IT = a.N * a.HB * a.WB;
@@ -501,13 +491,8 @@ int segnb_fprop_rw_try(segnb_try_outcome* did, const segnb_conv_geom* g, const v
                        const segnb_upcat_src* uc, const segnb_upcat_src* upsum) {
     *did = SEGNB_TRY_DECLINED;
     if (!segnb_knob_fprop_dma() || !segnb_knob_fprop_rw()) return 0;
-    if (!segnb_taps_3x3(g) || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return 0;
-    if (g->QH != g->Ho || g->QW != g->Wo || g->Ci % 32 != 0 || g->Ci > 96 || g->Co > 96 || g->Wo < 12) return 0;
-    int dhmin = g->dh[0], dwmin = g->dw[0];      // (segnb_taps_3x3 above: the spans are 2)
-    for (int t = 1; t < 9; ++t) {
-        dhmin = g->dh[t] < dhmin ? g->dh[t] : dhmin;
-        dwmin = g->dw[t] < dwmin ? g->dw[t] : dwmin;
-    }
+    if (!whole_output_3x3_s1(g) || g->Ci % 32 != 0 || g->Ci > 96 || g->Co > 96 || g->Wo < 12) return 0;
+    const segnb_tap_win win = segnb_tap_window(g);
     FdArgs a;
     a.x = (const bf16_t*)in;
     a.w = (const bf16_t*)wpacked;
@@ -521,16 +506,9 @@ int segnb_fprop_rw_try(segnb_try_outcome* did, const segnb_conv_geom* g, const v
     a.Ci = g->Ci; a.Co = g->Co; a.ld_x = g->ld_in; a.ld_out = g->ld_out;
     a.Ktot = 9 * g->Ci;
     a.NCH = g->Ci / 32;
-    {
-        const long long ob = (((long long)g->N * g->Ho * g->Wo - 1) * g->ld_out + g->Co) * 2;
-        if (ob >= (1ll << 31)) return 0;
-        a.out_bytes = (unsigned)ob;
-    }
-    a.dhmin = dhmin; a.dwmin = dwmin;
-    for (int t = 0; t < 9; ++t) {
-        a.dh[t] = g->dh[t] - dhmin;
-        a.dw[t] = g->dw[t] - dwmin;
-    }
+    if (!segnb_fits_desc(segnb_nhwc_bytes((long long)g->N * g->Ho * g->Wo, g->ld_out, g->Co, 2), &a.out_bytes)) return 0;
+    a.dhmin = win.dhmin; a.dwmin = win.dwmin;
+    segnb_rel_taps(g, win, a.dh, a.dw);
     a.dbg = segnb_knob_fprop_dma_dbg();
     a.up_out = nullptr;
     a.no_prev = 0;
@@ -552,9 +530,7 @@ int segnb_fprop_rw_try(segnb_try_outcome* did, const segnb_conv_geom* g, const v
         a.NCHU = uc->Cu / 32;
         a.Hu = g->Hi / 2;
         a.Wu = g->Wi / 2;
-        const long long ub = (((long long)g->N * a.Hu * a.Wu - 1) * uc->ld_u + uc->Cu) * 2;
-        if (ub >= (1ll << 31)) return 0;
-        a.u_bytes = (unsigned)ub;
+        if (!segnb_fits_desc(segnb_nhwc_bytes((long long)g->N * a.Hu * a.Wu, uc->ld_u, uc->Cu, 2), &a.u_bytes)) return 0;
     }
     a.bn_y = nullptr;
     take_act_epilogue(a, ep);
@@ -584,6 +560,5 @@ int segnb_fprop_rw_try(segnb_try_outcome* did, const segnb_conv_geom* g, const v
         rc = launch_rw<RwCfg<96, 2>>(a, stream);
     else
         return 0;
-    if (rc == -12345) return 0;
     return segnb_try_launched(did, rc);
 }

@@ -302,12 +302,7 @@ __global__ __launch_bounds__(256) void conv_fprop_s1x9_kernel(const FpS1Args a) 
 template <int BN, int R, int WT, int WAVES_M, int BKC, int TPS = 1>
 int launch_fs1(FpS1Args& a, hipStream_t stream) {
     using C = FpS1Cfg<BN, R, WT, WAVES_M, BKC, TPS>;
-    static int attr_rc = [] {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fprop_s1x9_kernel<BN, R, WT, WAVES_M, BKC, TPS>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM);
-        if (e != hipSuccess) segnb_set_error("fprop_s1 hipFuncSetAttribute: %s", hipGetErrorString(e));
-        return (int)e;
-    }();
+    static const int attr_rc = segnb_opt_in_lds("fprop_s1", C::SMEM, conv_fprop_s1x9_kernel<BN, R, WT, WAVES_M, BKC, TPS>);
     if (attr_rc) return attr_rc;
     a.HB = (a.H + R - 1) / R;
     a.WB = (a.W + WT - 1) / WT;
@@ -326,8 +321,6 @@ int launch_fs1(FpS1Args& a, hipStream_t stream) {
     return 0;
 }
 
-constexpr int NOT_HANDLED = -12345;
-
 template <int BKC>
 int dispatch_fs1(FpS1Args& a, hipStream_t stream) {
     const int cus = segnb_num_cus();
@@ -341,14 +334,14 @@ int dispatch_fs1(FpS1Args& a, hipStream_t stream) {
             return launch_fs1<64, 4, 32, 2, BKC>(a, stream);
         // wide layers on >= 28-pixel rows: the general gather kernel's flattened-pixel 128x128 tiles (no partial
         // row segments, one barrier per step) measure 20-25 % faster than the image-tile form here
-        return NOT_HANDLED;
+        return SEGNB_LAUNCH_DECLINED;
     }
     // measured per layer on MI355X (tools/layer_bench.py, after the general kernel got buffer-descriptor gathers):
     //   8 < W <= 16 : 64-channel tiles here (2 blocks / CU) beat both the 128-channel tiles (-20 %) and the general
     //                 kernel, except for very wide outputs (Co > 1024: the data gradient of a concat layer)
     //   W <= 8      : the general kernel's flattened 128x128 tiles are 25 % faster than 8x8 image tiles
     if (a.W > 8 && a.Co <= 1024) return launch_fs1<64, 8, 16, 2, BKC>(a, stream);
-    return NOT_HANDLED;
+    return SEGNB_LAUNCH_DECLINED;
 }
 
 }  // namespace
@@ -357,13 +350,8 @@ int dispatch_fs1(FpS1Args& a, hipStream_t stream) {
 int segnb_fprop_s1_try(segnb_try_outcome* did, const segnb_conv_geom* g, const void* in, const void* wpacked, const float* bias, int bias_n,
                        void* out, double* stats, hipStream_t stream, const float* drop, int ld_drop, int stats_ld) {
     *did = SEGNB_TRY_DECLINED;
-    if (!segnb_taps_3x3(g) || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return 0;
-    if (g->QH != g->Ho || g->QW != g->Wo || g->Ci < 32) return 0;
-    int dhmin = g->dh[0], dwmin = g->dw[0];      // (segnb_taps_3x3 above: the spans are 2)
-    for (int t = 1; t < 9; ++t) {
-        dhmin = g->dh[t] < dhmin ? g->dh[t] : dhmin;
-        dwmin = g->dw[t] < dwmin ? g->dw[t] : dwmin;
-    }
+    if (!whole_output_3x3_s1(g) || g->Ci < 32) return 0;
+    const segnb_tap_win win = segnb_tap_window(g);
     FpS1Args a;
     a.x = (const bf16_t*)in;
     a.w = (const bf16_t*)wpacked;
@@ -377,12 +365,8 @@ int segnb_fprop_s1_try(segnb_try_outcome* did, const segnb_conv_geom* g, const v
     a.N = g->N; a.H = g->Ho; a.W = g->Wo; a.Hi = g->Hi; a.Wi = g->Wi;
     a.Ci = g->Ci; a.Co = g->Co; a.ld_x = g->ld_in; a.ld_out = g->ld_out;
     a.Ktot = 9 * g->Ci;
-    a.dhmin = dhmin; a.dwmin = dwmin;
-    for (int t = 0; t < 9; ++t) {
-        a.dh[t] = g->dh[t] - dhmin;
-        a.dw[t] = g->dw[t] - dwmin;
-    }
+    a.dhmin = win.dhmin; a.dwmin = win.dwmin;
+    segnb_rel_taps(g, win, a.dh, a.dw);
     const int rc = (g->Ci % 64 == 0) ? dispatch_fs1<64>(a, stream) : dispatch_fs1<32>(a, stream);
-    if (rc == NOT_HANDLED) return 0;
     return segnb_try_launched(did, rc);
 }

@@ -271,12 +271,7 @@ __global__ __launch_bounds__(256, 1) void conv_fprop_sx_kernel(const FxArgs a) {
 template <int S, int BCI, int R, int WT, int KH, int KW, int BCO>
 int launch_fx(FxArgs& a, hipStream_t stream) {
     using C = FxCfg<S, BCI, R, WT, KH, KW, BCO>;
-    static int attr_rc = [] {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fprop_sx_kernel<S, BCI, R, WT, KH, KW, BCO>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM);
-        if (e != hipSuccess) segnb_set_error("fprop_sx hipFuncSetAttribute: %s", hipGetErrorString(e));
-        return (int)e;
-    }();
+    static const int attr_rc = segnb_opt_in_lds("fprop_sx", C::SMEM, conv_fprop_sx_kernel<S, BCI, R, WT, KH, KW, BCO>);
     if (attr_rc) return attr_rc;
     a.HB = (a.QH + R - 1) / R;
     a.WB = (a.QW + WT - 1) / WT;
@@ -299,21 +294,14 @@ int segnb_fprop_sx_try(segnb_try_outcome* did, const segnb_conv_geom* g, const v
                        int bias_n, void* out, double* stats, hipStream_t stream) {
     *did = SEGNB_TRY_DECLINED;
     if ((g->in_step != 1 && g->in_step != 2) || g->QW < 24 || g->ntaps > 49) return 0;
-    int dhmin = g->dh[0], dhmax = g->dh[0], dwmin = g->dw[0], dwmax = g->dw[0];
-    for (int t = 1; t < g->ntaps; ++t) {
-        dhmin = g->dh[t] < dhmin ? g->dh[t] : dhmin;
-        dhmax = g->dh[t] > dhmax ? g->dh[t] : dhmax;
-        dwmin = g->dw[t] < dwmin ? g->dw[t] : dwmin;
-        dwmax = g->dw[t] > dwmax ? g->dw[t] : dwmax;
-    }
-    const int kh = dhmax - dhmin + 1, kw = dwmax - dwmin + 1;
-    if (g->ntaps > kh * kw) return 0;                               // (a repeated tap: not a window)
+    const segnb_tap_win win = segnb_tap_window(g);
+    if (g->ntaps > win.kh * win.kw) return 0;                       // (a repeated tap: not a window)
     // Served: the 8-channel stride-2 stem (linknet.py:16: 183 -> 148 us at 512x512 bs=16).  The template also instantiates for
     // 3x3 / 1x1 stride 2, the 2x2-window phases of transposed convolutions, 2x2 and 1x1 stride 1 and 16-channel-multiple 3x3
     // (all parity-tested once), but there one (tile, chunk) item is 8-40 MFMAs behind three barriers and a staged store, and
     // the general gather kernel with five resident blocks per CU was 10-120 us faster per launch (profiles/r03_ab.txt):
     // LinkNet34 1955 -> 1869 images/s with all of them on.  They are not dispatched.
-    if (g->in_step != 2 || kh > 7 || kw > 7 || g->Ci != 8) return 0;
+    if (g->in_step != 2 || win.kh > 7 || win.kw > 7 || g->Ci != 8) return 0;
     FxArgs a;
     a.x = (const bf16_t*)in;
     a.w = (const bf16_t*)wpacked;
@@ -324,11 +312,8 @@ int segnb_fprop_sx_try(segnb_try_outcome* did, const segnb_conv_geom* g, const v
     a.N = g->N; a.QH = g->QH; a.QW = g->QW; a.Hi = g->Hi; a.Wi = g->Wi; a.Ho = g->Ho; a.Wo = g->Wo;
     a.out_step = g->out_step; a.oh0 = g->oh0; a.ow0 = g->ow0;
     a.Ci = g->Ci; a.Co = g->Co; a.ld_x = g->ld_in; a.ld_out = g->ld_out;
-    a.dhmin = dhmin; a.dwmin = dwmin; a.ntaps = g->ntaps;
-    for (int t = 0; t < g->ntaps; ++t) {
-        a.dh[t] = (signed char)(g->dh[t] - dhmin);
-        a.dw[t] = (signed char)(g->dw[t] - dwmin);
-    }
+    a.dhmin = win.dhmin; a.dwmin = win.dwmin; a.ntaps = g->ntaps;
+    segnb_rel_taps(g, win, a.dh, a.dw);
     const int rc = launch_fx<2, 8, 8, 32, 7, 7, 64>(a, stream);
     return segnb_try_launched(did, rc);
 }

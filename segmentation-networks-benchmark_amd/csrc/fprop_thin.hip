@@ -256,16 +256,14 @@ __global__ __launch_bounds__(256, 2) void conv_thin_kernel(const ThinArgs a) {
 }
 
 bool thin_geometry(const segnb_conv_geom* g) {
-    if (!segnb_taps_3x3(g) || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return false;
-    if (g->QH != g->Ho || g->QW != g->Wo || g->Hi != g->Ho || g->Wi != g->Wo) return false;
+    if (!whole_output_3x3_s1(g) || g->Hi != g->Ho || g->Wi != g->Wo) return false;
     if ((g->Ci != 8 && g->Ci != 16) || g->Co % 8 != 0 || g->Co < 48 || g->Co > TH_MAXC) return false;
     // (measured, tools/dense_dgrad_bench.py: from 8 x 32 x 32 pixels up this kernel wins -- 15.6 vs 18.4 us with the reduction at 656
     // channels -- below, the general kernel's channel-parallel tiles do: 9.9 vs 12.8 us at 8 x 16 x 16 x 896)
     if ((long long)g->N * g->Ho * g->Wo < 4096) return false;
     if (g->ld_in % 8 != 0 || g->ld_out % 8 != 0) return false;
-    const long long ob = (((long long)g->N * g->Ho * g->Wo - 1) * g->ld_out + g->Co) * 2;
-    const long long ib = (((long long)g->N * g->Hi * g->Wi - 1) * g->ld_in + g->Ci) * 2;
-    return ob < (1ll << 31) && ib < (1ll << 31);
+    return segnb_fits_desc(segnb_nhwc_bytes((long long)g->N * g->Ho * g->Wo, g->ld_out, g->Co, 2)) &&
+           segnb_fits_desc(segnb_nhwc_bytes((long long)g->N * g->Hi * g->Wi, g->ld_in, g->Ci, 2));
 }
 
 }  // namespace
@@ -278,9 +276,9 @@ int segnb_fprop_thin_try(segnb_try_outcome* did, const segnb_conv_geom* g, const
     a.x = (const bf16_t*)in;
     a.w = (const bf16_t*)wpacked;
     a.out = (bf16_t*)out;
-    a.x_bytes = (unsigned)((((long long)g->N * g->Hi * g->Wi - 1) * g->ld_in + g->Ci) * 2);
+    a.x_bytes = (unsigned)segnb_nhwc_bytes((long long)g->N * g->Hi * g->Wi, g->ld_in, g->Ci, 2);      // (both fit: thin_geometry)
     a.w_bytes = (unsigned)((long long)g->Co * 9 * g->Ci * 2);
-    a.out_bytes = (unsigned)((((long long)g->N * g->Ho * g->Wo - 1) * g->ld_out + g->Co) * 2);
+    a.out_bytes = (unsigned)segnb_nhwc_bytes((long long)g->N * g->Ho * g->Wo, g->ld_out, g->Co, 2);
     a.N = g->N; a.H = g->Ho; a.W = g->Wo; a.Ci = g->Ci; a.Co = g->Co; a.ld_x = g->ld_in; a.ld_out = g->ld_out;
     for (int t = 0; t < 9; ++t) {
         a.dh[t] = g->dh[t];

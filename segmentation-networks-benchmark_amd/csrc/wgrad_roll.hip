@@ -332,12 +332,7 @@ __global__ __launch_bounds__(WR_WAVES * 64, 2) void conv_wgrad_roll_kernel(const
 
 template <int TFX, int TFD, int DL>
 int launch_wroll_dl(WRollArgs& a, int nslab, hipStream_t stream) {
-    static int attr_rc = [] {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_roll_kernel<TFX, TFD, DL>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, WR_SMEM);
-        if (e != hipSuccess) segnb_set_error("wgrad_roll hipFuncSetAttribute: %s", hipGetErrorString(e));
-        return (int)e;
-    }();
+    static const int attr_rc = segnb_opt_in_lds("wgrad_roll", WR_SMEM, conv_wgrad_roll_kernel<TFX, TFD, DL>);
     if (attr_rc) return attr_rc;
     a.NCOH = (a.Co + 15) / 16;
     a.NSTRIP = (a.W + 31) / 32;
@@ -585,12 +580,7 @@ __global__ __launch_bounds__(NW * 64, 1) void conv_wgrad_c8roll_kernel(const WRo
 
 template <int TFD, int DL, int NW, int COH>
 int launch_c8roll_nw(WRollArgs& a, int nslab, hipStream_t stream) {
-    static int attr_rc = [] {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_c8roll_kernel<TFD, DL, NW, COH>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, w8_smem<NW, COH>());
-        if (e != hipSuccess) segnb_set_error("wgrad_c8roll hipFuncSetAttribute: %s", hipGetErrorString(e));
-        return (int)e;
-    }();
+    static const int attr_rc = segnb_opt_in_lds("wgrad_c8roll", w8_smem<NW, COH>(), conv_wgrad_c8roll_kernel<TFD, DL, NW, COH>);
     if (attr_rc) return attr_rc;
     a.NCOH = 1;
     a.NSTRIP = (a.W + 31) / 32;
@@ -626,17 +616,11 @@ int launch_c8roll(WRollArgs& a, int nslab, hipStream_t stream) {
 }  // namespace
 
 bool segnb_wgrad_roll_applies(const segnb_conv_geom* g) {
-    if (!segnb_taps_3x3(g) || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return false;
-    if (g->QH != g->Ho || g->QW != g->Wo || g->Hi != g->Ho || g->Wi != g->Wo) return false;
+    if (!whole_output_3x3_s1(g) || g->Hi != g->Ho || g->Wi != g->Wo) return false;
     if (g->Ci != 32 || g->Co > 32 || g->Co % 8 != 0 || g->Wo < 32 || g->ld_in % 8 != 0 || g->ld_out % 8 != 0) return false;
-    bool seen[9] = {false, false, false, false, false, false, false, false, false};
-    for (int t = 0; t < 9; ++t) {
+    for (int t = 0; t < 9; ++t)          // (padding 1: the window's origin is (-1, -1), as the tap table of the try assumes)
         if (g->dh[t] < -1 || g->dh[t] > 1 || g->dw[t] < -1 || g->dw[t] > 1) return false;
-        const int k = (g->dh[t] + 1) * 3 + (g->dw[t] + 1);
-        if (seen[k]) return false;
-        seen[k] = true;
-    }
-    return true;
+    return segnb_window_once_3x3(g, segnb_tap_window(g));
 }
 
 // nslab: the slab count of the workspace (segnb_conv_wgrad_slabs): one block per
@@ -653,11 +637,9 @@ int segnb_wgrad_roll_try(segnb_try_outcome* did, const segnb_conv_geom* g, const
     a.ld_x = g->ld_in;
     a.ld_d = g->ld_out;
     a.ld_d2 = 0;
-    const long long xb = (((long long)g->N * g->Hi * g->Wi - 1) * g->ld_in + g->Ci) * 2;
-    const long long db = (((long long)g->N * g->Ho * g->Wo - 1) * g->ld_out + g->Co) * 2;
-    if (xb >= (1ll << 31) || db >= (1ll << 31)) return 0;
-    a.x_bytes = (unsigned)xb;
-    a.d_bytes = (unsigned)db;
+    if (!segnb_fits_desc(segnb_nhwc_bytes((long long)g->N * g->Hi * g->Wi, g->ld_in, g->Ci, 2), &a.x_bytes) ||
+        !segnb_fits_desc(segnb_nhwc_bytes((long long)g->N * g->Ho * g->Wo, g->ld_out, g->Co, 2), &a.d_bytes))
+        return 0;
     a.d2_bytes = 0;
     a.dwp = dwp;
     a.N = g->N; a.H = g->Ho; a.W = g->Wo; a.Ci = g->Ci; a.Co = g->Co;
@@ -679,10 +661,8 @@ int segnb_wgrad_roll_try(segnb_try_outcome* did, const segnb_conv_geom* g, const
         if (tfd->kind != SEGNB_TF_BNBWD || tfd->coef == nullptr || tfd->bcoef == nullptr || tfd->y == nullptr || tfd->drop != nullptr ||
             tfd->Cp < g->Co || tfd->ld_y % 8 != 0)
             return 0;
-        const long long yb = (((long long)g->N * g->Ho * g->Wo - 1) * tfd->ld_y + g->Co) * 2;
-        if (yb >= (1ll << 31)) return 0;
+        if (!segnb_fits_desc(segnb_nhwc_bytes((long long)g->N * g->Ho * g->Wo, tfd->ld_y, g->Co, 2), &a.d2_bytes)) return 0;
         a.d2 = (const bf16_t*)tfd->y;
-        a.d2_bytes = (unsigned)yb;
         a.ld_d2 = tfd->ld_y;
         a.tfd_coef = tfd->coef;
         a.tfd_bcoef = tfd->bcoef;
@@ -702,17 +682,11 @@ int segnb_wgrad_roll_try(segnb_try_outcome* did, const segnb_conv_geom* g, const
 }
 
 bool segnb_wgrad_c8roll_applies(const segnb_conv_geom* g) {
-    if (!segnb_taps_3x3(g) || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return false;
-    if (g->QH != g->Ho || g->QW != g->Wo || g->Hi != g->Ho || g->Wi != g->Wo) return false;
+    if (!whole_output_3x3_s1(g) || g->Hi != g->Ho || g->Wi != g->Wo) return false;
     if (g->Ci != 8 || g->Co > 32 || g->Co % 8 != 0 || g->Wo < 32 || g->ld_in % 8 != 0 || g->ld_out % 8 != 0) return false;
-    bool seen[9] = {false, false, false, false, false, false, false, false, false};
-    for (int t = 0; t < 9; ++t) {
+    for (int t = 0; t < 9; ++t)          // (padding 1: the window's origin is (-1, -1), as the tap table of the try assumes)
         if (g->dh[t] < -1 || g->dh[t] > 1 || g->dw[t] < -1 || g->dw[t] > 1) return false;
-        const int k = (g->dh[t] + 1) * 3 + (g->dw[t] + 1);
-        if (seen[k]) return false;
-        seen[k] = true;
-    }
-    return true;
+    return segnb_window_once_3x3(g, segnb_tap_window(g));
 }
 
 // the first layer's weight gradient (conv_wgrad_c8roll_kernel).  bna: dy recomputed from (g, y) (dout is then ignored)
@@ -725,7 +699,7 @@ int segnb_wgrad_c8roll_try(segnb_try_outcome* did, const segnb_conv_geom* g, con
     const long long npix = (long long)g->N * g->Ho * g->Wo;
     a.x = (const bf16_t*)in;
     a.ld_x = g->ld_in;
-    const long long xb = ((npix - 1) * g->ld_in + g->Ci) * 2;
+    const long long xb = segnb_nhwc_bytes(npix, g->ld_in, g->Ci, 2);
     long long db, d2b = 0;
     if (bna != nullptr) {
         if (bna->ld_g % 8 != 0 || bna->ld_y % 8 != 0 || bna->Cp < g->Co) return 0;
@@ -733,8 +707,8 @@ int segnb_wgrad_c8roll_try(segnb_try_outcome* did, const segnb_conv_geom* g, con
         a.ld_d = bna->ld_g;
         a.d2 = (const bf16_t*)bna->y;
         a.ld_d2 = bna->ld_y;
-        db = ((npix - 1) * bna->ld_g + g->Co) * 2;
-        d2b = ((npix - 1) * bna->ld_y + g->Co) * 2;
+        db = segnb_nhwc_bytes(npix, bna->ld_g, g->Co, 2);
+        d2b = segnb_nhwc_bytes(npix, bna->ld_y, g->Co, 2);
         a.tfd_coef = bna->coef;
         a.tfd_bcoef = bna->bcoef;
         a.tfd_Cp = bna->Cp;
@@ -745,16 +719,13 @@ int segnb_wgrad_c8roll_try(segnb_try_outcome* did, const segnb_conv_geom* g, con
         a.ld_d = g->ld_out;
         a.d2 = nullptr;
         a.ld_d2 = 0;
-        db = ((npix - 1) * g->ld_out + g->Co) * 2;
+        db = segnb_nhwc_bytes(npix, g->ld_out, g->Co, 2);
         a.tfd_coef = a.tfd_bcoef = nullptr;
         a.tfd_Cp = 0;
         a.tfd_act = 0;
         a.tfd_slope = 0.f;
     }
-    if (xb >= (1ll << 31) || db >= (1ll << 31) || d2b >= (1ll << 31)) return 0;
-    a.x_bytes = (unsigned)xb;
-    a.d_bytes = (unsigned)db;
-    a.d2_bytes = (unsigned)d2b;
+    if (!segnb_fits_desc(xb, &a.x_bytes) || !segnb_fits_desc(db, &a.d_bytes) || !segnb_fits_desc(d2b, &a.d2_bytes)) return 0;
     a.dwp = dwp;
     a.N = g->N; a.H = g->Ho; a.W = g->Wo; a.Ci = g->Ci; a.Co = g->Co;
     a.Ktot = 9 * g->Ci;

@@ -1009,12 +1009,7 @@ int launch_s1(WgS1Args& a, int nslab, hipStream_t stream, bool partial, const se
     constexpr int tile_bytes = TL::XROWS * lds_stride(BCI) + TL::YROWS * lds_stride(BCO);
     constexpr int smem = wg_ws_db<BCO, BCI, R, WT, FLAT>() ? 2 * tile_bytes : tile_bytes;
     static_assert(smem <= 160 * 1024, "tiles fit the LDS");
-    static int attr_rc = [] {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_s1x9_kernel<BCO, BCI, R, WT, FLAT, BNA>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        if (e != hipSuccess) segnb_set_error("wgrad_s1 hipFuncSetAttribute: %s", hipGetErrorString(e));
-        return (int)e;
-    }();
+    static const int attr_rc = segnb_opt_in_lds("wgrad_s1", smem, conv_wgrad_s1x9_kernel<BCO, BCI, R, WT, FLAT, BNA>);
     if (attr_rc) return attr_rc;
     a.HB = (a.H + R - 1) / R;
     a.WB = (a.W + WT - 1) / WT;
@@ -1059,13 +1054,7 @@ struct S1Choice {
 };
 S1Choice s1_choose(const segnb_conv_geom* g) {
     S1Choice c = {0, 0, 0};
-    if (!segnb_taps_3x3(g) || g->in_step != 1 || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0) return c;
-    if (g->QH != g->Ho || g->QW != g->Wo) return c;
-    int dhmin = g->dh[0], dwmin = g->dw[0];      // (segnb_taps_3x3 above: the spans are 2)
-    for (int t = 1; t < 9; ++t) {
-        dhmin = g->dh[t] < dhmin ? g->dh[t] : dhmin;
-        dwmin = g->dw[t] < dwmin ? g->dw[t] : dwmin;
-    }
+    if (!whole_output_3x3_s1(g)) return c;
     const bool thin = g->Co <= 32 || g->Ci <= 32;
     if (thin) {
         if (g->Wo < 24) return c;
@@ -1284,7 +1273,7 @@ struct SxChoice {
 SxChoice sx_choose(const segnb_conv_geom* g) {
     SxChoice c = {0, 0, 64};
     static const bool off = getenv("SEGNB_WGRAD_SX") != nullptr && getenv("SEGNB_WGRAD_SX")[0] == '0';
-    if (off || g->out_step != 1 || g->oh0 != 0 || g->ow0 != 0 || g->QH != g->Ho || g->QW != g->Wo) return c;
+    if (off || !whole_output(g)) return c;
     if (g->in_step == 1 && g->ntaps == 1 && g->dh[0] == 0 && g->dw[0] == 0 && g->Hi == g->Ho && g->Wi == g->Wo &&
         g->Ho * g->Wo >= 256) {                      // (per image: the choice may not depend on the batch size)
         if (g->Ci <= 16) c = {4, 16};
@@ -1293,26 +1282,13 @@ SxChoice sx_choose(const segnb_conv_geom* g) {
         else c = {7, 128};
         return c;
     }
+    const segnb_tap_win win = segnb_tap_window(g);
+    const int kh = win.kh, kw = win.kw;
     if (g->in_step == 1) {
-        int hmin = g->dh[0], hmax = g->dh[0], wmin = g->dw[0], wmax = g->dw[0];
-        for (int t = 1; t < g->ntaps; ++t) {
-            hmin = g->dh[t] < hmin ? g->dh[t] : hmin;
-            hmax = g->dh[t] > hmax ? g->dh[t] : hmax;
-            wmin = g->dw[t] < wmin ? g->dw[t] : wmin;
-            wmax = g->dw[t] > wmax ? g->dw[t] : wmax;
-        }
-        if (g->ntaps == 4 && hmax - hmin == 1 && wmax - wmin == 1 && g->Ci % 32 == 0 && g->Co <= 32 && g->Wo >= 24) c = {8, 32, 32};
+        if (g->ntaps == 4 && kh == 2 && kw == 2 && g->Ci % 32 == 0 && g->Co <= 32 && g->Wo >= 24) c = {8, 32, 32};
         return c;
     }
     if (g->in_step != 2) return c;
-    int dhmin = g->dh[0], dhmax = g->dh[0], dwmin = g->dw[0], dwmax = g->dw[0];
-    for (int t = 1; t < g->ntaps; ++t) {
-        dhmin = g->dh[t] < dhmin ? g->dh[t] : dhmin;
-        dhmax = g->dh[t] > dhmax ? g->dh[t] : dhmax;
-        dwmin = g->dw[t] < dwmin ? g->dw[t] : dwmin;
-        dwmax = g->dw[t] > dwmax ? g->dw[t] : dwmax;
-    }
-    const int kh = dhmax - dhmin + 1, kw = dwmax - dwmin + 1;
     if (g->ntaps != kh * kw) return c;
     if (kh == 7 && kw == 7 && g->Ci == 8 && g->Wo >= 32) c = {1, 8};
     else if (kh == 3 && kw == 3 && g->Ci % 32 == 0 && g->Wo >= 24) c = {2, 32};
@@ -1327,12 +1303,7 @@ int launch_sx(WgSxArgs& a, int nslab, hipStream_t stream, bool partial) {
     constexpr int XR = (R - 1) * S + KH, XC = (WT - 1) * S + KW;
     constexpr int smem = XR * XC * lds_stride_step(BCI, S) + R * WT * lds_stride(BCO);
     static_assert(smem <= 160 * 1024, "tiles fit the LDS");
-    static int attr_rc = [] {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_sx_kernel<S, BCI, R, WT, KH, KW, BCO>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        if (e != hipSuccess) segnb_set_error("wgrad_sx hipFuncSetAttribute: %s", hipGetErrorString(e));
-        return (int)e;
-    }();
+    static const int attr_rc = segnb_opt_in_lds("wgrad_sx", smem, conv_wgrad_sx_kernel<S, BCI, R, WT, KH, KW, BCO>);
     if (attr_rc) return attr_rc;
     a.HB = (a.H + R - 1) / R;
     a.WB = (a.W + WT - 1) / WT;
@@ -1416,22 +1387,15 @@ int segnb_wgrad_s1_try(segnb_try_outcome* did, const segnb_conv_geom* g, const v
     if (tgt != nullptr) partial = true;           // the slabs are summed by segnb_wgrad_to_param
     if (uc != nullptr && (uc->Cu % 8 != 0 || uc->Cu <= 0 || uc->Cu >= g->Ci || (g->Hi & 1) || (g->Wi & 1))) return 0;
     if (bna != nullptr && c.cfg != 1 && c.cfg != 6) return 0;      // (thin 32 x 32 tiles only)
-    int dhmin = g->dh[0], dwmin = g->dw[0];
-    for (int t = 1; t < 9; ++t) {
-        dhmin = g->dh[t] < dhmin ? g->dh[t] : dhmin;
-        dwmin = g->dw[t] < dwmin ? g->dw[t] : dwmin;
-    }
+    const segnb_tap_win win = segnb_tap_window(g);
     WgS1Args a;
     a.x = (const bf16_t*)in;
     a.dy = (const bf16_t*)dout;
     a.dwp = dwp;
     a.N = g->N; a.H = g->Ho; a.W = g->Wo; a.Hi = g->Hi; a.Wi = g->Wi;
     a.Ci = g->Ci; a.Co = g->Co; a.ld_x = g->ld_in; a.ld_dy = g->ld_out;
-    a.dhmin = dhmin; a.dwmin = dwmin;
-    for (int t = 0; t < 9; ++t) {
-        a.dh[t] = g->dh[t] - dhmin;
-        a.dw[t] = g->dw[t] - dwmin;
-    }
+    a.dhmin = win.dhmin; a.dwmin = win.dwmin;
+    segnb_rel_taps(g, win, a.dh, a.dw);
     a.Ktot = 9 * g->Ci;
     a.u = uc != nullptr ? (const bf16_t*)uc->u : nullptr;
     a.Cu = uc != nullptr ? uc->Cu : 0;
@@ -1469,23 +1433,16 @@ int segnb_wgrad_sx_try(segnb_try_outcome* did, const segnb_conv_geom* g, const v
     *did = SEGNB_TRY_DECLINED;
     const SxChoice c = sx_choose(g);
     if (!c.cfg) return 0;
-    int dhmin = g->dh[0], dwmin = g->dw[0];
-    for (int t = 1; t < g->ntaps; ++t) {
-        dhmin = g->dh[t] < dhmin ? g->dh[t] : dhmin;
-        dwmin = g->dw[t] < dwmin ? g->dw[t] : dwmin;
-    }
+    const segnb_tap_win win = segnb_tap_window(g);
     WgSxArgs a;
     a.x = (const bf16_t*)in;
     a.dy = (const bf16_t*)dout;
     a.dwp = dwp;
     a.N = g->N; a.H = g->Ho; a.W = g->Wo; a.Hi = g->Hi; a.Wi = g->Wi;
     a.Ci = g->Ci; a.Co = g->Co; a.ld_x = g->ld_in; a.ld_dy = g->ld_out;
-    a.dhmin = dhmin; a.dwmin = dwmin;
+    a.dhmin = win.dhmin; a.dwmin = win.dwmin;
     a.ntaps = g->ntaps;
-    for (int t = 0; t < g->ntaps; ++t) {
-        a.dh[t] = (signed char)(g->dh[t] - dhmin);
-        a.dw[t] = (signed char)(g->dw[t] - dwmin);
-    }
+    segnb_rel_taps(g, win, a.dh, a.dw);
     a.Ktot = g->ntaps * g->Ci;
     int rc;
     if (c.cfg >= 4 && c.cfg <= 7) {

@@ -7,6 +7,7 @@ Run as a script on the commit whose behaviour is to be pinned (the PARENT of a c
 
 It runs everything twice and refuses to write a table the library does not repeat itself.  The weight gradient of a row that the
 general kernel serves is left out of the digests (dW: null): that kernel sums with fp32 atomics and is not bit-reproducible.
+A table that exists is widened, not replaced: the script refuses to write unless it reproduces every row the table already holds.
 """
 import hashlib
 import json
@@ -42,10 +43,13 @@ CASES = {
     'general_stride2': ('bf16', 2, 16, 16, 64, 64, 3, 2, True),
     'wsx_1x1': ('bf16', 2, 16, 16, 64, 64, 1, 1, True),
     'general_f32': ('f32', 2, 12, 20, 32, 64, 3, 1, True),
+    # fprop_thin.hip thin_geometry: a data gradient of 16 -> >= 48 channels over N * Ho * Wo >= 4096 pixels, no bias or statistics
+    'thin_48_16': ('bf16', 2, 32, 64, 48, 16, 3, 1, True),
+    # fprop_sx.hip segnb_fprop_sx_try: in_step == 2, 8 input channels, QW >= 24 (an input 48 wide)
+    'sx_8_32_stride2': ('bf16', 1, 8, 48, 8, 32, 3, 2, True),
 }
-# selectors that no geometry of N <= 2, H, W <= 32 reaches, and the gate that keeps them away
-UNREACHED = {'kernel:fprop_thin': 'fprop_thin.hip thin_geometry: N * Ho * Wo >= 4096 pixels (2 x 32 x 32 = 2048)',
-             'kernel:fprop_sx': 'fprop_sx.hip segnb_fprop_sx_try: in_step == 2 and QW >= 24, an input 48 wide'}
+# selectors that no case above reaches, and the gate that keeps them away
+UNREACHED = {}
 FPROP_SELECTORS = ['kernel:fprop_' + s for s in ('c8', 'thin', 'roll', 'rw', 'dma', 'deepk', 's1', 'sx', 'general')]
 WGRAD_SELECTORS = ['kernel:wgrad_' + s for s in ('roll', 'c8roll', 's1', 'sx', 'general')]
 
@@ -130,13 +134,15 @@ CU_QUERIES = ('segnb_conv_upcat_ok', 'segnb_conv_fprop_upsum_ok')               
 UPCONV_QUERIES = ('segnb_upconv_fprop_ok', 'segnb_upconv_fprop_acc_ok')           # (N, H, W, Ci, Co, ld_out, dtype)
 TF_QUERY = 'segnb_conv_fprop_tf_ok'                                               # (g, dtype, kind)
 GRID_C_IN, GRID_C_OUT, GRID_W = (8, 16, 32, 64, 96, 128, 512), (8, 32, 64, 96, 256), (8, 12, 16, 32)
-GRID_TAPS = ((3, 1, 1), (3, 2, 1), (1, 1, 1), (3, 1, 2), (4, 2, 1))               # (kernel, stride, dilation); pad = dilation * ((kernel - 1) // 2)
+# (kernel, stride, dilation[, pad]); pad = dilation * ((kernel - 1) // 2) unless given.  The last row is a window without padding
+# (linknet.py:60): its forward origin is 0 and its data-gradient origin -2, beside the -1 of the padded rows
+GRID_TAPS = ((3, 1, 1), (3, 2, 1), (1, 1, 1), (3, 1, 2), (4, 2, 1), (3, 1, 1, 0))
 GRID_CU = (8, 32, 64)
 
 
-def _geom(N, H, W, Ci, Co, k, stride, dil, side='f'):
+def _geom(N, H, W, Ci, Co, k, stride, dil, side='f', pad=None):
     from segnb.engine import ConvOp
-    pad = dil * ((k - 1) // 2)
+    pad = dil * ((k - 1) // 2) if pad is None else pad
     (Ho, Wo), fwd = cp.conv_fwd(H, W, k, k, stride, pad, dil)
     if side == 'f':
         return ConvOp._make_geom(fwd[0], N, H, W, Ci, Ci, Ho, Wo, Co, Co)
@@ -147,12 +153,12 @@ def predicate_table():
     """{query: its answers over the grid in grid order, comma-separated}; nothing is launched"""
     lib = nv.load()
     out = {q: [] for q in GEOM_QUERIES + CU_QUERIES + UPCONV_QUERIES + (TF_QUERY,)}
-    for k, stride, dil in GRID_TAPS:
+    for k, stride, dil, *pad in GRID_TAPS:
         for W in GRID_W:
             for Ci in GRID_C_IN:
                 for Co in GRID_C_OUT:
                     for side in 'fd':
-                        g = _geom(2, 8 if W < 16 else W, W, Ci, Co, k, stride, dil, side)
+                        g = _geom(2, 8 if W < 16 else W, W, Ci, Co, k, stride, dil, side, *pad)
                         for dt in (nv.BF16, nv.F32):
                             for q in GEOM_QUERIES:
                                 out[q].append(getattr(lib, q)(g, dt))
@@ -212,8 +218,109 @@ def error_paths():
     return out
 
 
+# ------------------------------------------------------------------------------------------------ 5. the fused entry points
+# Tensors of a row that are sum tables written with fp64 atomics, by the name the driver gives them.  One that the parent does not
+# repeat is left out of the digests (null, and named in the row's 'excluded'); any other tensor has to repeat.
+FUSED_SUM_TABLES = ('stats', 'sums', 'stats virtual', 'stats segment')
+FUSED_EXCLUDED = 'a sum table written with fp64 atomics: the parent does not repeat its own bits'
+FUSED_ACT_CASES = ('rw 32->64 relu', 'upconv T4x4 s2 relu')       # test_hip_ops.ACT_EP_CASES: a plain and a ConvTranspose2d(4, 2, 1) case
+
+
+def _digests(d):
+    return {k: _sha(v) for k, v in sorted(d.items()) if torch.is_tensor(v)}
+
+
+def _conv_op_launches():
+    """one segnb_conv_fprop_drop, one segnb_conv_fprop_u8 (with the packed pixels) and one segnb_conv_fprop_bnreduce launch through
+    ConvOp, each at a small shape its *_ok accepts -> {row: {tensor: torch tensor}}"""
+    from segnb.engine import ConvOp, InputNorm, Runtime, View
+    rt = Runtime(torch.device('cuda:0'), 'bf16')
+    dev, out = rt.device, {}
+
+    def conv(Co, Ci, segs, bias, seed, dgrad):
+        w = _randn((Co, Ci, 3, 3), seed, (2.0 / (Ci * 9)) ** 0.5).to(dev)
+        return ConvOp(rt, w, _randn((Co,), seed + 1).to(dev) if bias else None, segs, 1, 1, False, need_dgrad=dgrad)
+
+    def filled(N, H, W, C, seed):
+        v = View.alloc(rt, N, H, W, C)
+        v.dense().copy_(_randn((N, H, W, C), seed).to(dev, rt.tdtype))
+        return v
+
+    # conv -> Dropout2d -> slice statistics: <= 32 output channels behind more than 96 input channels (segnb_conv_fprop_drop_ok)
+    N, H, W, C1, C2 = 2, 16, 16, 128, 16
+    op = conv(C2, C1, [(C1, C1)], True, 81, False)
+    op.pack(H, W)
+    LD, OFF = C1 + C2 + 24, C1
+    cat, table = View.alloc(rt, N, H, W, LD), rt.zeros((16, 2, LD), torch.float64)
+    drop = (_randn((N, C2), 83) > -0.8).float().mul(1.25).to(dev)
+    assert op.drop_epilogue_ok(N, H, W, LD)
+    op.fprop_drop(filled(N, H, W, C1, 84), cat.slice(OFF, C2), drop, (table, OFF, LD))
+    out['fprop_drop 2x16x16 128->16'] = {'y': cat.t, 'stats': table.sum(0)}
+    # the first layer from the uint8 batch (segnb_conv_fprop_u8_ok: 8 padded channels -> <= 32, at least 12 wide)
+    N, H, W = 2, 16, 16
+    img = torch.randint(0, 256, (N, H, W, 3), generator=torch.Generator().manual_seed(85), dtype=torch.uint8).to(dev)
+    op = conv(32, 3, [(3, 8)], True, 86, False)
+    op.pack(H, W)
+    assert op.u8_direct_ok(N, H, W, 32)
+    xp, yv, st = View.alloc(rt, N, H, W, 8), View.alloc(rt, N, H, W, 32), rt.zeros((16, 2, 32), torch.float64)
+    op.fprop_u8(img, InputNorm(), yv, st, xp)
+    out['fprop_u8 2x16x16 3->32'] = {'y': yv.t, 'packed': xp.t, 'stats': st.sum(0)}
+    # a data gradient with the BatchNorm-backward reduction of the producing layer in its store pass (segnb_conv_fprop_bnreduce_ok)
+    N, H, W, C = 2, 16, 32, 32
+    op = conv(C, C, [(C, C)], False, 88, True)
+    op.pack(H, W)
+    dyv, dxv, y1 = filled(N, H, W, C, 90), View.alloc(rt, N, H, W, C), filled(N, H, W, C, 91)
+    coef = torch.stack([0.5 + _randn((C,), 92).abs(), _randn((C,), 93, 0.3), _randn((C,), 94, 0.2), 0.5 + _randn((C,), 95).abs()])
+    coef, sums = coef.contiguous().to(dev), rt.zeros((16, 2, C), torch.float64)
+    assert op.dgrad_bnreduce_ok(dyv, dxv)
+    op.dgrad(dyv, dxv, bn_reduce=(y1, coef, sums, nv.ACT_LEAKY, 0.01))
+    out['dgrad bn_reduce 2x16x32 32->32'] = {'dx': dxv.t, 'sums': sums.sum(0)}
+    torch.cuda.synchronize()
+    return out
+
+
+def fused_table():
+    """{row: {tensor: SHA-256 of its bytes}}: every stored tensor the drivers of tests/fused_errbound.py produce at their smallest
+    served shapes, and the three launches of _conv_op_launches"""
+    import fused_errbound as fe
+    from test_hip_ops import ACT_EP_CASES
+    out = {}
+    s = fe.THIN_SERVED[0]
+    dx, dx_f, sums = fe.run_thin('cuda', s, fe.thin_data(s))
+    out['thin ' + fe.sid(s)] = _digests({'dx': dx, 'dx fused': dx_f, 'sums': sums})
+    s = fe.TF_SHAPES[1]
+    for use_drop in (False, True):
+        out['tf %s%s' % (fe.sid(s), ' drop' if use_drop else '')] = _digests(fe.run_tf('cuda', s, fe.tf_data(s, use_drop)))
+    for s in (fe.UPCAT_SHAPES[0], fe.UPCAT_SHAPES[2]):
+        out['upcat ' + fe.sid(s)] = _digests(fe.run_upcat('cuda', s, fe.upcat_data(s)))
+    acts = {c[0]: c for c in ACT_EP_CASES}
+    for name in FUSED_ACT_CASES:
+        for with_bn in (False, True):
+            y, buf, coef = fe.run_act('cuda', acts[name], 'bf16', with_bn, fe.act_data(acts[name], 'bf16'))
+            # (the one-launch transposed convolution takes no folded BatchNorm: run_act asserts that its gate says so)
+            out['act %s%s' % (name, ' evalbn' if with_bn else '')] = {'served': False} if y is None else _digests({'y': y, 'buffer': buf})
+    for row, tensors in _conv_op_launches().items():
+        out[row] = _digests(tensors)
+    return out
+
+
+def fused_without_unrepeated_sums(*runs):
+    """the first of several fused_table() results with the sum tables that differ between them left out; anything else that
+    differs is an error"""
+    out = {}
+    for row, first in runs[0].items():
+        out[row] = dict(first)
+        for k in first:
+            if any(r[row][k] != first[k] for r in runs[1:]):
+                assert k in FUSED_SUM_TABLES, ('not reproducible', row, k)
+                out[row][k] = None
+                out[row]['excluded'] = FUSED_EXCLUDED
+    return out
+
+
 def record():
-    return {'cases': {k: run_case(v) for k, v in sorted(CASES.items())}, 'predicates': predicate_table(), 'errors': error_paths()}
+    return {'cases': {k: run_case(v) for k, v in sorted(CASES.items())}, 'predicates': predicate_table(), 'errors': error_paths(),
+            'fused': fused_table()}
 
 
 if __name__ == '__main__':
@@ -224,8 +331,22 @@ if __name__ == '__main__':
     assert a['predicates'] == b['predicates'] and a['errors'] == b['errors']
     for k, v in sorted(a['errors'].items()):
         print(k, v)
+    a['fused'] = fused_without_unrepeated_sums(a['fused'], b['fused'], fused_table())
+    for k, v in sorted(a['fused'].items()):
+        print(k, sorted(t for t in v if v[t] is None), len(v))
     seen = {n for c in a['cases'].values() for side in c['names'] for n in side}
+    print('selectors not reached:', sorted(set(FPROP_SELECTORS + WGRAD_SELECTORS) - seen))
     assert seen | set(UNREACHED) == set(FPROP_SELECTORS + WGRAD_SELECTORS), sorted(set(FPROP_SELECTORS + WGRAD_SELECTORS) - seen)
+    if os.path.exists(JSON_PATH):
+        # a table that is being widened: what it already holds is reproduced as it stands (a predicate's answers over a longer
+        # grid begin with the answers it had)
+        with open(JSON_PATH) as f:
+            old = json.load(f)
+        for k, v in old['cases'].items():
+            assert a['cases'][k] == v, ('the table\'s row is not reproduced', k, a['cases'][k], v)
+        assert all(a['errors'][k] == v for k, v in old['errors'].items())
+        assert all((a['predicates'][q] + ',').startswith(v + ',') for q, v in old['predicates'].items())
+        assert all(a['fused'][k] == v for k, v in old.get('fused', {}).items())
     with open(sys.argv[1] if len(sys.argv) > 1 else JSON_PATH, 'w') as f:
         json.dump(a, f, indent=0, sort_keys=True, separators=(',', ':'))
         f.write('\n')

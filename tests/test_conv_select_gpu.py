@@ -6,7 +6,9 @@ were factored out (tests/conv_select_parent.json, written by tests/conv_select.p
   2. the answer of every fast-path query over a grid of geometries -- host functions, so this one runs without a GPU too;
   3. SHA-256 of the output bytes of every launch of 1: the kernels and their arguments did not change, so neither do the bits
      (left out: weight gradients of the general kernel, which sums with fp32 atomics -- named in the table);
-  4. status and message of the refusals that moved into helpers, and which call consumes an armed segnb_wgrad_target.
+  4. status and message of the refusals that moved into helpers, and which call consumes an armed segnb_wgrad_target;
+  5. SHA-256 of every stored tensor of the fused entry points at their smallest served shapes (conv_select.fused_table: the drivers
+     of tests/fused_errbound.py and three ConvOp launches); a sum table the parent does not repeat is named in its row.
 """
 import json
 import os
@@ -30,6 +32,27 @@ def test_table_covers_every_selector():
     for k, c in PARENT['cases'].items():
         assert c['y'] and c['dx'], k                                   # no forward or data-gradient row is left out
         assert c['dW'] or ('kernel:wgrad_general' in c['names'][2] and c['dW_excluded'] == cs.DW_EXCLUDED), k
+
+
+def test_fused_section_leaves_no_stored_tensor_out():
+    rows = PARENT['fused']
+    assert len(rows) == 12 and sum(not r.get('served', True) for r in rows.values()) == 1      # (the transposed case with BatchNorm)
+    for k, row in rows.items():
+        left_out = [t for t, v in row.items() if v is None]
+        assert set(left_out) <= set(cs.FUSED_SUM_TABLES), (k, left_out)          # no forward or data-gradient tensor is left out
+        assert not left_out or row['excluded'] == cs.FUSED_EXCLUDED, k
+        assert row.get('served', True) is False or any(t in row for t in ('y', 'dx', 'y plain')), k
+
+
+@gpu
+def test_fused_outputs_are_bit_identical_to_the_parents():
+    got = cs.fused_table()
+    assert sorted(got) == sorted(PARENT['fused'])
+    for k, want in sorted(PARENT['fused'].items()):
+        assert sorted(got[k]) == sorted(t for t in want if t != 'excluded'), k
+        for t, v in want.items():
+            if v is not None and t != 'excluded':
+                assert got[k][t] == v, (k, t)
 
 
 @pytest.fixture(scope='module')

@@ -6,6 +6,9 @@ them is the start of two kernels that disagree.
 
 A site that has to stay spelled out -- routed through the helper the kernel's device code differs from the parent build's
 (tools/devcode_ab.py) -- is an entry of SPELLED_OUT with its reason, and carries a comment in the source.
+
+The same for the host side of the kernel tries: the window origin, the tap tables relative to it, the extent of a
+buffer descriptor, the dynamic-LDS opt-in, the whole-output gate and the declined status are in common.h only (LAUNCH_SPELLED_OUT).
 """
 import glob
 import os
@@ -104,3 +107,69 @@ def test_spelled_out_sites_are_the_listed_ones():
     loads = files_with(r'\[e\]\s*=\s*[\w.\->]*bcoef\[2\s*\*', src)
     assert loads == {'wgrad_s1.hip': 1, 'wgrad_roll.hip': 1}, loads
     assert files_with(r'pack2bf\(\w+,\s*0\.f\)\s*<<\s*16', src) == {'wgrad_roll.hip': 1}
+
+
+# ---- the host side of the kernel tries: window origin, descriptor extents, LDS opt-in, declined status --------
+# (file, text of the site) -> why the site is not routed through the helper of common.h; none so far
+LAUNCH_SPELLED_OUT = {}
+
+
+def _elsewhere(pattern, src=None):
+    """files other than common.h in which the pattern occurs, without the listed exceptions"""
+    hits = files_with(pattern, src)
+    hits.pop('common.h', None)
+    for (name, text), reason in LAUNCH_SPELLED_OUT.items():
+        assert reason
+        if name in hits and re.search(pattern, text):
+            hits[name] -= 1
+    return {n: c for n, c in hits.items() if c}
+
+
+def test_tap_window_is_computed_in_one_place():
+    src = sources()
+    # the window origin loop, under any names of the two minima, and the "each of the nine positions once" table
+    assert files_with(r'\w*min\s*=\s*g->dh\[0\]', src).get('common.h') == 1
+    assert _elsewhere(r'\w*min\s*=\s*g->dh\[0\]', src) == {}
+    assert files_with(r'bool\s+seen\[9\]', src).get('common.h') == 1
+    assert _elsewhere(r'\bseen\[', src) == {}
+    # the tap table relative to the origin: filled by segnb_rel_taps
+    assert _elsewhere(r'\.d[hw]\[t\]\s*=\s*(\(signed char\))?\(?g->d[hw]\[t\]\s*-', src) == {}
+    for name in ('segnb_tap_window', 'segnb_rel_taps', 'segnb_window_once_3x3', 'segnb_nhwc_bytes', 'segnb_fits_desc',
+                 'segnb_opt_in_lds', 'whole_output', 'whole_output_3x3_s1', 'segnb_try_launched'):
+        assert files_with(r'(?m)^(SEGNB_HOST_INLINE|inline|int)\s[\w ]*\b%s\([^;{]*\)\s*\{' % name, src) == {'common.h': 1}, name
+    assert src['common.h'].count('spans are 2') == 1 and _elsewhere(r'spans are 2', src) == {}
+
+
+def test_lds_opt_in_is_written_once():
+    assert files_with(r'hipFuncSetAttribute') == {'common.h': 2}      # (the call and its message)
+    assert files_with(r'\bset_smem\b') == {}
+
+
+def test_one_declined_status():
+    src = sources()
+    assert files_with(r'-\s*12345\b', src) == {} and files_with(r'NOT_HANDLED', src) == {}
+    assert files_with(r'constexpr\s+int\s+SEGNB_LAUNCH_DECLINED\s*=', src) == {'common.h': 1}
+    # its only reader is segnb_try_launched: everywhere else the constant is returned, never compared
+    assert files_with(r'[!=]=\s*SEGNB_LAUNCH_DECLINED|SEGNB_LAUNCH_DECLINED\s*[!=]=', src) == {'common.h': 1}
+    for name, text in src.items():
+        if name != 'common.h':
+            assert len(re.findall(r'SEGNB_LAUNCH_DECLINED', text)) == len(re.findall(r'return SEGNB_LAUNCH_DECLINED;', text)), name
+
+
+def test_descriptor_extent_is_written_once():
+    src = sources()
+    # ((pixels - 1) * ld + C) * element size, under any operand names; and its comparison with 2 GiB
+    assert _elsewhere(r'-\s*1\)\s*\*\s*[\w.\->]+\s*\+\s*[\w.\->]+\)\s*\*\s*(2|4|esz)\b', src) == {}
+    assert len(re.findall(r'-\s*1\)\s*\*\s*ld\s*\+\s*C\)\s*\*\s*esz', src['common.h'])) == 1
+    # what is still compared with 1ll << 31 elsewhere is a pixel count, a weight matrix or a workspace -- other statements
+    for name, text in src.items():
+        for line in text.split('\n'):
+            if '1ll << 31' in line and name != 'common.h':
+                assert re.search(r'N \* (g->)?H|\bw\b|\bwb\b|tiles \* ks|N \* g->Hi', line), (name, line)
+
+
+def test_whole_output_gate_is_written_once():
+    src = sources()
+    assert _elsewhere(r'out_step\s*[!=]=\s*1', src) == {}
+    assert _elsewhere(r'QH\s*[!=]=\s*g->Ho', src) == {}
+    assert len(re.findall(r'QH\s*==\s*g->Ho', src['common.h'])) == 1
