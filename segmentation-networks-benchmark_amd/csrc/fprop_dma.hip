@@ -137,6 +137,18 @@ struct WsCfg {
     static_assert(TM + TN <= 6, "fragment wait statement");
 };
 
+// EPI: the instantiation that carries the previous tile's store rows INSIDE the MFMA stream of a tap (conv_fprop_ws_kernel, matrix
+// stream).  A wrapper type, not a ninth parameter: the instantiations of the plain order keep their symbols, so two builds can be
+// compared kernel by kernel (tools/devcode_ab.py), and one library holds both orders behind segnb_tune("fprop_dma_epi").
+template <class C_>
+struct WsEpi : C_ {
+    static constexpr bool EPI = true;
+};
+template <class C, class = void>
+struct ws_epi_of : std::false_type {};
+template <class C>
+struct ws_epi_of<C, std::enable_if_t<C::EPI>> : std::true_type {};
+
 // EP: the affine + activation epilogue (segnb_conv_fprop_act) is a SEPARATE instantiation: as run-time checks in the staging
 // code of the training kernels it cost 0.22 ms per step (5.62 vs 5.40 ms, same box)
 // STATS: BatchNorm statistics in the store rows (forward launches) -- data gradients take none and run the instantiation
@@ -164,6 +176,8 @@ __global__ __launch_bounds__(512) void conv_fprop_ws_kernel(const FdArgs a) {
     constexpr int OUT_ROW = C::OUT_ROW, NF = TM + TN;
     constexpr int NTAP = C::NTAP, KW = C::KW;
     constexpr int SM = NTAP & 3;                         // weight-ring stage of step (chunk cg, tap t) = (cg * SM + t) & 3
+    constexpr bool EPI = ws_epi_of<C>::value;            // store rows in the MFMA gaps (WsEpi)
+    static_assert(!EPI || (C::MF16 && !SPLITK && !EP && C::UP == 0 && C::NTAP == 9), "store rows in the MFMA gaps: 16x16x32 form, 3 x 3 window, whole-K tiles");
 
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
     int* sPix = reinterpret_cast<int*>(smem + C::OFF_PIX);
@@ -581,8 +595,11 @@ __global__ __launch_bounds__(512) void conv_fprop_ws_kernel(const FdArgs a) {
         // EPILOGUE IN THE MFMA SHADOW.  At the end of a tile the accumulators are staged (bias, bf16) into a buffer of
         // their own -- no barrier: the first tap barrier of the next tile publishes it -- and the tile's coalesced
         // stores + BatchNorm statistics are issued one staged row per thread and tap during taps 1..RPT of the NEXT
-        // tile, between its MFMAs (a matrix wave needs 8 of every 32 issue cycles).  Serialised, the epilogue was
-        // 2-2.5 k cycles per tile: 30 % of a 64 -> 64 tile, 7 % of a 256 -> 256 one.
+        // tile.  Serialised, the epilogue was 2-2.5 k cycles per tile: 30 % of a 64 -> 64 tile, 7 % of a 256 -> 256 one.
+        // In the plain order a tap's row runs BEHIND the tap's last MFMA, in front of the barrier (in-kernel stamps,
+        // tools/wsepi_stamps.py: ~190 cycles per row tap in which the matrix pipe drains, 8 times per tile); the WsEpi
+        // instantiations (epi_tap below) place it BETWEEN the MFMAs, one step per gap.  The staging and the halo waves' switch
+        // to the next tile (set_fetch_tile, tap NTAP - 2) are the rest of what a tile costs beyond its taps: DESIGN.md 13.28.
         // ---- compute-side per-lane constants: fragment offsets (see the uniform kernel for the swizzle) -----------
         constexpr bool MF16 = C::MF16;
         int tile_no_out = 0;
@@ -797,8 +814,166 @@ __global__ __launch_bounds__(512) void conv_fprop_ws_kernel(const FdArgs a) {
 #pragma unroll
                 for (int q = 0; q < NRD; ++q) issue(q, 0, 0, arow[0], 0, 0);
             }
+            // ---- EPI: one tap, with or without a store row of the previous tile INSIDE its MFMA stream.  The row's two LDS reads go
+            // out at the tap's start, as in the plain order; they are older than every fragment read the tap issues, so the wait in
+            // front of the last pixel row of the tap's first K slice (at most the rd_before look-ahead reads outstanding) covers
+            // them, and from that gap on the row is worked off one step per MFMA gap: the store offset, the buffer_store_b128, then
+            // one statistics element per gap -- same thread, same row, same additions to s1[] / s2[] in the same order.  Every step
+            // is fenced by empty volatile statements naming its registers, which the compiler keeps in order with the MFMAs and the
+            // fragment reads.  Nothing but the barrier follows the last MFMA.
+            // Whether a tap carries a row is a COMPILE-TIME fact here (ROWS): the block's first tile is peeled off the tile loop and
+            // the first chunk off the chunk loop, so the taps are straight-line code.  (Chosen per tap at run time, the two bodies
+            // met in 8 diamonds per chunk and the fragment / accumulator registers no longer fitted: 256 VGPRs + 200-800 bytes of
+            // scratch.)
+            constexpr int RSTEPS = STATS ? 10 : 2;                  // gap steps of a store row
+            constexpr int SLOT0 = (TM16 - 1) * TN16;                // first gap behind the wait that covers the row reads
+            static_assert(!EPI || (NTAP == 9 && RSTEPS <= 2 * C::NMF - SLOT0), "a store row fits the gaps of a 3 x 3 window's tap");
+            auto epi_tap = [&](auto t_c, auto rows_c, f32x4_t (&accr)[TM16][TN16], bool first_chunk, int tile_no)
+                               __attribute__((always_inline)) {
+                constexpr int t = decltype(t_c)::value, ROWS = decltype(rows_c)::value;
+                constexpr int tn = t == NTAP - 1 ? 0 : t + 1;
+                const int a_base = (cg & 1) * C::A_BYTES;
+                const int bstage = ((cg * SM + t) & (NB - 1)) * C::B_STAGE;
+                const int bnext = ((cg * SM + t + 1) & (NB - 1)) * C::B_STAGE;
+                const int anext = t == NTAP - 1 ? ((cg + 1) & 1) * C::A_BYTES : a_base;
+                if (wave == 0) FD_STAMP(0, cg * 9 + t, 0);
+                if constexpr (ROWS == 1) row_load(t - 1, sPix + ((tile_no + 3) & 3) * BM);
+                unsigned voff = OOB;
+                float rm = 0.f;
+                auto row_step = [&](int k) __attribute__((always_inline)) {      // (k: constant once the MFMA loops are unrolled)
+                    int& pix = row_pix;
+                    u32x4_t& v = row_v;
+                    if (k == 0) {
+                        if (DBG && (a.dbg & (4 | 16))) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // (timing builds: no fragment waits)
+                        asm volatile("" : "+v"(pix), "+v"(v));      // landed: older than the fragment reads just waited for
+                        const bool ok = cok && pix >= 0;
+                        voff = ok ? (unsigned)pix * (unsigned)a.ld_out * 2u + (unsigned)(n_base + cc * 8) * 2u : OOB;
+                        rm = ok ? 1.f : 0.f;
+                        asm volatile("" : "+v"(voff), "+v"(rm));
+                    } else if (k == 1) {
+                        asm volatile("" : "+v"(voff), "+v"(v) : : "memory");
+                        if (!(DBG && (a.dbg & 8))) __builtin_amdgcn_raw_buffer_store_b128(v, rs_out, (int)voff, 0, 0);
+                        asm volatile("" ::: "memory");
+                    } else if constexpr (STATS) {
+                        const int e = k - 2;
+                        if constexpr (MASK) asm volatile("" : "+v"(v), "+v"(s1[e]));
+                        else asm volatile("" : "+v"(v), "+v"(s1[e]), "+v"(s2[e]));
+                        const unsigned w = e < 2 ? v.x : e < 4 ? v.y : e < 6 ? v.z : v.w;
+                        const float f = __uint_as_float((e & 1) ? (w & 0xffff0000u) : (w << 16));      // (unpack8, element e)
+                        const float fm = f * rm;
+                        s1[e] += fm;
+                        if constexpr (!MASK) s2[e] += fm * fm;
+                        if constexpr (MASK) asm volatile("" : "+v"(s1[e]));
+                        else asm volatile("" : "+v"(s1[e]), "+v"(s2[e]));
+                    }
+                };
+                if (!(DBG && (a.dbg & 4))) {
+                    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+                    for (int kk = 0; kk < 2; ++kk) {
+                        const int cur = kk, nxt = kk ^ 1;
+                        const int wbase = kk == 0 ? bstage : bnext;
+                        const int xbase = kk == 0 ? a_base + arow[t / KW] : anext + arow[tn / KW];
+                        ws_wait_xw<TM16 - 1>(fx[cur][0], fw[cur]);
+#pragma unroll
+                        for (int i = 0; i < TM16; ++i) {
+                            static_for<TM16 - 1>([&](auto k_c) {
+                                constexpr int k = decltype(k_c)::value + 1;
+                                if (i == k) ws_wait1<TM16 - 1 - k + C::rd_before(k * TN16)>(fx[cur][k]);
+                            });
+#pragma unroll
+                            for (int j = 0; j < TN16; ++j) {
+                                const int q = i * TN16 + j;
+                                if (C::rd_before(q + 1) > C::rd_before(q) && !(DBG && (a.dbg & 16))) {
+                                    if (kk == 0) issue(C::rd_before(q), nxt, wbase, xbase, t, 1);
+                                    else issue(C::rd_before(q), nxt, wbase, xbase, tn, 0);
+                                }
+                                const int s = kk * C::NMF + q - SLOT0;
+                                if (!(SEGNB_EXP & 256) && s >= 0 && s < ROWS * RSTEPS) row_step(s);
+                                if (t == 0 && kk == 0 && first_chunk)
+                                    FD_MFMA16_0(accr[i][j], fw[cur][j], fx[cur][i]);
+                                else
+                                    FD_MFMA16(accr[i][j], fw[cur][j], fx[cur][i]);
+                            }
+                        }
+                    }
+                    __builtin_amdgcn_s_setprio(0);
+                    if (SEGNB_EXP & 256) {      // (experiment 256: the peeled taps with the row BEHIND the MFMAs -- what the gaps are worth)
+#pragma unroll
+                        for (int s = 0; s < ROWS * RSTEPS; ++s) row_step(s);
+                    }
+                } else {
+#pragma unroll
+                    for (int s = 0; s < ROWS * RSTEPS; ++s) row_step(s);
+                }
+                if (wave == 0) FD_STAMP(0, cg * 9 + t, 1);
+                if (wave == 0) FD_STAMP(0, cg * 9 + t, 2);
+                raw_barrier();
+                if (wave == 0) FD_STAMP(0, cg * 9 + t, 3);
+            };
             int tile_no = 0;
             bool pending = false;
+            if constexpr (EPI) {
+                // one tile: its chunks, then the staging.  PEND: 0 = the block's first tile, nothing to store yet; 1 = every later one
+                auto tile_body = [&](auto pend_c) __attribute__((always_inline)) {
+                    constexpr int PEND = decltype(pend_c)::value;
+                    f32x4_t acc[TM16][TN16];
+                    // the first chunk, peeled: from the block's second tile on its taps 1..RPT carry the previous tile's store rows
+                    static_for<NTAP>([&](auto t_c) {
+                        constexpr int t = decltype(t_c)::value;
+                        epi_tap(t_c, std::integral_constant<int, (PEND == 1 && t >= 1 && t <= C::RPT) ? 1 : 0>{}, acc, true, tile_no);
+                    });
+                    ++cg;
+                    for (int c = 1; c < a.NCH; ++c, ++cg)
+                        static_for<NTAP>([&](auto t_c) { epi_tap(t_c, std::integral_constant<int, 0>{}, acc, false, tile_no); });
+                    // (as below: the look-ahead reads have landed, the last MFMA results too, before compiler-scheduled code runs)
+                    ws_wait_xw<0>(fx[0][0], fw[0]);
+#pragma unroll
+                    for (int i = 1; i < TM16; ++i) ws_wait1<0>(fx[0][i]);
+                    asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::);
+                    // the staging of the plain order (below), without its split-K, affine and phase-forward forms
+                    const int r16 = lane & 15, g4 = lane >> 4;
+                    float4 bv[TN16];
+                    uint2 mrow[MASK ? TM16 : 1];
+                    if constexpr (MASK) {
+#pragma unroll
+                        for (int i = 0; i < TM16; ++i)
+                            mrow[i] = *reinterpret_cast<const uint2*>(smem + C::SMEM + (wm * C::WM + 16 * i + r16) * 8);
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < TN16; ++j) bv[j] = *reinterpret_cast<const float4*>(sBias + wn * C::WN + 16 * j + 4 * g4);
+                    }
+#pragma unroll
+                    for (int i = 0; i < TM16; ++i) {
+                        const int row = wm * C::WM + 16 * i + r16;
+#pragma unroll
+                        for (int j = 0; j < TN16; ++j) {
+                            const int col = wn * C::WN + 16 * j + 4 * g4;
+                            uint2 pk;
+                            if constexpr (MASK) {
+                                const unsigned mb = (j < 2 ? mrow[i].x : mrow[i].y) >> (8 * ((2 * j + (g4 >> 1)) & 3) + 4 * (g4 & 1));
+                                const unsigned g01 = pack2bf(acc[i][j][0], acc[i][j][1]);
+                                const unsigned g23 = pack2bf(acc[i][j][2], acc[i][j][3]);
+                                const float g0 = __uint_as_float(g01 << 16), g1 = __uint_as_float(g01 & 0xffff0000u);
+                                const float g2 = __uint_as_float(g23 << 16), g3 = __uint_as_float(g23 & 0xffff0000u);
+                                pk.x = pack2bf((mb & 1u) ? g0 : g0 * mask_neg, (mb & 2u) ? g1 : g1 * mask_neg);
+                                pk.y = pack2bf((mb & 4u) ? g2 : g2 * mask_neg, (mb & 8u) ? g3 : g3 * mask_neg);
+                            } else {
+                                pk.x = pack2bf(acc[i][j][0] + bv[j].x, acc[i][j][1] + bv[j].y);
+                                pk.y = pack2bf(acc[i][j][2] + bv[j].z, acc[i][j][3] + bv[j].w);
+                            }
+                            *reinterpret_cast<uint2*>(sOut + row * OUT_ROW + col * 2) = pk;
+                        }
+                    }
+                    pending = true;
+                };
+                if (it < a.IT) {
+                    tile_body(std::integral_constant<int, 0>{});
+                    it += a.GM;
+                    ++tile_no;
+                }
+                for (; it < a.IT; it += a.GM, ++tile_no) tile_body(std::integral_constant<int, 1>{});
+            } else {
             for (; it < a.IT; it += a.GM, ++tile_no) {
                 f32x4_t acc[TM16][TN16];
                 // UPF: what the skip segment's launch left at this tile's output pixels (4 bf16 per accumulator quad),
@@ -966,6 +1141,7 @@ __global__ __launch_bounds__(512) void conv_fprop_ws_kernel(const FdArgs a) {
                 }
                 }
                 pending = !SPLITK || ks_last;
+            }
             }
             tile_no_out = tile_no;
             pending_out = pending;
@@ -1210,6 +1386,23 @@ int ksplit_factor(const FdArgs& a, int it_total, int ntl, int nch) {
     return ks;
 }
 
+// Which order of the store rows serves a launch (segnb_tune "fprop_dma_epi"): the WsEpi instantiations exist for the 16x16x32
+// configurations of the 3 x 3 window the ZF_UNET step launches without split K -- 14 x 14 and 16 x 16 tiles (statistics, none,
+// activation mask, timing build); everything else (8 x 32 tiles, the 2 x 2-window forms, the tall 7 x 7 form and its split K, the
+// affine epilogue, the 32x32x16 stream) keeps the plain order whatever the knob says.
+// by_default: what the configuration takes at knob -1 (tools/wsepi_bench.py, profiles/wsepi_ab.txt).
+template <class C>
+constexpr bool ws_has_epi() {
+    return C::MF16 && !C::TALL && C::BN == 64 && C::NTAP == 9 && ((C::R == 14 && C::WT == 14) || (C::R == 16 && C::WT == 16));
+}
+bool ws_epi_selected(bool by_default) {
+    const int k = segnb_knob_fprop_dma_epi();
+    const bool on = k < 0 ? by_default : k != 0;
+    if (on && g_segnb_census_on) segnb_census("epi:1");
+    return on;
+}
+constexpr bool WS_EPI_DEFAULT = true;
+
 template <class C>
 int launch_ws(FdArgs& a, hipStream_t stream) {
     if (a.bn_y != nullptr && !C::MASK_OK) return SEGNB_LAUNCH_DECLINED;      // (activation mask: 16 x 16 tiles, 16x16x32 form)
@@ -1223,6 +1416,15 @@ int launch_ws(FdArgs& a, hipStream_t stream) {
             if (rc == 0)
                 rc = segnb_opt_in_lds("fprop_ws", C::SMEM, conv_fprop_ws_kernel<C, false, false, true, true>,
                                       conv_fprop_ws_kernel<C, false, false, false, true>);
+        }
+        if constexpr (ws_has_epi<C>()) {
+            using CE = WsEpi<C>;
+            if (rc == 0)
+                rc = segnb_opt_in_lds("fprop_ws", C::SMEM, conv_fprop_ws_kernel<CE, false>, conv_fprop_ws_kernel<CE, true>,
+                                      conv_fprop_ws_kernel<CE, false, false, false>);
+            if constexpr (C::MASK_OK) {
+                if (rc == 0) rc = segnb_opt_in_lds("fprop_ws", C::SMEM + 2048, conv_fprop_ws_kernel<CE, false, false, true, false, true>);
+            }
         }
         return rc;
     }();
@@ -1258,6 +1460,25 @@ int launch_ws(FdArgs& a, hipStream_t stream) {
     if (gm < 1) gm = 1;
     if (gm > a.IT) gm = a.IT;
     a.GM = gm;
+    if constexpr (ws_has_epi<C>()) {
+        // the store rows inside the MFMA stream (WsEpi): every form of this configuration but the affine epilogue's
+        if (a.ep_act < 0 && ws_epi_selected(WS_EPI_DEFAULT)) {
+            using CE = WsEpi<C>;
+            const dim3 grid(a.GM * a.NTL), block(C::NT);
+            if (a.bn_y != nullptr) {
+                if constexpr (C::MASK_OK)
+                    hipLaunchKernelGGL((conv_fprop_ws_kernel<CE, false, false, true, false, true>), grid, block, C::SMEM + 2048, stream, a);
+                else
+                    return SEGNB_LAUNCH_DECLINED;
+            } else if (a.stats == nullptr && !a.dbg && segnb_knob_fprop_nostats())
+                hipLaunchKernelGGL((conv_fprop_ws_kernel<CE, false, false, false>), grid, block, C::SMEM, stream, a);
+            else if (a.dbg)
+                hipLaunchKernelGGL((conv_fprop_ws_kernel<CE, true>), grid, block, C::SMEM, stream, a);
+            else
+                hipLaunchKernelGGL((conv_fprop_ws_kernel<CE, false>), grid, block, C::SMEM, stream, a);
+            return 0;
+        }
+    }
     if (a.bn_y != nullptr) {      // activation mask of the producing layer (MASK instantiation: 16x16x32 form only)
         if constexpr (C::MASK_OK) {
             hipLaunchKernelGGL((conv_fprop_ws_kernel<C, false, false, true, false, true>), dim3(a.GM * a.NTL), dim3(C::NT), C::SMEM + 2048,
@@ -1292,7 +1513,9 @@ bool ws14_serves(const FdArgs& a) {
 
 int launch_ws14(FdArgs& a, hipStream_t stream) {
     using C = WsCfg14;
-    static const int attr_rc = segnb_opt_in_lds("fprop_ws", C::SMEM, conv_fprop_ws_kernel<C, false>, conv_fprop_ws_kernel<C, false, false, false>);
+    using CE = WsEpi<C>;
+    static const int attr_rc = segnb_opt_in_lds("fprop_ws", C::SMEM, conv_fprop_ws_kernel<C, false>, conv_fprop_ws_kernel<C, false, false, false>,
+                                                conv_fprop_ws_kernel<CE, false>, conv_fprop_ws_kernel<CE, false, false, false>);
     if (attr_rc) return attr_rc;
     a.HB = a.H / C::R;
     a.WB = a.W / C::WT;
@@ -1306,6 +1529,13 @@ int launch_ws14(FdArgs& a, hipStream_t stream) {
     if (gm > a.IT) gm = a.IT;
     a.GM = gm;
     if (g_segnb_census_on) segnb_census("tile:ws14");      // (beside the selector's "kernel:fprop_dma": which tile served it)
+    if (ws_epi_selected(WS_EPI_DEFAULT)) {
+        if (a.stats == nullptr && segnb_knob_fprop_nostats())
+            hipLaunchKernelGGL((conv_fprop_ws_kernel<CE, false, false, false>), dim3(a.GM * a.NTL), dim3(C::NT), C::SMEM, stream, a);
+        else
+            hipLaunchKernelGGL((conv_fprop_ws_kernel<CE, false>), dim3(a.GM * a.NTL), dim3(C::NT), C::SMEM, stream, a);
+        return 0;
+    }
     if (a.stats == nullptr && segnb_knob_fprop_nostats())
         hipLaunchKernelGGL((conv_fprop_ws_kernel<C, false, false, false>), dim3(a.GM * a.NTL), dim3(C::NT), C::SMEM, stream, a);
     else

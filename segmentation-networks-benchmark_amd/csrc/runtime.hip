@@ -360,6 +360,10 @@ int segnb_knob_fprop_ksplit() {
 }
 static int g_fprop_dma_dbg = 0;
 int segnb_knob_fprop_dma_dbg() { return g_fprop_dma_dbg; }
+// conv_fprop_ws_kernel, where the previous tile's store rows run (fprop_dma.hip: WsEpi): -1 = the per-configuration default,
+// 0 = behind the MFMAs of their tap (every launch), 1 = in the MFMA gaps wherever that instantiation exists
+static int g_fprop_dma_epi = -1;
+int segnb_knob_fprop_dma_epi() { return g_fprop_dma_epi; }
 // The share of the CUs the WIDE weight-gradient launches size their pixel split for (segnb_conv_wgrad_slabs and the launches
 // that follow), as a RECORDABLE call: a model whose side stream is the longer one (UNet16: 12 ms of weight gradients against a
 // 17 ms dependent chain that ends 1.7 ms earlier) takes all CUs for them, another in the same process keeps the default half;
@@ -472,6 +476,10 @@ extern "C" int segnb_tune(const char* key, int value) {
     }
     if (strcmp(key, "fprop_ksplit") == 0) {
         g_fprop_ksplit = value < 0 ? 0 : value;
+        return 0;
+    }
+    if (strcmp(key, "fprop_dma_epi") == 0) {
+        g_fprop_dma_epi = value < 0 ? -1 : (value ? 1 : 0);
         return 0;
     }
     if (strcmp(key, "fprop_dma_dbg") == 0) {      // timing builds only: results are WRONG when non-zero
