@@ -11,6 +11,7 @@ typedef __attribute__((ext_vector_type(2))) unsigned u32x2_t;
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4_t;
 typedef __attribute__((ext_vector_type(2))) short s16x2_t;
+typedef __attribute__((ext_vector_type(2))) unsigned short u16x2_t;
 typedef __attribute__((address_space(3))) bf16x4_t* lds_bf16x4_ptr;
 typedef __attribute__((address_space(3))) unsigned char* lds_u8_ptr;
 

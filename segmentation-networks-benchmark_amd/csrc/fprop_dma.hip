@@ -35,6 +35,7 @@
 #include "common.h"
 
 #include "fprop_dma.h"
+#include "tile_div.h"
 
 #include <mutex>
 #include <vector>
@@ -44,6 +45,13 @@
 #endif
 
 namespace {
+
+// conv_fprop_ws_kernel's argument: FdArgs and the two divisions of the halo waves' tile switch (set_fetch_tile: tile index ->
+// image, tile row, tile column) as multiplier / shift pairs of tile_div.h, filled by the launchers (ws_tile_div).  A struct of
+// its own behind FdArgs: that one is conv_fprop_rw_kernel's argument too, and its kernels keep their argument layout.
+struct WsArgs : FdArgs {
+    TileDiv div_hw, div_w;      // / (HB * WB), / WB
+};
 
 // in-kernel time stamps of block 0 (timing builds, segnb_tune("fprop_dma_dbg", 32)): [role][step][4] shader clocks.
 // The instrumented kernels are SEPARATE instantiations (template flag DBG): as run-time checks the stamp / timing-build
@@ -166,7 +174,7 @@ struct ws_epi_of<C, std::enable_if_t<C::EPI>> : std::true_type {};
 // (In the matrix waves themselves -- 32 registers per tile in the accumulator layout, or 2 x 8 in flight three taps ahead of a
 // fold -- the loads either spilled or stalled the MFMA stream: 64 -> 64 @ 1024 x 1024 x 4 took 673 us against 486 plain.)
 template <class C, bool DBG, bool EP = false, bool STATS = true, bool SPLITK = false, bool MASK = false>
-__global__ __launch_bounds__(512) void conv_fprop_ws_kernel(const FdArgs a) {
+__global__ __launch_bounds__(512) void conv_fprop_ws_kernel(const WsArgs a) {
     static_assert(!SPLITK || (!EP && !DBG && C::UP == 0 && C::NTAP == 9), "split K: plain 3 x 3 forward / data gradient");
     static_assert(!MASK || (STATS && !EP && !DBG && !SPLITK && C::MF16 && C::UP == 0 && C::NTAP == 9 && !C::TALL && C::BM == 256 &&
                             C::BN == 64 && C::WAVES_M == 4 && C::SMEM + 2048 <= 160 * 1024),
@@ -346,7 +354,14 @@ __global__ __launch_bounds__(512) void conv_fprop_ws_kernel(const FdArgs a) {
             // The same call writes the tile's output pixel table (read by the store rows one tile later).
             unsigned a_rel[APW], a_xy[APW], a_voff[C::NPL][APW];
             unsigned a_uoff[APW];         // virtual concat: the same halo pixels in the low-resolution tensor u
-            const bool vcat = a.u != nullptr;
+            // ... and their offset in u relative to the tile: halo pixel (h0 + xr, w0 + xc) is u pixel ((h0 + xr) >> 1, (w0 + xc) >> 1),
+            // and as the tile origin (hb R, wb WT) is even the halves split into the origin's and the lane's
+            constexpr bool VCAT = !C::UPD && !C::UPF && !C::TALL;
+            static_assert(!VCAT || (R % 2 == 0 && WT % 2 == 0), "virtual concat: even tile origins");
+            unsigned a_urel[VCAT ? APW : 1];
+            unsigned a_sec = 0;           // (P32) bit pa: this lane's slot of piece pa holds the chunk's SECOND plane
+            static_assert(APW <= 32, "one bit per halo piece");
+            const bool vcat = VCAT && a.u != nullptr;
         #pragma unroll
             for (int pa = 0; pa < APW; ++pa) {
                 const int pix = ((lw & 1) + C::NAW * pa) * 8 + (lane >> 3);
@@ -359,8 +374,44 @@ __global__ __launch_bounds__(512) void conv_fprop_ws_kernel(const FdArgs a) {
                     if (a.P32)       // 32-channel planes: slots 0..3 / 4..7 of a halo row come from the chunk's first / second plane
                         a_rel[pa] = (unsigned)((xr * a.Wi + xc) * 2) * (unsigned)a.ld_x * 2u + (unsigned)(((q ^ ((key >> 1) & 7)) & 3) * 16);
                 a_xy[pa] = pix < C::NPIX ? (unsigned)xr | ((unsigned)xc << 16) : 0x7fff7fffu;      // never inside the image
+                // (one opaque value per piece: the border test of every piece stays the same straight-line code, whether the piece
+                // can hold the filler or not)
+                asm volatile("" : "+v"(a_xy[pa]));
+                a_sec |= (unsigned)(((q ^ ((xc >> 1) & 7)) >> 2) & 1) << pa;
+                if constexpr (VCAT)
+                    a_urel[pa] = vcat ? (unsigned)(((a.dhmin + xr) >> 1) * a.Wu + ((a.dwmin + xc) >> 1)) * (unsigned)a.ld_u * 2u +
+                                            (unsigned)((q ^ ((key >> 1) & 7)) * 16)
+                                      : 0u;
             }
-            auto set_fetch_tile = [&](int it, int table) {
+            // the output pixel table: per lane the tile row / column of its entries and their pixel offset from the tile's first pixel
+            constexpr int NPR = (BM + C::NAW * 64 - 1) / (C::NAW * 64);
+            unsigned p_rc[NPR], p_rel[NPR];
+        #pragma unroll
+            for (int k = 0; k < NPR; ++k) {
+                const int rr = (lw & 1) * 64 + lane + k * C::NAW * 64;
+                const int row = rr / WT, col = rr % WT;
+                const bool in_tile = R * WT == BM || rr < R * WT;      // (14 x 14 tiles: rows 196..223 are dummies)
+                p_rc[k] = in_tile ? (unsigned)row | ((unsigned)col << 16) : 0x7fff7fffu;
+                asm volatile("" : "+v"(p_rc[k]));
+                p_rel[k] = C::UPF ? (unsigned)(4 * row * a.W + 2 * col) : (unsigned)(row * a.W + col);
+            }
+            // One axis of a tile's border test as two scalars: the halo coordinates x (16-bit field of a_xy) with
+            // 0 <= o + x < lim are those with (x - lo) mod 2^16 <= len1; an empty range (a dead tile: lim = 0) takes lo = 2^15,
+            // which no field reaches (real coordinates are below 64, the filler is 0x7fff: the range ends below that).
+            auto axis = [](int o, int lim, unsigned& lo, unsigned& len1) {
+                const int l = max(-o, 0), h = min(lim - o, 0x7fff);
+                lo = h > l ? (unsigned)l : 0x8000u;
+                len1 = h > l ? (unsigned)(h - l - 1) : 0u;
+            };
+            // both fields of xy inside their ranges: two packed 16-bit operations and one compare
+            auto inside = [](unsigned xy, unsigned lo2, unsigned len2) {
+                const u16x2_t d = __builtin_bit_cast(u16x2_t, xy) - __builtin_bit_cast(u16x2_t, lo2);
+                const u16x2_t m = __builtin_elementwise_max(d, __builtin_bit_cast(u16x2_t, len2));
+                return __builtin_bit_cast(unsigned, m) == len2;
+            };
+            auto set_fetch_tile = [&](int it_, int table) {
+                // the tile index and everything derived from it is wave-uniform: scalar registers, scalar unit
+                const int it = C::TALL ? it_ : __builtin_amdgcn_readfirstlane(it_);
                 const bool live = it < a.IT;
                 if constexpr (C::TALL) {
                     // virtual row v of the tall image -> (image v / (H+1), row v % (H+1)); row H of an image is the shared
@@ -390,32 +441,31 @@ __global__ __launch_bounds__(512) void conv_fprop_ws_kernel(const FdArgs a) {
                     }
                     return;
                 }
-                const int n = it / (a.HB * a.WB);
+                // (image, tile row, tile column) of the tile: the launcher's multiplier / shift pairs (tile_div.h), no division
+                const int n = (int)tile_div((unsigned)it, a.div_hw);
                 const int rem = it - n * (a.HB * a.WB);
-                const int hb = rem / a.WB, wb = rem - hb * a.WB;
+                const int hb = (int)tile_div((unsigned)rem, a.div_w), wb = rem - hb * a.WB;
+                unsigned lo_r, lo_c, len_r, len_c;
                 if constexpr (C::UPD) {
                     // plane (py, px): halo position (xr, xc) = plane pixel (hb R - py + xr, wb WT - px + xc), valid inside
                     // the H x W plane; its source is dz pixel (2 Yp + py, 2 Xp + px).  (32-bit wrap-around arithmetic: the
                     // tile origin may lie one plane pixel outside the tensor, a VALID lane's offset never does)
-                    const unsigned hlim = live ? (unsigned)a.H : 0u;
                     static_for<4>([&](auto pl_c) {
                         constexpr int pl = decltype(pl_c)::value, py = pl >> 1, px = pl & 1;
                         const int y0 = hb * R - py, x0 = wb * WT - px;
                         const unsigned base = (unsigned)(((n * a.Hi + 2 * y0 + py) * a.Wi + 2 * x0 + px) * a.ld_x * 2);
+                        axis(y0, live ? a.H : 0, lo_r, len_r);
+                        axis(x0, a.W, lo_c, len_c);
+                        const unsigned lo2 = lo_r | (lo_c << 16), len2 = len_r | (len_c << 16);
         #pragma unroll
-                        for (int pa = 0; pa < APW; ++pa) {
-                            const int yp = y0 + (int)(a_xy[pa] & 0xffffu), xp = x0 + (int)(a_xy[pa] >> 16);
-                            const bool ok = (unsigned)yp < hlim && (unsigned)xp < (unsigned)a.W;
-                            a_voff[pl][pa] = ok ? base + a_rel[pa] : OOB;
-                        }
+                        for (int pa = 0; pa < APW; ++pa) a_voff[pl][pa] = inside(a_xy[pa], lo2, len2) ? base + a_rel[pa] : OOB;
                     });
                     if (a.P32) {
                         // chunk c reads plane 2 c in its first four slots and plane 2 c + 1 in the others: fold the four
                         // plane sets into two per-chunk sets, lane by lane
         #pragma unroll
                         for (int pa = 0; pa < APW; ++pa) {
-                            const int xc = (int)(a_xy[pa] >> 16);
-                            const bool second = ((((int)lane & 7) ^ ((xc >> 1) & 7)) >> 2) != 0;
+                            const bool second = (a_sec >> pa & 1u) != 0;
                             a_voff[0][pa] = second ? a_voff[1][pa] : a_voff[0][pa];
                             a_voff[1][pa] = second ? a_voff[3][pa] : a_voff[2][pa];
                         }
@@ -423,31 +473,33 @@ __global__ __launch_bounds__(512) void conv_fprop_ws_kernel(const FdArgs a) {
                 } else {
                 const int h0 = hb * R + (C::UPF ? py - 1 : a.dhmin), w0 = wb * WT + (C::UPF ? px - 1 : a.dwmin);
                 const unsigned base = (unsigned)(((n * a.Hi + h0) * a.Wi + w0) * a.ld_x * 2);
-                const unsigned hlim = live ? (unsigned)a.Hi : 0u;
+                axis(h0, live ? a.Hi : 0, lo_r, len_r);
+                axis(w0, a.Wi, lo_c, len_c);
+                const unsigned lo2 = lo_r | (lo_c << 16), len2 = len_r | (len_c << 16);
         #pragma unroll
-                for (int pa = 0; pa < APW; ++pa) {
-                    const int hi = h0 + (int)(a_xy[pa] & 0xffffu), wi = w0 + (int)(a_xy[pa] >> 16);
-                    const bool ok = (unsigned)hi < hlim && (unsigned)wi < (unsigned)a.Wi;
-                    a_voff[0][pa] = ok ? base + a_rel[pa] : OOB;
-                    if (vcat) {      // nearest-x2 upsample = the pixel (hi >> 1, wi >> 1) of u, same channel slot
-                        const int pixl = ((lw & 1) + C::NAW * pa) * 8 + (lane >> 3);
-                        const int keyl = C::XC % 2 == 0 ? pixl % XC : pixl;
-                        a_uoff[pa] = ok ? (unsigned)((n * a.Hu + (hi >> 1)) * a.Wu + (wi >> 1)) * (unsigned)a.ld_u * 2u +
-                                              (unsigned)(((lane & 7) ^ ((keyl >> 1) & 7)) * 16)
-                                        : OOB;
+                for (int pa = 0; pa < APW; ++pa) a_voff[0][pa] = inside(a_xy[pa], lo2, len2) ? base + a_rel[pa] : OOB;
+                if constexpr (VCAT) {
+                    // nearest-x2 upsample = the pixel (hi >> 1, wi >> 1) of u, same channel slot.  (A loop of its own, the border test
+                    // taken again: one loop with this branch in it became selects that every launch without u paid for too)
+                    if (vcat) {
+                        const unsigned base_u = (unsigned)((n * a.Hu + hb * (R / 2)) * a.Wu + wb * (WT / 2)) * (unsigned)a.ld_u * 2u;
+        #pragma unroll
+                        for (int pa = 0; pa < APW; ++pa) a_uoff[pa] = inside(a_xy[pa], lo2, len2) ? base_u + a_urel[pa] : OOB;
                     }
                 }
                 }
                 // output pixel of tile rows (-1 = outside the image): 128 halo-wave threads, BM / 128 rows each
                 const int t128 = (lw & 1) * 64 + lane;
+                axis(0, live ? a.H - hb * R : 0, lo_r, len_r);       // tile row < rows of the image left below the tile's first
+                axis(0, a.W - wb * WT, lo_c, len_c);
+                const unsigned plo2 = lo_r | (lo_c << 16), plen2 = len_r | (len_c << 16);
+                // the tile's first pixel (UPF: of this block's phase in the high-resolution output; p_rel steps by two there)
+                const unsigned obase = C::UPF ? (unsigned)((n * 2 * a.H + 2 * hb * R + py) * (2 * a.W) + 2 * wb * WT + px)
+                                              : (unsigned)((n * a.H + hb * R) * a.W + wb * WT);
         #pragma unroll
-                for (int rr = t128; rr < BM; rr += C::NAW * 64) {
-                    const int ho = hb * R + rr / WT, wo = wb * WT + rr % WT;
-                    const bool in_tile = R * WT == BM || rr < R * WT;      // (14 x 14 tiles: rows 196..223 are dummies)
-                    if constexpr (C::UPF)       // the tile row's pixel of this block's phase in the high-resolution output
-                        sPix[table * BM + rr] = (live && ho < a.H && wo < a.W) ? (n * 2 * a.H + 2 * ho + py) * (2 * a.W) + 2 * wo + px : -1;
-                    else
-                        sPix[table * BM + rr] = (live && in_tile && ho < a.H && wo < a.W) ? (n * a.H + ho) * a.W + wo : -1;
+                for (int k = 0; k < NPR; ++k) {
+                    const int rr = t128 + k * C::NAW * 64;
+                    if (rr < BM) sPix[table * BM + rr] = inside(p_rc[k], plo2, plen2) ? (int)(obase + p_rel[k]) : -1;
                 }
             };
             auto fetch_a = [&](int p0, int p1, int c_, int buf) {
@@ -1367,7 +1419,7 @@ int ksplit_workspace(hipStream_t stream, size_t slab_bytes, int ntiles, float** 
 // split K pays where a launch has fewer (pixel tile, channel tile) pairs than half the CUs it may use: the 7 x 7 level of
 // lib/models/zf_unet.py:44-56 (8 tall row tiles x 8..16 channel tiles at bs = 32).  Returns the number of slices (1 = no split)
 template <class C>
-int ksplit_factor(const FdArgs& a, int it_total, int ntl, int nch) {
+int ksplit_factor(const WsArgs& a, int it_total, int ntl, int nch) {
     if (!C::TALL || !segnb_knob_fprop_ksplit()) return 1;
     if (a.ep_act >= 0 || a.dbg || a.up_out != nullptr) return 1;
     const long long tiles = (long long)it_total * ntl;
@@ -1403,8 +1455,17 @@ bool ws_epi_selected(bool by_default) {
 }
 constexpr bool WS_EPI_DEFAULT = true;
 
+// The tile switch's two divisions as multiplier / shift pairs (tile_div.h), once a.HB, a.WB and a.GM are set.  A halo wave passes
+// tile indices up to IT - 1 + 2 GM (the look-ahead of a block's last tiles); false when they leave the range the pairs are held to.
+bool ws_tile_div(WsArgs& a) {
+    if ((long long)a.N * a.HB * a.WB + 2ll * a.GM > (long long)TILE_DIV_MAX) return false;
+    a.div_hw = tile_div_make((uint32_t)(a.HB * a.WB));
+    a.div_w = tile_div_make((uint32_t)a.WB);
+    return true;
+}
+
 template <class C>
-int launch_ws(FdArgs& a, hipStream_t stream) {
+int launch_ws(WsArgs& a, hipStream_t stream) {
     if (a.bn_y != nullptr && !C::MASK_OK) return SEGNB_LAUNCH_DECLINED;      // (activation mask: 16 x 16 tiles, 16x16x32 form)
     static const int attr_rc = [] {
         int rc = segnb_opt_in_lds("fprop_ws", C::SMEM, conv_fprop_ws_kernel<C, false>, conv_fprop_ws_kernel<C, true>,
@@ -1440,6 +1501,7 @@ int launch_ws(FdArgs& a, hipStream_t stream) {
     a.NCH = a.Ci / 64;
     a.KS = 1;
     a.ntmajor = C::TALL ? 1 : 0;
+    a.div_hw = a.div_w = tile_div_make(1);      // (the tall form walks virtual rows: it has no tile grid to divide by)
     if constexpr (C::TALL) {
         const int ks = ksplit_factor<C>(a, a.IT, a.NTL, a.NCH);
         if (ks > 1 && ksplit_workspace(stream, (size_t)a.IT * a.NTL * ks * 65536, a.IT * a.NTL, &a.ks_slab, &a.ks_cnt) == 0) {
@@ -1460,6 +1522,8 @@ int launch_ws(FdArgs& a, hipStream_t stream) {
     if (gm < 1) gm = 1;
     if (gm > a.IT) gm = a.IT;
     a.GM = gm;
+    if constexpr (!C::TALL)
+        if (!ws_tile_div(a)) return SEGNB_LAUNCH_DECLINED;
     if constexpr (ws_has_epi<C>()) {
         // the store rows inside the MFMA stream (WsEpi): every form of this configuration but the affine epilogue's
         if (a.ep_act < 0 && ws_epi_selected(WS_EPI_DEFAULT)) {
@@ -1506,12 +1570,12 @@ int launch_ws(FdArgs& a, hipStream_t stream) {
 // forwards, the virtual concat among them) and without (the data gradients); everything else stays on the 256-row tiles.
 using WsCfg14 = WsCfg<64, 14, 14, 2, false, true>;
 
-bool ws14_serves(const FdArgs& a) {
+bool ws14_serves(const WsArgs& a) {
     return a.H % 14 == 0 && a.W % 14 == 0 && a.W <= 56 && a.Co > 32 && a.bn_y == nullptr && a.ep_act < 0 && !a.dbg &&
            a.up_out == nullptr && segnb_knob_fprop_mf16();
 }
 
-int launch_ws14(FdArgs& a, hipStream_t stream) {
+int launch_ws14(WsArgs& a, hipStream_t stream) {
     using C = WsCfg14;
     using CE = WsEpi<C>;
     static const int attr_rc = segnb_opt_in_lds("fprop_ws", C::SMEM, conv_fprop_ws_kernel<C, false>, conv_fprop_ws_kernel<C, false, false, false>,
@@ -1528,6 +1592,7 @@ int launch_ws14(FdArgs& a, hipStream_t stream) {
     if (gm < 1) gm = 1;
     if (gm > a.IT) gm = a.IT;
     a.GM = gm;
+    if (!ws_tile_div(a)) return SEGNB_LAUNCH_DECLINED;
     if (g_segnb_census_on) segnb_census("tile:ws14");      // (beside the selector's "kernel:fprop_dma": which tile served it)
     if (ws_epi_selected(WS_EPI_DEFAULT)) {
         if (a.stats == nullptr && segnb_knob_fprop_nostats())
@@ -1545,7 +1610,7 @@ int launch_ws14(FdArgs& a, hipStream_t stream) {
 
 // the plane gather (data gradient of an upsampled segment): one instantiation (no statistics, no epilogue)
 template <class C>
-int launch_ws_upd(FdArgs& a, hipStream_t stream) {
+int launch_ws_upd(WsArgs& a, hipStream_t stream) {
     static const int attr_rc = segnb_opt_in_lds("fprop_ws", C::SMEM, conv_fprop_ws_kernel<C, false, false, false>);
     if (attr_rc) return attr_rc;
     a.HB = (a.H + C::R - 1) / C::R;
@@ -1561,13 +1626,14 @@ int launch_ws_upd(FdArgs& a, hipStream_t stream) {
     if (gm < 1) gm = 1;
     if (gm > a.IT) gm = a.IT;
     a.GM = gm;
+    if (!ws_tile_div(a)) return SEGNB_LAUNCH_DECLINED;
     hipLaunchKernelGGL((conv_fprop_ws_kernel<C, false, false, false>), dim3(a.GM * a.NTL), dim3(C::NT), C::SMEM, stream, a);
     return 0;
 }
 
 // the forward of an up-sampled segment: four phases in one launch, accumulating (WsCfg UP_ = 2)
 template <class C>
-int launch_ws_upf(FdArgs& a, hipStream_t stream) {
+int launch_ws_upf(WsArgs& a, hipStream_t stream) {
     static const int attr_rc = segnb_opt_in_lds("fprop_ws", C::SMEM, conv_fprop_ws_kernel<C, false, false, true>);
     if (attr_rc) return attr_rc;
     a.HB = (a.H + C::R - 1) / C::R;
@@ -1584,6 +1650,7 @@ int launch_ws_upf(FdArgs& a, hipStream_t stream) {
     if (gm < 1) gm = 1;
     if (gm > a.IT) gm = a.IT;
     a.GM = gm;
+    if (!ws_tile_div(a)) return SEGNB_LAUNCH_DECLINED;
     hipLaunchKernelGGL((conv_fprop_ws_kernel<C, false, false, true>), dim3(a.GM * a.NTL), dim3(C::NT), C::SMEM, stream, a);
     return 0;
 }
@@ -1598,7 +1665,7 @@ bool upd_geometry(const segnb_conv_geom* g) {
     return true;
 }
 
-int try_upd(const segnb_conv_geom* g, FdArgs& a, hipStream_t stream) {
+int try_upd(const segnb_conv_geom* g, WsArgs& a, hipStream_t stream) {
     if (!upd_geometry(g)) return SEGNB_LAUNCH_DECLINED;
     a.Ktot = 16 * g->Ci;
     a.dhmin = a.dwmin = 0;
@@ -1627,7 +1694,7 @@ int try_upd(const segnb_conv_geom* g, FdArgs& a, hipStream_t stream) {
 // were not measured: they take the tile under the knob only.
 constexpr unsigned WS14_DEFAULT_LEVELS = 7u;
 
-int dispatch_fd(FdArgs& a, hipStream_t stream) {
+int dispatch_fd(WsArgs& a, hipStream_t stream) {
     // A/B testing (segnb_tune / environment): "fprop_dma" = 0 disables this path, "fprop_dma_cfg" forces a configuration
     // (0: 8 x 32, 1: 16 x 16, 2: tall 36 x 7, 3: 14 x 14 in 224 rows -- a launch the 14 x 14 form does not serve takes its
     // default tile: declined, not refused)
@@ -1701,7 +1768,7 @@ int segnb_fprop_upf_try(segnb_try_outcome* did, int N, int H, int W, int Ci, int
     *did = SEGNB_TRY_DECLINED;
     if (!segnb_knob_fprop_dma() || !segnb_knob_fprop_upd()) return 0;
     if (Ci % 64 != 0 || Ci < 128 || (Co <= 32 && !no_prev) || W < 12) return 0;
-    FdArgs a;
+    WsArgs a;
     a.x = (const bf16_t*)in;
     a.w = (const bf16_t*)wpacked;
     a.x_bytes = in_bytes;
@@ -1778,7 +1845,7 @@ int segnb_fprop_dma_try(segnb_try_outcome* did, const segnb_conv_geom* g, const 
                           stats != nullptr || bias != nullptr || !segnb_taps_3x3(g) || !segnb_knob_fprop_mask()))
         return 0;
     if (g->ntaps == 16 && ep == nullptr && stats == nullptr && bias == nullptr && segnb_knob_fprop_upd()) {
-        FdArgs a;
+        WsArgs a;
         a.x = (const bf16_t*)in;
         a.w = (const bf16_t*)wpacked;
         a.x_bytes = in_bytes;
@@ -1803,7 +1870,7 @@ int segnb_fprop_dma_try(segnb_try_outcome* did, const segnb_conv_geom* g, const 
     }
     if (!whole_output_3x3_s1(g) || g->Ci % 64 != 0) return 0;
     const segnb_tap_win win = segnb_tap_window(g);
-    FdArgs a;
+    WsArgs a;
     a.x = (const bf16_t*)in;
     a.w = (const bf16_t*)wpacked;
     a.x_bytes = in_bytes;

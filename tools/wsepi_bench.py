@@ -2,7 +2,8 @@
 """Stand-alone times of the conv_fprop_ws_kernel launches of the ZF_UNET bs=32 224x224 step that the WsEpi instantiations serve
 (segnb_tune "fprop_dma_epi": the previous tile's store rows inside the MFMA stream of their tap) -- 3 x 3 window, 16 x 16 or
 14 x 14 tiles, 112^2 .. 14^2: forward with statistics and data gradient of encK.l1 / .l2 (= decK.l2), the virtual-concat forward
-of decK.l1 and its skip-segment data gradient.
+of decK.l1 and its skip-segment data gradient -- and the three plane-gather launches (data gradient of decK.l1's up segment at
+56^2, 28^2 and 14^2 low resolution; below 12 columns another kernel serves it), which share the halo waves' tile switch.
 
     [SEGNB_LIB=<another build's libsegnb_hip.so>] python tools/wsepi_bench.py [--epi -1|0|1] [--reps 300] [--tag NAME]
 
@@ -84,7 +85,8 @@ def main():
         cu, cs = 2 * c, c
         wt = torch.randn(c, cu + cs, 3, 3, device='cuda') * 0.05
         op = UpCatConvOp(rt, wt, torch.zeros(c, device='cuda'), [(cu, cu), (cs, cs)], need_dgrad=True)
-        PackTable(rt, op.full.pack_jobs(hw, hw) + op.skip.pack_jobs(hw, hw), 'segnb_pack_weight_multi', 'segnb_pack_weight').run()
+        PackTable(rt, op.full.pack_jobs(hw, hw) + op.skip.pack_jobs(hw, hw) + op.up.pack_jobs(hw // 2, hw // 2),
+                  'segnb_pack_weight_multi', 'segnb_pack_weight').run()
         cat, dcat = View.alloc(rt, N, hw, hw, cu + cs), View.alloc(rt, N, hw, hw, cu + cs)
         cat.t.normal_()
         uv, duv = View.alloc(rt, N, hw // 2, hw // 2, cu), View.alloc(rt, N, hw // 2, hw // 2, cu)
@@ -97,6 +99,8 @@ def main():
         skip_dx = dcat.slice(cu, cs)
         report('dec%d.l1.vcat' % lvl, lambda: op.fprop(cat, yv, stats))
         report('dec%d.l1.skipdg' % lvl, lambda: op.skip.dgrad(dyv, skip_dx))
+        if hw // 2 >= 12:       # the up segment's data gradient on the low-resolution grid: the 2 x 2-window plane gather (plain order)
+            report('dec%d.l1.updg' % lvl, lambda: op.up.dgrad(dyv, duv))
         del cat, dcat
     print('%s total          %8.2f' % (args.tag, total))
 

@@ -11,6 +11,8 @@ then, from the stamped launch (256-row tiles: the timing instantiation exists fo
   row taps        the same over the taps that carry one (taps 1..8 of a tile's first chunk, from the block's second tile on)
   staging         last tap's stamp 3 -> the next tile's first stamp 0 (mean over the block's tiles)
   per tile        (row tap length - plain tap length) x 8 + staging: what a tile costs beyond its taps
+  switch          the barrier wait (stamp 2 -> 3) of tap 7 in the chunks where the halo waves switch to the next tile
+                  (set_fetch_tile: the chunk in front of a tile's last chunk), and of tap 7 in the other chunks
 (profiles/wsepi_ab.txt, section 0)."""
 import argparse
 import ctypes
@@ -69,7 +71,7 @@ def main():
     rt = Runtime('cuda', 'bf16')
     N = args.batch
     print('launch            alone us  steps/CU  us/step | plain taps: mfma  row  barrier  length | row taps: mfma  row  barrier  length |'
-          ' staging | per tile (cycles)')
+          ' staging | per tile (cycles) | tap 7 barrier: switch  other')
     for hw, c in LAUNCHES:
         wt = torch.randn(c, c, 3, 3, device='cuda') * 0.05
         op = ConvOp(rt, wt, torch.zeros(c, device='cuda'), [(c, c)], 1, 1, False, True)
@@ -95,7 +97,7 @@ def main():
                 os.makedirs(args.raw, exist_ok=True)
                 np.save(os.path.join(args.raw, 'stamps_%d_%s.npy' % (hw, what)), st)
             n = min(nsteps, 255)
-            plain, row, staging = [], [], []
+            plain, row, staging, switch, other7 = [], [], [], [], []
             for s in range(n):
                 tile, cs = divmod(s, nch * 9)
                 m = st[s]
@@ -105,13 +107,16 @@ def main():
                         staging.append(st[s + 1][0] - m[3])
                     nxt = m[3] - m[0]
                 rec = (m[1] - m[0], m[2] - m[1], m[3] - m[2], nxt)
+                if cs % 9 == 7:             # the switch stands in the chunk in front of the tile's last one (every chunk when there is one)
+                    (switch if cs // 9 == max(nch - 2, 0) else other7).append(m[3] - m[2])
                 (row if tile >= 1 and 1 <= cs <= 8 else plain).append(rec)
             pm = np.mean(plain, 0)
             rm = np.mean(row, 0) if row else np.zeros(4)
             sg = float(np.mean(staging)) if staging else 0.0
             per_tile = (rm[3] - pm[3]) * 8 + sg if row else sg
-            print('%3d^2 %3d->%-3d %-5s %7.2f  %8d  %7.3f | %16.0f %4.0f %8.0f %7.0f | %14.0f %4.0f %8.0f %7.0f | %7.0f | %8.0f' % (
-                hw, c, c, what, us, nsteps, us / nsteps, pm[0], pm[1], pm[2], pm[3], rm[0], rm[1], rm[2], rm[3], sg, per_tile), flush=True)
+            print('%3d^2 %3d->%-3d %-5s %7.2f  %8d  %7.3f | %16.0f %4.0f %8.0f %7.0f | %14.0f %4.0f %8.0f %7.0f | %7.0f | %8.0f | %21.0f %6.0f' % (
+                hw, c, c, what, us, nsteps, us / nsteps, pm[0], pm[1], pm[2], pm[3], rm[0], rm[1], rm[2], rm[3], sg, per_tile,
+                np.mean(switch) if switch else 0.0, np.mean(other7) if other7 else 0.0), flush=True)
 
 
 if __name__ == '__main__':
