@@ -48,8 +48,8 @@ int segnb_device_cus(void);
  *   "fprop_dma"      0 = never use the direct-to-LDS 3x3 pipeline (fprop_dma.hip), 1 = use it where it applies
  *   "fprop_dma_cfg"  -1 = automatic tile configuration, n >= 0 = force configuration n (0: 8 x 32 pixels, 1: 16 x 16, 2: tall 36 x 7,
  *                    3: 14 x 14 in 224 rows -- where a configuration does not serve a launch, the launch takes its default)
- *   "fprop_dma_epi"  where conv_fprop_ws_kernel runs the previous tile's store rows: -1 = per-configuration default, 0 = behind the
- *                    MFMAs of their tap, 1 = inside the MFMA stream wherever that instantiation exists (same bits either way)
+ *   "fprop_dma_epi"  how conv_fprop_ws_kernel's taps carry the previous tile's store rows: -1 = per-configuration default, 0 = chosen
+ *                    per tap at run time, 1 = peeled straight-line taps wherever that instantiation exists (same bits either way)
  *   "fprop_rw"       0 = never use the resident-weights pipeline of the thin layers (fprop_rw.hip)
  *   "fprop_dma_dbg"  timing builds (parts of the pipeline removed; results are WRONG when non-zero)
  *   "conv_cu_pct"    percentage (1..100) of the CUs the persistent convolution kernels size their grids for

@@ -127,7 +127,7 @@ bool segnb_fprop_general_forced();      // conv_igemm.hip: SEGNB_FPROP_GENERAL i
 int segnb_knob_fprop_dma();       // runtime.hip: segnb_tune() knobs
 int segnb_knob_fprop_dma_cfg();
 int segnb_knob_fprop_dma_dbg();
-int segnb_knob_fprop_dma_epi();   // -1 default, 0 / 1: store rows of conv_fprop_ws_kernel behind / inside the MFMA stream of their tap
+int segnb_knob_fprop_dma_epi();   // -1 default, 0 / 1: store rows of conv_fprop_ws_kernel on taps chosen at run time / on peeled taps
 int segnb_knob_fprop_nostats();   // 1: launches without statistics run the statistics-free instantiation of conv_fprop_ws_kernel
 int segnb_knob_rw_store_waves();  // 2 or 4 store waves in conv_fprop_rw_kernel
 int segnb_knob_bnreduce_fused();  // 1: segnb_conv_fprop_bnreduce_ok may say yes

@@ -40,10 +40,6 @@
 #include <mutex>
 #include <vector>
 
-#ifndef SEGNB_EXP
-#define SEGNB_EXP 0      // experiments on the production kernel (whole-file compile-time switches; never set in the build)
-#endif
-
 namespace {
 
 // conv_fprop_ws_kernel's argument: FdArgs and the two divisions of the halo waves' tile switch (set_fetch_tile: tile index ->
@@ -145,8 +141,8 @@ struct WsCfg {
     static_assert(TM + TN <= 6, "fragment wait statement");
 };
 
-// EPI: the instantiation that carries the previous tile's store rows INSIDE the MFMA stream of a tap (conv_fprop_ws_kernel, matrix
-// stream).  A wrapper type, not a ninth parameter: the instantiations of the plain order keep their symbols, so two builds can be
+// EPI: the instantiation whose taps are straight-line code -- which of them carries a store row of the previous tile is a
+// compile-time fact of the peeled first tile and first chunk (conv_fprop_ws_kernel, matrix stream).  A wrapper type, not a ninth parameter: the instantiations of the plain order keep their symbols, so two builds can be
 // compared kernel by kernel (tools/devcode_ab.py), and one library holds both orders behind segnb_tune("fprop_dma_epi").
 template <class C_>
 struct WsEpi : C_ {
@@ -184,8 +180,8 @@ __global__ __launch_bounds__(512) void conv_fprop_ws_kernel(const WsArgs a) {
     constexpr int OUT_ROW = C::OUT_ROW, NF = TM + TN;
     constexpr int NTAP = C::NTAP, KW = C::KW;
     constexpr int SM = NTAP & 3;                         // weight-ring stage of step (chunk cg, tap t) = (cg * SM + t) & 3
-    constexpr bool EPI = ws_epi_of<C>::value;            // store rows in the MFMA gaps (WsEpi)
-    static_assert(!EPI || (C::MF16 && !SPLITK && !EP && C::UP == 0 && C::NTAP == 9), "store rows in the MFMA gaps: 16x16x32 form, 3 x 3 window, whole-K tiles");
+    constexpr bool EPI = ws_epi_of<C>::value;            // store rows on peeled, straight-line taps (WsEpi)
+    static_assert(!EPI || (C::MF16 && !SPLITK && !EP && C::UP == 0 && C::NTAP == 9), "store rows on peeled taps: 16x16x32 form, 3 x 3 window, whole-K tiles");
 
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
     int* sPix = reinterpret_cast<int*>(smem + C::OFF_PIX);
@@ -337,12 +333,12 @@ __global__ __launch_bounds__(512) void conv_fprop_ws_kernel(const WsArgs a) {
                         constexpr int tf = t + 3 < NTAP ? t + 3 : t + 3 - NTAP;
                         const int cf = t + 3 < NTAP ? c : cn;
                         if (lw == 0) FD_STAMP(1, cg * 9 + t, 0);
-                        if (!(SEGNB_EXP & 1) && !(DBG && (a.dbg & 1))) fetch_b(cf, tf, (cg * SM + t + 3) & (NB - 1));
+                        if (!(DBG && (a.dbg & 1))) fetch_b(cf, tf, (cg * SM + t + 3) & (NB - 1));
                         if (lw == 0) FD_STAMP(1, cg * 9 + t, 1);
                         // the weights of tap t+2 (fetched during tap t-1) have landed: only this tap's fetch stays in flight
                         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(BPW) : "memory");
                         if (lw == 0) FD_STAMP(1, cg * 9 + t, 2);
-                        if (!(SEGNB_EXP & 64) || t % 3 == 2) raw_barrier();      // (experiment 64: one barrier per kernel row -- WRONG results, timing only)
+                        raw_barrier();
                         if (lw == 0) FD_STAMP(1, cg * 9 + t, 3);
                     });
                 }
@@ -605,7 +601,7 @@ __global__ __launch_bounds__(512) void conv_fprop_ws_kernel(const WsArgs a) {
                         constexpr int t = decltype(t_c)::value;
                         if (lw == C::NBW) FD_STAMP(2, cg * 9 + t, 0);
                         if constexpr (t < C::A_STEPS)
-                            if (!(SEGNB_EXP & 2) && !(DBG && (a.dbg & 2))) fetch_a(t * APS, (t + 1) * APS, cn, abuf ^ 1);
+                            if (!(DBG && (a.dbg & 2))) fetch_a(t * APS, (t + 1) * APS, cn, abuf ^ 1);
                         if constexpr (MASK) {
                             // the producing layer's activated output at THIS tile's pixels: 16 bytes (8 channels) x 16 rows per thread,
                             // requested behind the first chunk's first halo pieces (in flight for the whole tile: the counted wait of
@@ -623,7 +619,7 @@ __global__ __launch_bounds__(512) void conv_fprop_ws_kernel(const WsArgs a) {
                             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                         }
                         if (lw == C::NBW) FD_STAMP(2, cg * 9 + t, 2);
-                        if (!(SEGNB_EXP & 64) || t % 3 == 2) raw_barrier();      // (experiment 64: one barrier per kernel row -- WRONG results, timing only)
+                        raw_barrier();
                         if (lw == C::NBW) FD_STAMP(2, cg * 9 + t, 3);
                     });
                 }
@@ -648,10 +644,12 @@ __global__ __launch_bounds__(512) void conv_fprop_ws_kernel(const WsArgs a) {
         // their own -- no barrier: the first tap barrier of the next tile publishes it -- and the tile's coalesced
         // stores + BatchNorm statistics are issued one staged row per thread and tap during taps 1..RPT of the NEXT
         // tile.  Serialised, the epilogue was 2-2.5 k cycles per tile: 30 % of a 64 -> 64 tile, 7 % of a 256 -> 256 one.
-        // In the plain order a tap's row runs BEHIND the tap's last MFMA, in front of the barrier (in-kernel stamps,
-        // tools/wsepi_stamps.py: ~190 cycles per row tap in which the matrix pipe drains, 8 times per tile); the WsEpi
-        // instantiations (epi_tap below) place it BETWEEN the MFMAs, one step per gap.  The staging and the halo waves' switch
-        // to the next tile (set_fetch_tile, tap NTAP - 2) are the rest of what a tile costs beyond its taps: DESIGN.md 13.28.
+        // In both orders a tap's row runs BEHIND the tap's last MFMA, in front of the barrier (one tap body: `tap` below).  The
+        // plain order decides per tap at run time whether it carries a row (in-kernel stamps, tools/wsepi_stamps.py: ~190 cycles
+        // per row tap in which the matrix pipe drains, 8 times per tile); in the WsEpi instantiations it is a compile-time fact
+        // of peeled, straight-line taps -- that is the whole of their gain: placing the row BETWEEN the MFMAs, one fenced step
+        // per gap, measured the same on every launch and was removed.  The staging and the halo waves'
+        // switch to the next tile (set_fetch_tile, tap NTAP - 2) are the rest of what a tile costs beyond its taps.
         // ---- compute-side per-lane constants: fragment offsets (see the uniform kernel for the swizzle) -----------
         constexpr bool MF16 = C::MF16;
         int tile_no_out = 0;
@@ -866,69 +864,62 @@ __global__ __launch_bounds__(512) void conv_fprop_ws_kernel(const WsArgs a) {
 #pragma unroll
                 for (int q = 0; q < NRD; ++q) issue(q, 0, 0, arow[0], 0, 0);
             }
-            // ---- EPI: one tap, with or without a store row of the previous tile INSIDE its MFMA stream.  The row's two LDS reads go
-            // out at the tap's start, as in the plain order; they are older than every fragment read the tap issues, so the wait in
-            // front of the last pixel row of the tap's first K slice (at most the rd_before look-ahead reads outstanding) covers
-            // them, and from that gap on the row is worked off one step per MFMA gap: the store offset, the buffer_store_b128, then
-            // one statistics element per gap -- same thread, same row, same additions to s1[] / s2[] in the same order.  Every step
-            // is fenced by empty volatile statements naming its registers, which the compiler keeps in order with the MFMAs and the
-            // fragment reads.  Nothing but the barrier follows the last MFMA.
-            // Whether a tap carries a row is a COMPILE-TIME fact here (ROWS): the block's first tile is peeled off the tile loop and
-            // the first chunk off the chunk loop, so the taps are straight-line code.  (Chosen per tap at run time, the two bodies
-            // met in 8 diamonds per chunk and the fragment / accumulator registers no longer fitted: 256 VGPRs + 200-800 bytes of
-            // scratch.)
-            constexpr int RSTEPS = STATS ? 10 : 2;                  // gap steps of a store row
-            constexpr int SLOT0 = (TM16 - 1) * TN16;                // first gap behind the wait that covers the row reads
-            static_assert(!EPI || (NTAP == 9 && RSTEPS <= 2 * C::NMF - SLOT0), "a store row fits the gaps of a 3 x 3 window's tap");
-            auto epi_tap = [&](auto t_c, auto rows_c, f32x4_t (&accr)[TM16][TN16], bool first_chunk, int tile_no)
-                               __attribute__((always_inline)) {
-                constexpr int t = decltype(t_c)::value, ROWS = decltype(rows_c)::value;
+            int tile_no = 0;                                       // pixel table of tile k = k & 3 (written by the halo waves)
+            bool pending = false;                                  // a staged tile waits for its store rows
+            // ---- ONE TAP of the stream, for both orders: bases, stamps, the two K slices with their counted waits and look-ahead
+            // reads, the store row(s) of the previous tile that the tap carries, the barrier.  A row's two LDS reads go out at the
+            // tap's start (row_load); its store and statistics run behind the tap's last MFMA, in front of the barrier.  Whether a
+            // tap carries a row (MODE):
+            //   ROW_NONE  it does not;
+            //   ROW_ONE   one row, a compile-time fact: the peeled taps of the WsEpi tile body -- straight-line code;
+            //   ROW_RT    decided at run time, the plain order: taps 1..RPT of a tile's first chunk while a tile is pending (3 x 3
+            //             window), steps 1.. across its first chunks, a.RPS rows each (2 x 2 window: 4 taps per chunk).
+            // c: the chunk of the tile (the tile's first MFMAs take C = 0; ROW_RT: which step of the tile this is).
+            constexpr int ROW_NONE = 0, ROW_ONE = 1, ROW_RT = 2;
+            auto tap = [&](auto t_c, auto mode_c, f32x4_t (&accr)[TM16][TN16], int c) __attribute__((always_inline)) {
+                constexpr int t = decltype(t_c)::value, MODE = decltype(mode_c)::value;
                 constexpr int tn = t == NTAP - 1 ? 0 : t + 1;
                 const int a_base = (cg & 1) * C::A_BYTES;
+                const bool drain = pending && c == 0;          // (ROW_RT) this chunk carries the previous tile's stores
                 const int bstage = ((cg * SM + t) & (NB - 1)) * C::B_STAGE;
                 const int bnext = ((cg * SM + t + 1) & (NB - 1)) * C::B_STAGE;
                 const int anext = t == NTAP - 1 ? ((cg + 1) & 1) * C::A_BYTES : a_base;
                 if (wave == 0) FD_STAMP(0, cg * 9 + t, 0);
-                if constexpr (ROWS == 1) row_load(t - 1, sPix + ((tile_no + 3) & 3) * BM);
-                unsigned voff = OOB;
-                float rm = 0.f;
-                auto row_step = [&](int k) __attribute__((always_inline)) {      // (k: constant once the MFMA loops are unrolled)
-                    int& pix = row_pix;
-                    u32x4_t& v = row_v;
-                    if (k == 0) {
-                        if (DBG && (a.dbg & (4 | 16))) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // (timing builds: no fragment waits)
-                        asm volatile("" : "+v"(pix), "+v"(v));      // landed: older than the fragment reads just waited for
-                        const bool ok = cok && pix >= 0;
-                        voff = ok ? (unsigned)pix * (unsigned)a.ld_out * 2u + (unsigned)(n_base + cc * 8) * 2u : OOB;
-                        rm = ok ? 1.f : 0.f;
-                        asm volatile("" : "+v"(voff), "+v"(rm));
-                    } else if (k == 1) {
-                        asm volatile("" : "+v"(voff), "+v"(v) : : "memory");
-                        if (!(DBG && (a.dbg & 8))) __builtin_amdgcn_raw_buffer_store_b128(v, rs_out, (int)voff, 0, 0);
-                        asm volatile("" ::: "memory");
-                    } else if constexpr (STATS) {
-                        const int e = k - 2;
-                        if constexpr (MASK) asm volatile("" : "+v"(v), "+v"(s1[e]));
-                        else asm volatile("" : "+v"(v), "+v"(s1[e]), "+v"(s2[e]));
-                        const unsigned w = e < 2 ? v.x : e < 4 ? v.y : e < 6 ? v.z : v.w;
-                        const float f = __uint_as_float((e & 1) ? (w & 0xffff0000u) : (w << 16));      // (unpack8, element e)
-                        const float fm = f * rm;
-                        s1[e] += fm;
-                        if constexpr (!MASK) s2[e] += fm * fm;
-                        if constexpr (MASK) asm volatile("" : "+v"(s1[e]));
-                        else asm volatile("" : "+v"(s1[e]), "+v"(s2[e]));
+                constexpr bool row_tap = MODE == ROW_ONE || (MODE == ROW_RT && (NTAP != 9 || (t >= 1 && t <= C::RPT)));
+                bool do_row = MODE == ROW_ONE;
+                int krow = t - 1;
+                if constexpr (MODE == ROW_RT) {
+                    if constexpr (NTAP == 9) {
+                        do_row = drain;
+                    } else {
+                        // (a.RPS = 1: rows 0..RPT-1 on steps 1..RPT;  2: rows 2 k, 2 k + 1 on step k + 1 -- tiles of fewer
+                        // than RPT + 1 steps: 128 input channels)
+                        const int si = c * NTAP + t;
+                        krow = (si - 1) * a.RPS;
+                        do_row = pending && si >= 1 && krow < C::RPT;
                     }
-                };
+                }
+                if constexpr (row_tap)
+                    if (do_row) {
+                        row_load(krow, sPix + ((tile_no + 3) & 3) * BM);
+                        if constexpr (NTAP != 9)
+                            if (a.RPS == 2) row_load2(krow + 1, sPix + ((tile_no + 3) & 3) * BM);
+                    }
                 if (!(DBG && (a.dbg & 4))) {
                     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
                     for (int kk = 0; kk < 2; ++kk) {
                         const int cur = kk, nxt = kk ^ 1;
+                        // the slice fetched during this one: (t, 1) in this tap's stage, or (t + 1, 0) in the next tap's
                         const int wbase = kk == 0 ? bstage : bnext;
                         const int xbase = kk == 0 ? a_base + arow[t / KW] : anext + arow[tn / KW];
+                        // the current slice's x0, w0..w3 have landed (its x1..x3 may still be in flight; the
+                        // two row-store reads of a row tap are younger: the count is then conservative)
                         ws_wait_xw<TM16 - 1>(fx[cur][0], fw[cur]);
 #pragma unroll
                         for (int i = 0; i < TM16; ++i) {
+                            // row i's pixels have landed: the older x(i+1).. and the rd_before(i * TN16) reads of the next
+                            // slice may be outstanding (4 x 4: counts 4, 5, 6 -- one read every second MFMA gap)
                             static_for<TM16 - 1>([&](auto k_c) {
                                 constexpr int k = decltype(k_c)::value + 1;
                                 if (i == k) ws_wait1<TM16 - 1 - k + C::rd_before(k * TN16)>(fx[cur][k]);
@@ -940,9 +931,7 @@ __global__ __launch_bounds__(512) void conv_fprop_ws_kernel(const WsArgs a) {
                                     if (kk == 0) issue(C::rd_before(q), nxt, wbase, xbase, t, 1);
                                     else issue(C::rd_before(q), nxt, wbase, xbase, tn, 0);
                                 }
-                                const int s = kk * C::NMF + q - SLOT0;
-                                if (!(SEGNB_EXP & 256) && s >= 0 && s < ROWS * RSTEPS) row_step(s);
-                                if (t == 0 && kk == 0 && first_chunk)
+                                if (t == 0 && kk == 0 && c == 0)
                                     FD_MFMA16_0(accr[i][j], fw[cur][j], fx[cur][i]);
                                 else
                                     FD_MFMA16(accr[i][j], fw[cur][j], fx[cur][i]);
@@ -950,199 +939,45 @@ __global__ __launch_bounds__(512) void conv_fprop_ws_kernel(const WsArgs a) {
                         }
                     }
                     __builtin_amdgcn_s_setprio(0);
-                    if (SEGNB_EXP & 256) {      // (experiment 256: the peeled taps with the row BEHIND the MFMAs -- what the gaps are worth)
-#pragma unroll
-                        for (int s = 0; s < ROWS * RSTEPS; ++s) row_step(s);
-                    }
-                } else {
-#pragma unroll
-                    for (int s = 0; s < ROWS * RSTEPS; ++s) row_step(s);
                 }
                 if (wave == 0) FD_STAMP(0, cg * 9 + t, 1);
+                if constexpr (row_tap)
+                    if (do_row) {
+                        if (DBG && (a.dbg & (4 | 16))) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // (timing builds: no fragment reads behind the row's)
+                        if constexpr (NTAP != 9)
+                            asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(row_pix), "+v"(row_v), "+v"(row_pix2), "+v"(row_v2) : "n"(NRD));
+                        else
+                            asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(row_pix), "+v"(row_v) : "n"(NRD));     // older than the NRD look-ahead reads
+                        row_store();
+                        if constexpr (NTAP != 9)
+                            if (a.RPS == 2) row_store_of(row_pix2, row_v2);
+                        // ROW_ONE: the row's additions end HERE.  The run-time order has its branch around them; without one the
+                        // compiler sinks them into the next tap's MFMA stream and keeps their operands live across it (227 -> 251
+                        // VGPRs on 16 x 16 tiles, 256 and scratch on 14 x 14: DESIGN.md 13.30)
+                        if constexpr (MODE == ROW_ONE && STATS) {
+                            asm volatile("" : "+v"(s1[0]), "+v"(s1[1]), "+v"(s1[2]), "+v"(s1[3]), "+v"(s1[4]), "+v"(s1[5]), "+v"(s1[6]), "+v"(s1[7]));
+                            if constexpr (!MASK) asm volatile("" : "+v"(s2[0]), "+v"(s2[1]), "+v"(s2[2]), "+v"(s2[3]), "+v"(s2[4]), "+v"(s2[5]), "+v"(s2[6]), "+v"(s2[7]));
+                        }
+                    }
                 if (wave == 0) FD_STAMP(0, cg * 9 + t, 2);
                 raw_barrier();
                 if (wave == 0) FD_STAMP(0, cg * 9 + t, 3);
             };
-            int tile_no = 0;
-            bool pending = false;
-            if constexpr (EPI) {
-                // one tile: its chunks, then the staging.  PEND: 0 = the block's first tile, nothing to store yet; 1 = every later one
-                auto tile_body = [&](auto pend_c) __attribute__((always_inline)) {
-                    constexpr int PEND = decltype(pend_c)::value;
-                    f32x4_t acc[TM16][TN16];
-                    // the first chunk, peeled: from the block's second tile on its taps 1..RPT carry the previous tile's store rows
-                    static_for<NTAP>([&](auto t_c) {
-                        constexpr int t = decltype(t_c)::value;
-                        epi_tap(t_c, std::integral_constant<int, (PEND == 1 && t >= 1 && t <= C::RPT) ? 1 : 0>{}, acc, true, tile_no);
-                    });
-                    ++cg;
-                    for (int c = 1; c < a.NCH; ++c, ++cg)
-                        static_for<NTAP>([&](auto t_c) { epi_tap(t_c, std::integral_constant<int, 0>{}, acc, false, tile_no); });
-                    // (as below: the look-ahead reads have landed, the last MFMA results too, before compiler-scheduled code runs)
-                    ws_wait_xw<0>(fx[0][0], fw[0]);
-#pragma unroll
-                    for (int i = 1; i < TM16; ++i) ws_wait1<0>(fx[0][i]);
-                    asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::);
-                    // the staging of the plain order (below), without its split-K, affine and phase-forward forms
-                    const int r16 = lane & 15, g4 = lane >> 4;
-                    float4 bv[TN16];
-                    uint2 mrow[MASK ? TM16 : 1];
-                    if constexpr (MASK) {
-#pragma unroll
-                        for (int i = 0; i < TM16; ++i)
-                            mrow[i] = *reinterpret_cast<const uint2*>(smem + C::SMEM + (wm * C::WM + 16 * i + r16) * 8);
-                    } else {
-#pragma unroll
-                        for (int j = 0; j < TN16; ++j) bv[j] = *reinterpret_cast<const float4*>(sBias + wn * C::WN + 16 * j + 4 * g4);
-                    }
-#pragma unroll
-                    for (int i = 0; i < TM16; ++i) {
-                        const int row = wm * C::WM + 16 * i + r16;
-#pragma unroll
-                        for (int j = 0; j < TN16; ++j) {
-                            const int col = wn * C::WN + 16 * j + 4 * g4;
-                            uint2 pk;
-                            if constexpr (MASK) {
-                                const unsigned mb = (j < 2 ? mrow[i].x : mrow[i].y) >> (8 * ((2 * j + (g4 >> 1)) & 3) + 4 * (g4 & 1));
-                                const unsigned g01 = pack2bf(acc[i][j][0], acc[i][j][1]);
-                                const unsigned g23 = pack2bf(acc[i][j][2], acc[i][j][3]);
-                                const float g0 = __uint_as_float(g01 << 16), g1 = __uint_as_float(g01 & 0xffff0000u);
-                                const float g2 = __uint_as_float(g23 << 16), g3 = __uint_as_float(g23 & 0xffff0000u);
-                                pk.x = pack2bf((mb & 1u) ? g0 : g0 * mask_neg, (mb & 2u) ? g1 : g1 * mask_neg);
-                                pk.y = pack2bf((mb & 4u) ? g2 : g2 * mask_neg, (mb & 8u) ? g3 : g3 * mask_neg);
-                            } else {
-                                pk.x = pack2bf(acc[i][j][0] + bv[j].x, acc[i][j][1] + bv[j].y);
-                                pk.y = pack2bf(acc[i][j][2] + bv[j].z, acc[i][j][3] + bv[j].w);
-                            }
-                            *reinterpret_cast<uint2*>(sOut + row * OUT_ROW + col * 2) = pk;
-                        }
-                    }
-                    pending = true;
-                };
-                if (it < a.IT) {
-                    tile_body(std::integral_constant<int, 0>{});
-                    it += a.GM;
-                    ++tile_no;
-                }
-                for (; it < a.IT; it += a.GM, ++tile_no) tile_body(std::integral_constant<int, 1>{});
-            } else {
-            for (; it < a.IT; it += a.GM, ++tile_no) {
-                f32x4_t acc[TM16][TN16];
-                // UPF: what the skip segment's launch left at this tile's output pixels (4 bf16 per accumulator quad),
-                // requested now, added when the accumulators are staged -- a whole tile later
-                uint2 prev[C::UPF ? TM16 : 1][C::UPF ? TN16 : 1];
-                if constexpr (C::UPF) {
-                    const int r16 = lane & 15, g4 = lane >> 4;
-                    const int* tab = sPix + (tile_no & 3) * BM;
-#pragma unroll
-                    for (int i = 0; i < TM16; ++i) {
-                        const int opix = tab[wm * C::WM + 16 * i + r16];
-#pragma unroll
-                        for (int j = 0; j < TN16; ++j) {
-                            const int ch = n_base + wn * C::WN + 16 * j + 4 * g4;
-                            uint2 v = make_uint2(0u, 0u);
-                            if (opix >= 0 && ch < a.Co && !a.no_prev)
-                                v = *reinterpret_cast<const uint2*>(a.out + (long long)opix * a.ld_out + ch);
-                            prev[i][j] = v;
-                        }
-                    }
-                }
-                for (int c = 0; c < a.NCH; ++c, ++cg) {
-                    const int a_base = (cg & 1) * C::A_BYTES;
-                    const bool drain = pending && c == 0;
-                    static_for<NTAP>([&](auto t_c) {
-                        constexpr int t = decltype(t_c)::value;
-                        constexpr int tn = t == NTAP - 1 ? 0 : t + 1;
-                        auto& accr = acc;
-                        const int bstage = ((cg * SM + t) & (NB - 1)) * C::B_STAGE;
-                        const int bnext = ((cg * SM + t + 1) & (NB - 1)) * C::B_STAGE;
-                        const int anext = t == NTAP - 1 ? ((cg + 1) & 1) * C::A_BYTES : a_base;
-                        if (wave == 0) FD_STAMP(0, cg * 9 + t, 0);
-                        // the previous tile's store rows: one per tap from the tile's second step on -- taps 1..RPT of the first
-                        // chunk (3 x 3 window, compile-time) or steps 1..RPT across the first chunks (2 x 2 window: 4 taps each)
-                        constexpr bool row_tap9 = NTAP == 9 && t >= 1 && t <= C::RPT;
-                        bool do_row = false;
-                        int krow = t - 1;
-                        if constexpr (NTAP == 9) {
-                            do_row = drain;
-                        } else {
-                            // (a.RPS = 1: rows 0..RPT-1 on steps 1..RPT;  2: rows 2 k, 2 k + 1 on step k + 1 -- tiles of fewer
-                            // than RPT + 1 steps: 128 input channels)
-                            const int si = c * NTAP + t;
-                            krow = (si - 1) * a.RPS;
-                            do_row = pending && si >= 1 && krow < C::RPT;
-                        }
-                        if constexpr (row_tap9 || NTAP != 9)
-                            if (do_row) {
-                                row_load(krow, sPix + ((tile_no + 3) & 3) * BM);
-                                if constexpr (NTAP != 9)
-                                    if (a.RPS == 2) row_load2(krow + 1, sPix + ((tile_no + 3) & 3) * BM);
-                            }
-                        if (!(SEGNB_EXP & 4) && !(DBG && (a.dbg & 4))) {
-                            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-                            for (int kk = 0; kk < 2; ++kk) {
-                                const int cur = kk, nxt = kk ^ 1;
-                                // the slice fetched during this one: (t, 1) in this tap's stage, or (t + 1, 0) in the next tap's
-                                const int wbase = kk == 0 ? bstage : bnext;
-                                const int xbase = kk == 0 ? a_base + arow[t / KW] : anext + arow[tn / KW];
-                                // the current slice's x0, w0..w3 have landed (its x1..x3 may still be in flight; the
-                                // two row-store reads of a row tap are younger: the count is then conservative)
-                                ws_wait_xw<TM16 - 1>(fx[cur][0], fw[cur]);
-#pragma unroll
-                                for (int i = 0; i < TM16; ++i) {
-                                    // row i's pixels have landed: the older x(i+1).. and the rd_before(i * TN16) reads of the next
-                                    // slice may be outstanding (4 x 4: counts 4, 5, 6 -- one read every second MFMA gap)
-                                    static_for<TM16 - 1>([&](auto k_c) {
-                                        constexpr int k = decltype(k_c)::value + 1;
-                                        if (i == k) ws_wait1<TM16 - 1 - k + C::rd_before(k * TN16)>(fx[cur][k]);
-                                    });
-#pragma unroll
-                                    for (int j = 0; j < TN16; ++j) {
-                                        const int q = i * TN16 + j;
-                                        if (C::rd_before(q + 1) > C::rd_before(q) && !(SEGNB_EXP & 16) && !(DBG && (a.dbg & 16))) {
-                                            if (kk == 0) issue(C::rd_before(q), nxt, wbase, xbase, t, 1);
-                                            else issue(C::rd_before(q), nxt, wbase, xbase, tn, 0);
-                                        }
-                                        if (t == 0 && kk == 0 && c == 0)
-                                            FD_MFMA16_0(accr[i][j], fw[cur][j], fx[cur][i]);
-                                        else
-                                            FD_MFMA16(accr[i][j], fw[cur][j], fx[cur][i]);
-                                    }
-                                }
-                            }
-                            __builtin_amdgcn_s_setprio(0);
-                        }
-                        if (wave == 0) FD_STAMP(0, cg * 9 + t, 1);
-                        if constexpr (row_tap9 || NTAP != 9)
-                            if (do_row) {
-                                if (DBG && (a.dbg & 4)) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                                if constexpr (NTAP != 9)
-                                    asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(row_pix), "+v"(row_v), "+v"(row_pix2), "+v"(row_v2) : "n"(NRD));
-                                else
-                                    asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(row_pix), "+v"(row_v) : "n"(NRD));     // older than the NRD look-ahead reads
-                                row_store();
-                                if constexpr (NTAP != 9)
-                                    if (a.RPS == 2) row_store_of(row_pix2, row_v2);
-                            }
-                        if (wave == 0) FD_STAMP(0, cg * 9 + t, 2);
-                        raw_barrier();
-                        if (wave == 0) FD_STAMP(0, cg * 9 + t, 3);
-                    });
-                }
-                // look-ahead reads of the next tile's first slice must have LANDED before compiler-scheduled code runs
+            // behind a tile's last tap: the look-ahead reads of the next tile's first slice must have LANDED before compiler-scheduled
+            // code runs, and the last MFMA results before they are read
+            auto stream_landed = [&]() __attribute__((always_inline)) {
                 ws_wait_xw<0>(fx[0][0], fw[0]);
 #pragma unroll
                 for (int i = 1; i < TM16; ++i) ws_wait1<0>(fx[0][i]);
                 asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::);
-                if constexpr (SPLITK) {
-                    ks_last = ks_publish([&](auto p_c) { constexpr int p = decltype(p_c)::value; return acc[p / TN16][p % TN16]; });
-                    if (ks_last)
-                        ks_combine([&](auto p_c) { constexpr int p = decltype(p_c)::value; return acc[p / TN16][p % TN16]; },
-                                   [&](auto p_c, const f32x4_t v) { constexpr int p = decltype(p_c)::value; acc[p / TN16][p % TN16] = v; });
-                }
-                if (!SPLITK || ks_last) {
-                // accumulator tile (i, j): this lane holds channels 16 j + 4 g4 + {0..3} of pixel 16 i + r16
+            };
+            // UPF: what the skip segment's launch left at a tile's output pixels (4 bf16 per accumulator quad), requested at the
+            // tile's start, added when the accumulators are staged -- a whole tile later
+            uint2 prev[C::UPF ? TM16 : 1][C::UPF ? TN16 : 1];
+            // ---- ONE STAGING, for both orders: acc[TM16][TN16] -> the staged bf16 tile.  Plain: + bias; EP: affine + activation;
+            // UPF: + prev + bias, activation; MASK: the producing layer's activation mask, no bias.
+            // accumulator tile (i, j): this lane holds channels 16 j + 4 g4 + {0..3} of pixel 16 i + r16
+            auto stage = [&](f32x4_t (&acc)[TM16][TN16]) __attribute__((always_inline)) {
                 const int r16 = lane & 15, g4 = lane >> 4;
                 float4 bv[TN16], sv[TN16];
                 uint2 mrow[MASK ? TM16 : 1];      // MASK: the 64 mask bits of this lane's pixel rows (written by the halo waves)
@@ -1157,12 +992,12 @@ __global__ __launch_bounds__(512) void conv_fprop_ws_kernel(const WsArgs a) {
                     if constexpr (EP) sv[j] = *reinterpret_cast<const float4*>(sScale + wn * C::WN + 16 * j + 4 * g4);
                     else sv[j] = make_float4(1.f, 1.f, 1.f, 1.f);
                 }
+                // this lane's quad of tile (0, 0): row wm WM + r16, channel wn WN + 4 g4; tile (i, j) lies 16 i rows and 16 j channels on
+                unsigned char* const st0 = sOut + (wm * C::WM + r16) * OUT_ROW + (wn * C::WN + 4 * g4) * 2;
 #pragma unroll
                 for (int i = 0; i < TM16; ++i) {
-                    const int row = wm * C::WM + 16 * i + r16;
 #pragma unroll
                     for (int j = 0; j < TN16; ++j) {
-                        const int col = wn * C::WN + 16 * j + 4 * g4;
                         uint2 pk;
                         if constexpr (C::UPF) {
                             // (activation of a transposed convolution's own forward, segnb_upconv_fprop_act: max(v, v * neg) with
@@ -1185,15 +1020,69 @@ __global__ __launch_bounds__(512) void conv_fprop_ws_kernel(const WsArgs a) {
                             pk.x = pack2bf((mb & 1u) ? g0 : g0 * mask_neg, (mb & 2u) ? g1 : g1 * mask_neg);
                             pk.y = pack2bf((mb & 4u) ? g2 : g2 * mask_neg, (mb & 8u) ? g3 : g3 * mask_neg);
                         } else {
-                        pk.x = pack2bf(ep(acc[i][j][0], sv[j].x, bv[j].x), ep(acc[i][j][1], sv[j].y, bv[j].y));
-                        pk.y = pack2bf(ep(acc[i][j][2], sv[j].z, bv[j].z), ep(acc[i][j][3], sv[j].w, bv[j].w));
+                            pk.x = pack2bf(ep(acc[i][j][0], sv[j].x, bv[j].x), ep(acc[i][j][1], sv[j].y, bv[j].y));
+                            pk.y = pack2bf(ep(acc[i][j][2], sv[j].z, bv[j].z), ep(acc[i][j][3], sv[j].w, bv[j].w));
                         }
-                        *reinterpret_cast<uint2*>(sOut + row * OUT_ROW + col * 2) = pk;
+                        *reinterpret_cast<uint2*>(st0 + 16 * i * OUT_ROW + 16 * j * 2) = pk;
                     }
                 }
+            };
+            if constexpr (EPI) {
+                // WsEpi: whether a tap carries a row is a COMPILE-TIME fact -- the block's first tile is peeled off the tile loop and
+                // each tile's first chunk off the chunk loop, so the taps are straight-line code.  (Chosen per tap at run time the two
+                // bodies meet in 8 diamonds per chunk: the plain order, ~190 cycles per row tap -- DESIGN.md 13.28, 13.30.)
+                // PEND: 0 = the block's first tile, nothing to store yet; 1 = every later one: taps 1..RPT of the first chunk carry a row
+                auto tile_body = [&](auto pend_c) __attribute__((always_inline)) {
+                    constexpr int PEND = decltype(pend_c)::value;
+                    f32x4_t acc[TM16][TN16];
+                    static_for<NTAP>([&](auto t_c) {
+                        constexpr int t = decltype(t_c)::value;
+                        tap(t_c, std::integral_constant<int, (PEND == 1 && t >= 1 && t <= C::RPT) ? ROW_ONE : ROW_NONE>{}, acc, 0);
+                    });
+                    ++cg;
+                    for (int c = 1; c < a.NCH; ++c, ++cg)
+                        static_for<NTAP>([&](auto t_c) { tap(t_c, std::integral_constant<int, ROW_NONE>{}, acc, c); });
+                    stream_landed();
+                    stage(acc);
+                    pending = true;
+                };
+                if (it < a.IT) {
+                    tile_body(std::integral_constant<int, 0>{});
+                    it += a.GM;
+                    ++tile_no;
                 }
-                pending = !SPLITK || ks_last;
-            }
+                for (; it < a.IT; it += a.GM, ++tile_no) tile_body(std::integral_constant<int, 1>{});
+            } else {
+                for (; it < a.IT; it += a.GM, ++tile_no) {
+                    f32x4_t acc[TM16][TN16];
+                    if constexpr (C::UPF) {
+                        const int r16 = lane & 15, g4 = lane >> 4;
+                        const int* tab = sPix + (tile_no & 3) * BM;
+#pragma unroll
+                        for (int i = 0; i < TM16; ++i) {
+                            const int opix = tab[wm * C::WM + 16 * i + r16];
+#pragma unroll
+                            for (int j = 0; j < TN16; ++j) {
+                                const int ch = n_base + wn * C::WN + 16 * j + 4 * g4;
+                                uint2 v = make_uint2(0u, 0u);
+                                if (opix >= 0 && ch < a.Co && !a.no_prev)
+                                    v = *reinterpret_cast<const uint2*>(a.out + (long long)opix * a.ld_out + ch);
+                                prev[i][j] = v;
+                            }
+                        }
+                    }
+                    for (int c = 0; c < a.NCH; ++c, ++cg)
+                        static_for<NTAP>([&](auto t_c) { tap(t_c, std::integral_constant<int, ROW_RT>{}, acc, c); });
+                    stream_landed();
+                    if constexpr (SPLITK) {
+                        ks_last = ks_publish([&](auto p_c) { constexpr int p = decltype(p_c)::value; return acc[p / TN16][p % TN16]; });
+                        if (ks_last)
+                            ks_combine([&](auto p_c) { constexpr int p = decltype(p_c)::value; return acc[p / TN16][p % TN16]; },
+                                       [&](auto p_c, const f32x4_t v) { constexpr int p = decltype(p_c)::value; acc[p / TN16][p % TN16] = v; });
+                    }
+                    if (!SPLITK || ks_last) stage(acc);
+                    pending = !SPLITK || ks_last;
+                }
             }
             tile_no_out = tile_no;
             pending_out = pending;
@@ -1234,7 +1123,7 @@ __global__ __launch_bounds__(512) void conv_fprop_ws_kernel(const WsArgs a) {
                         constexpr bool row_tap = t >= 1 && t <= C::RPT;
                         if constexpr (row_tap)
                             if (drain) row_load(t - 1, sPix + ((tile_no + 3) & 3) * BM);
-                        if (!(SEGNB_EXP & 4) && !(DBG && (a.dbg & 4))) {
+                        if (!(DBG && (a.dbg & 4))) {
                             __builtin_amdgcn_s_setprio(1);
     #pragma unroll
                             for (int kk = 0; kk < 4; ++kk) {
@@ -1260,8 +1149,7 @@ __global__ __launch_bounds__(512) void conv_fprop_ws_kernel(const WsArgs a) {
     #pragma unroll
                                     for (int j = 0; j < TN; ++j) {
                                         const int q = i * TN + j;
-                                        if (!(SEGNB_EXP & 16) && !(DBG && (a.dbg & 16))) FD_READ(fr[set_new][q], ad[q]);
-                                        if ((SEGNB_EXP & 128) && i > 0) continue;      // (experiment 128: half the MFMAs -- timing only)
+                                        if (!(DBG && (a.dbg & 16))) FD_READ(fr[set_new][q], ad[q]);
                                         if (t == 0 && kk == 0 && c == 0)
                                             FD_MFMA0(accr[i][j], fr[set_cur][j], fr[set_cur][TN + i]);
                                         else
@@ -1278,7 +1166,7 @@ __global__ __launch_bounds__(512) void conv_fprop_ws_kernel(const WsArgs a) {
                                 row_store();
                             }
                         if (wave == 0) FD_STAMP(0, cg * 9 + t, 2);
-                        if (!(SEGNB_EXP & 64) || t % 3 == 2) raw_barrier();      // (experiment 64: one barrier per kernel row -- WRONG results, timing only)
+                        raw_barrier();
                         if (wave == 0) FD_STAMP(0, cg * 9 + t, 3);
                     });
                 }
@@ -1464,6 +1352,66 @@ bool ws_tile_div(WsArgs& a) {
     return true;
 }
 
+// persistent blocks per channel tile: the CUs a launch may use (segnb_tune "conv_cu_pct") over its ntl channel tiles
+int ws_blocks(int ntl) {
+    const int gm = segnb_knob_conv_cus() / ntl;
+    return gm < 1 ? 1 : gm;
+}
+
+// The tile grid of a launch, once for the four launchers: HB x WB tiles per image, IT in all (the tall form: row tiles of the
+// virtual image), ntl channel tiles, GM persistent blocks per channel tile, and the tile switch's division pairs.  False where
+// ws_tile_div declines; the tall form walks virtual rows -- it has no tile grid to divide by and skips the division.
+template <class C>
+bool ws_tile_grid(WsArgs& a, int ntl) {
+    a.HB = (a.H + C::R - 1) / C::R;
+    a.WB = (a.W + C::WT - 1) / C::WT;
+    a.IT = C::TALL ? (a.N * (a.H + 1) + C::R - 1) / C::R : a.N * a.HB * a.WB;
+    a.NTL = ntl;
+    a.KS = 1;
+    a.ntmajor = C::TALL ? 1 : 0;
+    int gm = ws_blocks(ntl);
+    if (gm > a.IT) gm = a.IT;
+    a.GM = gm;
+    a.div_hw = a.div_w = tile_div_make(1);
+    return C::TALL || ws_tile_div(a);
+}
+
+// Which instantiation serves a launch whose grid is set, and the launch: activation mask / no statistics / timing build / plain, for
+// a configuration K = C or WsEpi<C>.  The affine epilogue (EP) exists in the plain order only.  PAIR: the configuration has the
+// statistics / no-statistics pair and nothing else (the 14 x 14 tile: ws14_serves).
+template <class K, bool PAIR = false>
+int ws_launch_form(const WsArgs& a, hipStream_t stream) {
+    const dim3 grid(a.GM * a.NTL), block(K::NT);
+    if constexpr (!PAIR) {
+        if (a.bn_y != nullptr) {      // activation mask of the producing layer (MASK instantiation: 256 x 64 tiles of the 16x16x32 form)
+            if constexpr (K::MASK_OK) {
+                hipLaunchKernelGGL((conv_fprop_ws_kernel<K, false, false, true, false, true>), grid, block, K::SMEM + 2048, stream, a);
+                return 0;
+            } else {
+                return SEGNB_LAUNCH_DECLINED;
+            }
+        }
+        if constexpr (!ws_epi_of<K>::value) {
+            if (a.ep_act >= 0) {      // (never with statistics: segnb_conv_fprop_act takes none)
+                hipLaunchKernelGGL((conv_fprop_ws_kernel<K, false, true, false>), grid, block, K::SMEM, stream, a);
+                return 0;
+            }
+        }
+    }
+    if (a.stats == nullptr && !a.dbg && segnb_knob_fprop_nostats()) {
+        hipLaunchKernelGGL((conv_fprop_ws_kernel<K, false, false, false>), grid, block, K::SMEM, stream, a);
+        return 0;
+    }
+    if constexpr (!PAIR) {
+        if (a.dbg) {
+            hipLaunchKernelGGL((conv_fprop_ws_kernel<K, true>), grid, block, K::SMEM, stream, a);
+            return 0;
+        }
+    }
+    hipLaunchKernelGGL((conv_fprop_ws_kernel<K, false>), grid, block, K::SMEM, stream, a);
+    return 0;
+}
+
 template <class C>
 int launch_ws(WsArgs& a, hipStream_t stream) {
     if (a.bn_y != nullptr && !C::MASK_OK) return SEGNB_LAUNCH_DECLINED;      // (activation mask: 16 x 16 tiles, 16x16x32 form)
@@ -1490,18 +1438,9 @@ int launch_ws(WsArgs& a, hipStream_t stream) {
         return rc;
     }();
     if (attr_rc) return attr_rc;
-    a.HB = (a.H + C::R - 1) / C::R;
-    a.WB = (a.W + C::WT - 1) / C::WT;
-    a.IT = a.N * a.HB * a.WB;
-    if (C::TALL) {
-        if (a.W > C::WT || a.Hi != a.H || a.Wi != a.W) return SEGNB_LAUNCH_DECLINED;
-        a.IT = (a.N * (a.H + 1) + C::R - 1) / C::R;
-    }
-    a.NTL = (a.Co + C::BN - 1) / C::BN;
+    if (C::TALL && (a.W > C::WT || a.Hi != a.H || a.Wi != a.W)) return SEGNB_LAUNCH_DECLINED;
+    if (!ws_tile_grid<C>(a, (a.Co + C::BN - 1) / C::BN)) return SEGNB_LAUNCH_DECLINED;
     a.NCH = a.Ci / 64;
-    a.KS = 1;
-    a.ntmajor = C::TALL ? 1 : 0;
-    a.div_hw = a.div_w = tile_div_make(1);      // (the tall form walks virtual rows: it has no tile grid to divide by)
     if constexpr (C::TALL) {
         const int ks = ksplit_factor<C>(a, a.IT, a.NTL, a.NCH);
         if (ks > 1 && ksplit_workspace(stream, (size_t)a.IT * a.NTL * ks * 65536, a.IT * a.NTL, &a.ks_slab, &a.ks_cnt) == 0) {
@@ -1518,49 +1457,11 @@ int launch_ws(WsArgs& a, hipStream_t stream) {
             return 0;
         }
     }
-    int gm = segnb_knob_conv_cus() / a.NTL;
-    if (gm < 1) gm = 1;
-    if (gm > a.IT) gm = a.IT;
-    a.GM = gm;
-    if constexpr (!C::TALL)
-        if (!ws_tile_div(a)) return SEGNB_LAUNCH_DECLINED;
     if constexpr (ws_has_epi<C>()) {
-        // the store rows inside the MFMA stream (WsEpi): every form of this configuration but the affine epilogue's
-        if (a.ep_act < 0 && ws_epi_selected(WS_EPI_DEFAULT)) {
-            using CE = WsEpi<C>;
-            const dim3 grid(a.GM * a.NTL), block(C::NT);
-            if (a.bn_y != nullptr) {
-                if constexpr (C::MASK_OK)
-                    hipLaunchKernelGGL((conv_fprop_ws_kernel<CE, false, false, true, false, true>), grid, block, C::SMEM + 2048, stream, a);
-                else
-                    return SEGNB_LAUNCH_DECLINED;
-            } else if (a.stats == nullptr && !a.dbg && segnb_knob_fprop_nostats())
-                hipLaunchKernelGGL((conv_fprop_ws_kernel<CE, false, false, false>), grid, block, C::SMEM, stream, a);
-            else if (a.dbg)
-                hipLaunchKernelGGL((conv_fprop_ws_kernel<CE, true>), grid, block, C::SMEM, stream, a);
-            else
-                hipLaunchKernelGGL((conv_fprop_ws_kernel<CE, false>), grid, block, C::SMEM, stream, a);
-            return 0;
-        }
+        // the store rows on straight-line taps (WsEpi): every form of this configuration but the affine epilogue's
+        if (a.ep_act < 0 && ws_epi_selected(WS_EPI_DEFAULT)) return ws_launch_form<WsEpi<C>>(a, stream);
     }
-    if (a.bn_y != nullptr) {      // activation mask of the producing layer (MASK instantiation: 16x16x32 form only)
-        if constexpr (C::MASK_OK) {
-            hipLaunchKernelGGL((conv_fprop_ws_kernel<C, false, false, true, false, true>), dim3(a.GM * a.NTL), dim3(C::NT), C::SMEM + 2048,
-                               stream, a);
-            return 0;
-        } else {
-            return SEGNB_LAUNCH_DECLINED;
-        }
-    }
-    if (a.ep_act >= 0)            // (never with statistics: segnb_conv_fprop_act takes none)
-        hipLaunchKernelGGL((conv_fprop_ws_kernel<C, false, true, false>), dim3(a.GM * a.NTL), dim3(C::NT), C::SMEM, stream, a);
-    else if (a.stats == nullptr && !a.dbg && segnb_knob_fprop_nostats())
-        hipLaunchKernelGGL((conv_fprop_ws_kernel<C, false, false, false>), dim3(a.GM * a.NTL), dim3(C::NT), C::SMEM, stream, a);
-    else if (a.dbg)
-        hipLaunchKernelGGL((conv_fprop_ws_kernel<C, true>), dim3(a.GM * a.NTL), dim3(C::NT), C::SMEM, stream, a);
-    else
-        hipLaunchKernelGGL((conv_fprop_ws_kernel<C, false>), dim3(a.GM * a.NTL), dim3(C::NT), C::SMEM, stream, a);
-    return 0;
+    return ws_launch_form<C>(a, stream);
 }
 
 // 14 x 14-pixel tiles in 224 matrix rows (cfg 3) for images whose sides are multiples of 14: the tile count, block order and
@@ -1581,31 +1482,11 @@ int launch_ws14(WsArgs& a, hipStream_t stream) {
     static const int attr_rc = segnb_opt_in_lds("fprop_ws", C::SMEM, conv_fprop_ws_kernel<C, false>, conv_fprop_ws_kernel<C, false, false, false>,
                                                 conv_fprop_ws_kernel<CE, false>, conv_fprop_ws_kernel<CE, false, false, false>);
     if (attr_rc) return attr_rc;
-    a.HB = a.H / C::R;
-    a.WB = a.W / C::WT;
-    a.IT = a.N * a.HB * a.WB;
-    a.NTL = (a.Co + C::BN - 1) / C::BN;
+    if (!ws_tile_grid<C>(a, (a.Co + C::BN - 1) / C::BN)) return SEGNB_LAUNCH_DECLINED;      // (sides are multiples of 14: whole tiles)
     a.NCH = a.Ci / 64;
-    a.KS = 1;
-    a.ntmajor = 0;
-    int gm = segnb_knob_conv_cus() / a.NTL;
-    if (gm < 1) gm = 1;
-    if (gm > a.IT) gm = a.IT;
-    a.GM = gm;
-    if (!ws_tile_div(a)) return SEGNB_LAUNCH_DECLINED;
     if (g_segnb_census_on) segnb_census("tile:ws14");      // (beside the selector's "kernel:fprop_dma": which tile served it)
-    if (ws_epi_selected(WS_EPI_DEFAULT)) {
-        if (a.stats == nullptr && segnb_knob_fprop_nostats())
-            hipLaunchKernelGGL((conv_fprop_ws_kernel<CE, false, false, false>), dim3(a.GM * a.NTL), dim3(C::NT), C::SMEM, stream, a);
-        else
-            hipLaunchKernelGGL((conv_fprop_ws_kernel<CE, false>), dim3(a.GM * a.NTL), dim3(C::NT), C::SMEM, stream, a);
-        return 0;
-    }
-    if (a.stats == nullptr && segnb_knob_fprop_nostats())
-        hipLaunchKernelGGL((conv_fprop_ws_kernel<C, false, false, false>), dim3(a.GM * a.NTL), dim3(C::NT), C::SMEM, stream, a);
-    else
-        hipLaunchKernelGGL((conv_fprop_ws_kernel<C, false>), dim3(a.GM * a.NTL), dim3(C::NT), C::SMEM, stream, a);
-    return 0;
+    if (ws_epi_selected(WS_EPI_DEFAULT)) return ws_launch_form<CE, true>(a, stream);
+    return ws_launch_form<C, true>(a, stream);
 }
 
 // the plane gather (data gradient of an upsampled segment): one instantiation (no statistics, no epilogue)
@@ -1613,20 +1494,12 @@ template <class C>
 int launch_ws_upd(WsArgs& a, hipStream_t stream) {
     static const int attr_rc = segnb_opt_in_lds("fprop_ws", C::SMEM, conv_fprop_ws_kernel<C, false, false, false>);
     if (attr_rc) return attr_rc;
-    a.HB = (a.H + C::R - 1) / C::R;
-    a.WB = (a.W + C::WT - 1) / C::WT;
-    a.IT = a.N * a.HB * a.WB;
-    a.NTL = (a.Co + C::BN - 1) / C::BN;
     a.P32 = a.Ci == 32;
     a.NCHP = a.P32 ? 1 : a.Ci / 64;
     a.NCH = a.P32 ? 2 : 4 * a.NCHP;
     a.RPS = a.NCH * C::NTAP - 1 < C::RPT ? 2 : 1;               // the previous tile's store rows ride on steps 1.., one or two each
     if ((a.NCH * C::NTAP - 1) * a.RPS < C::RPT) return SEGNB_LAUNCH_DECLINED;
-    int gm = segnb_knob_conv_cus() / a.NTL;
-    if (gm < 1) gm = 1;
-    if (gm > a.IT) gm = a.IT;
-    a.GM = gm;
-    if (!ws_tile_div(a)) return SEGNB_LAUNCH_DECLINED;
+    if (!ws_tile_grid<C>(a, (a.Co + C::BN - 1) / C::BN)) return SEGNB_LAUNCH_DECLINED;
     hipLaunchKernelGGL((conv_fprop_ws_kernel<C, false, false, false>), dim3(a.GM * a.NTL), dim3(C::NT), C::SMEM, stream, a);
     return 0;
 }
@@ -1636,21 +1509,13 @@ template <class C>
 int launch_ws_upf(WsArgs& a, hipStream_t stream) {
     static const int attr_rc = segnb_opt_in_lds("fprop_ws", C::SMEM, conv_fprop_ws_kernel<C, false, false, true>);
     if (attr_rc) return attr_rc;
-    a.HB = (a.H + C::R - 1) / C::R;
-    a.WB = (a.W + C::WT - 1) / C::WT;
-    a.IT = a.N * a.HB * a.WB;
     a.NTLR = (a.Co + C::BN - 1) / C::BN;
-    a.NTL = 4 * a.NTLR;
     a.NCH = a.Ci / 64;
     a.NCHP = a.NCH;
     a.P32 = 0;
     a.RPS = a.NCH * C::NTAP - 1 < C::RPT ? 2 : 1;               // store rows per step
     if ((a.NCH * C::NTAP - 1) * a.RPS < C::RPT) return SEGNB_LAUNCH_DECLINED;
-    int gm = segnb_knob_conv_cus() / a.NTL;
-    if (gm < 1) gm = 1;
-    if (gm > a.IT) gm = a.IT;
-    a.GM = gm;
-    if (!ws_tile_div(a)) return SEGNB_LAUNCH_DECLINED;
+    if (!ws_tile_grid<C>(a, 4 * a.NTLR)) return SEGNB_LAUNCH_DECLINED;
     hipLaunchKernelGGL((conv_fprop_ws_kernel<C, false, false, true>), dim3(a.GM * a.NTL), dim3(C::NT), C::SMEM, stream, a);
     return 0;
 }
@@ -1673,9 +1538,7 @@ int try_upd(const segnb_conv_geom* g, WsArgs& a, hipStream_t stream) {
     a.dh[2] = a.dh[3] = 1;          // 2 x 2 window, row-major: (0,0) (0,1) (1,0) (1,1)
     a.dw[1] = a.dw[3] = 1;
     // 8 x 32 or 16 x 16 output tiles: fewer rounds of (equal) tiles on the persistent blocks wins, ties go to 16 x 16
-    const int ntl = (g->Co + 63) / 64;
-    int gm = segnb_knob_conv_cus() / ntl;
-    if (gm < 1) gm = 1;
+    const int gm = ws_blocks((g->Co + 63) / 64);
     const long long it0 = (long long)g->N * ((g->Ho + 7) / 8) * ((g->Wo + 31) / 32);
     const long long it1 = (long long)g->N * ((g->Ho + 15) / 16) * ((g->Wo + 15) / 16);
     int cfg = segnb_knob_fprop_dma_cfg();
@@ -1719,9 +1582,7 @@ int dispatch_fd(WsArgs& a, hipStream_t stream) {
         // 8 x 32 or 16 x 16 pixel tiles: whichever needs fewer rounds of (equal) tiles on the persistent blocks --
         // re-measured with the final kernel, the round count decides every case (e.g. 128 -> 384 @56x56: 11 vs 12
         // rounds, 104 vs 122 us; 64 -> 192 @112x112: 21 vs 19 rounds, 133 vs 116 us); ties go to 16 x 16
-        const int ntl = (a.Co + 63) / 64;
-        int gm = segnb_knob_conv_cus() / ntl;
-        if (gm < 1) gm = 1;
+        const int gm = ws_blocks((a.Co + 63) / 64);
         const long long it0 = (long long)a.N * ((a.H + 7) / 8) * ((a.W + 31) / 32);
         const long long it1 = (long long)a.N * ((a.H + 15) / 16) * ((a.W + 15) / 16);
         const long long r0 = (it0 + gm - 1) / gm, r1 = (it1 + gm - 1) / gm;
@@ -1794,9 +1655,7 @@ int segnb_fprop_upf_try(segnb_try_outcome* did, int N, int H, int W, int Ci, int
     a.ep_act = ep_act;          // (UPF: applied in the accumulator staging of this instantiation, not the EP one)
     a.ep_coef = nullptr;
     a.ep_slope = ep_slope;
-    const int ntl = 4 * ((Co + 63) / 64);
-    int gm = segnb_knob_conv_cus() / ntl;
-    if (gm < 1) gm = 1;
+    const int gm = ws_blocks(4 * ((Co + 63) / 64));
     const long long it0 = (long long)N * ((H + 7) / 8) * ((W + 31) / 32);
     const long long it1 = (long long)N * ((H + 15) / 16) * ((W + 15) / 16);
     int cfg = segnb_knob_fprop_dma_cfg();

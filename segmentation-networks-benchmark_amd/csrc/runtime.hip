@@ -360,8 +360,8 @@ int segnb_knob_fprop_ksplit() {
 }
 static int g_fprop_dma_dbg = 0;
 int segnb_knob_fprop_dma_dbg() { return g_fprop_dma_dbg; }
-// conv_fprop_ws_kernel, where the previous tile's store rows run (fprop_dma.hip: WsEpi): -1 = the per-configuration default,
-// 0 = behind the MFMAs of their tap (every launch), 1 = in the MFMA gaps wherever that instantiation exists
+// conv_fprop_ws_kernel, how its taps carry the previous tile's store rows (fprop_dma.hip: WsEpi): -1 = the per-configuration
+// default, 0 = chosen per tap at run time (every launch), 1 = peeled straight-line taps wherever that instantiation exists
 static int g_fprop_dma_epi = -1;
 int segnb_knob_fprop_dma_epi() { return g_fprop_dma_epi; }
 // The share of the CUs the WIDE weight-gradient launches size their pixel split for (segnb_conv_wgrad_slabs and the launches

@@ -109,6 +109,48 @@ def test_spelled_out_sites_are_the_listed_ones():
     assert files_with(r'pack2bf\(\w+,\s*0\.f\)\s*<<\s*16', src) == {'wgrad_roll.hip': 1}
 
 
+# ---- conv_fprop_ws_kernel's 16x16x32 matrix stream: one tap body and one staging for both row orders ---------
+def _count(name, needle, src=None):
+    """occurrences of the literal text in one file, without the sites listed in SPELLED_OUT / LAUNCH_SPELLED_OUT"""
+    n = (src or sources())[name].count(needle)
+    for table in (SPELLED_OUT, LAUNCH_SPELLED_OUT):
+        for (f, text), reason in table.items():
+            assert reason
+            if f == name and needle in text:
+                n -= 1
+    return n
+
+
+def test_ws_stream_has_one_tap_body_and_one_staging():
+    src = sources()
+    # the tap: the plain order and WsEpi call one lambda, so each MFMA macro of the 16x16x32 form has one call site
+    assert _count('fprop_dma.hip', 'FD_MFMA16_0(', src) == 1
+    assert _count('fprop_dma.hip', 'FD_MFMA16(', src) == 1
+    # the staging: the MASK bit selection is written once (mb & 1u ... mask_neg, two lines of four selects)
+    assert len(re.findall(r'\(mb & 1u\)[^\n]*mask_neg', src['fprop_dma.hip'])) == 1
+    assert _count('fprop_dma.hip', 'mb & 1u', src) == 1 and _count('fprop_dma.hip', 'mb & 4u', src) == 1
+    # a store row's address, store and statistics: row_store_of only (the per-gap row_step is gone)
+    assert _count('fprop_dma.hip', '__builtin_amdgcn_raw_buffer_store_b128(v, rs_out', src) == 1
+    assert files_with(r'\brow_step\s*=\s*\[', src) == {} and files_with(r'\bepi_tap\b', src) == {}
+
+
+def test_whole_file_experiment_switches_are_gone():
+    assert files_with(r'SEGNB_EXP') == {}
+
+
+def test_ws_tile_grid_is_set_up_once():
+    src = sources()
+    # the persistent blocks per channel tile and their clamp to the tile count
+    assert _count('fprop_dma.hip', 'segnb_knob_conv_cus() / ', src) == 1
+    assert _count('fprop_dma.hip', 'if (gm > a.IT) gm = a.IT;', src) == 1
+    assert len(re.findall(r'a\.HB\s*=', src['fprop_dma.hip'])) == 1 and len(re.findall(r'a\.WB\s*=', src['fprop_dma.hip'])) == 1
+    # ws_tile_div: defined once, called by the one grid helper
+    assert len(re.findall(r'\bws_tile_div\(a\)', src['fprop_dma.hip'])) == 1
+    # the mask / no statistics / timing / plain ladder: one launch of each instantiation form per configuration type
+    assert _count('fprop_dma.hip', 'hipLaunchKernelGGL((conv_fprop_ws_kernel<K, true>)', src) == 1
+    assert len(re.findall(r'hipLaunchKernelGGL\(\(conv_fprop_ws_kernel<CE?,', src['fprop_dma.hip'])) == 4      # split K (2), plane gather, phase forward
+
+
 # ---- the host side of the kernel tries (DESIGN.md 13.27): window origin, descriptor extents, LDS opt-in, declined status --------
 # (file, text of the site) -> why the site is not routed through the helper of common.h; none so far
 LAUNCH_SPELLED_OUT = {}

@@ -7,6 +7,7 @@ ceil(S / r) * ceil(S / t) for every pair (r, t): the tile grids of the ZF_UNET, 
 them -- EVERY numerator from 0 to TILE_DIV_MAX, the bound beyond which the launchers decline: quotient with /, remainder with %.
 Beyond that bound the range the header proves (numerators below 2^30, divisors below 2^30) is sampled at its edges."""
 import os
+import re
 import shutil
 import subprocess
 
@@ -121,7 +122,12 @@ def test_launchers_decline_beyond_the_bound():
     """every launcher of conv_fprop_ws_kernel that walks a tile grid sets the pairs through ws_tile_div, which refuses a tile count
     (look-ahead included) beyond TILE_DIV_MAX; the kernel itself divides nowhere by the grid"""
     text = open(os.path.join(CSRC, 'fprop_dma.hip')).read()
-    assert text.count('if (!ws_tile_div(a)) return SEGNB_LAUNCH_DECLINED;') == 4       # launch_ws, launch_ws14, launch_ws_upd, launch_ws_upf
+    # launch_ws, launch_ws14, launch_ws_upd, launch_ws_upf: the grid comes from ws_tile_grid, and a refusal declines the launch ...
+    assert len(re.findall(r'if \(!ws_tile_grid<C>\(a, [^;]*\)\) return SEGNB_LAUNCH_DECLINED;', text)) == 4
+    assert len(re.findall(r'\ba\.GM\s*=\s*gm;', text)) == 1 and len(re.findall(r'\ba\.HB\s*=', text)) == 1
+    # ... which is ws_tile_div's, for every form but the tall one (no tile grid: it walks virtual rows)
+    grid = text[text.index('bool ws_tile_grid(WsArgs& a, int ntl) {'):text.index('int ws_launch_form(')]
+    assert 'return C::TALL || ws_tile_div(a);' in grid and grid.index('a.GM = gm;') < grid.index('ws_tile_div(a)')
     assert '2ll * a.GM > (long long)TILE_DIV_MAX) return false;' in text
     kernel = text[text.index('void conv_fprop_ws_kernel('):text.index('int ksplit_factor(')]
     for spelled in ('/ a.WB', '/ (a.HB', '% a.WB'):

@@ -1,5 +1,6 @@
-"""-m gpu: conv_fprop_ws_kernel with the previous tile's store rows INSIDE the MFMA stream of their tap (segnb_tune
-"fprop_dma_epi" = 1, the WsEpi instantiations) against the plain order (knob 0) and against float64.
+"""-m gpu: conv_fprop_ws_kernel with the previous tile's store rows on peeled, straight-line taps (segnb_tune
+"fprop_dma_epi" = 1, the WsEpi instantiations: which tap carries a row is a compile-time fact; the row runs behind the tap's
+last MFMA as in the plain order, one tap body for both) against the plain order (knob 0) and against float64.
 
 Every geometry runs under knob 1 first -- fresh tensors, the first launch of that geometry in the test: a counted wait that misses
 a read shows on a cold launch only -- then under knob 1 again, then under knob 0:
@@ -13,8 +14,10 @@ a read shows on a cold launch only -- then under knob 1 again, t
 
 Geometries whose instantiation keeps the plain order (split K, the tall 7 x 7 form, the 2 x 2-window plane gather of an up
 segment) run under knob 1 without "epi:1" in the census and keep their bits."""
+import ctypes
 import functools
 
+import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
@@ -44,7 +47,7 @@ STAT_RTOL = 1e-6
 
 class knobs(object):
     """segnb_tune settings for a block, back at their defaults afterwards"""
-    DEFAULTS = {'fprop_dma_epi': -1, 'fprop_dma_cfg': -1, 'conv_cu_pct': 100, 'call_census': 0, 'fprop_ksplit': 1}
+    DEFAULTS = {'fprop_dma_epi': -1, 'fprop_dma_cfg': -1, 'conv_cu_pct': 100, 'call_census': 0, 'fprop_ksplit': 1, 'fprop_dma_dbg': 0}
 
     def __init__(self, **kv):
         self.kv = {k: v for k, v in kv.items() if v is not None}
@@ -84,9 +87,17 @@ def _plain_case(name, N, H, W, Ci, Co):
     return w, b, x, dy, eb.conv_refs(x, w, b, dy, 1, 1, False)
 
 
-def _launch_plain(w, b, x, dy, epi, cu_pct=None, cfg=None, ksplit=None):
+def _read_stamps():
+    """the in-kernel stamps of the last stamped launch's block 0: [role][step][4] shader clocks (role 0 = matrix wave 0)"""
+    buf = (ctypes.c_ulonglong * (3 * 256 * 4))()
+    nv.call('segnb_debug_stamps', ctypes.cast(buf, ctypes.c_void_p))
+    return np.array(buf[:], dtype=np.uint64).reshape(3, 256, 4)
+
+
+def _launch_plain(w, b, x, dy, epi, cu_pct=None, cfg=None, ksplit=None, dbg=None, stamps=None):
     """forward with statistics and data gradient on FRESH tensors under fprop_dma_epi = epi
-    -> raw bf16 y [N,H,W,Cop], statistics [16,2,Cop] (every replica), raw bf16 dx, census of the two launches"""
+    -> raw bf16 y [N,H,W,Cop], statistics [16,2,Cop] (every replica), raw bf16 dx, census of the two launches
+    (dbg: segnb_tune "fprop_dma_dbg" for the two launches; stamps: a list that takes the stamps read behind each of them)"""
     N, Ci, H, W = x.shape
     Co = w.shape[0]
     rt = Runtime('cuda', 'bf16')
@@ -100,10 +111,13 @@ def _launch_plain(w, b, x, dy, epi, cu_pct=None, cfg=None, ksplit=None):
     dxv.t.fill_(3.0)
     stats = rt.zeros((16, 2, op.Cop), torch.float64)
     torch.cuda.synchronize()
-    with knobs(fprop_dma_epi=epi, fprop_dma_cfg=cfg, conv_cu_pct=cu_pct, fprop_ksplit=ksplit, call_census=1):
+    with knobs(fprop_dma_epi=epi, fprop_dma_cfg=cfg, conv_cu_pct=cu_pct, fprop_ksplit=ksplit, fprop_dma_dbg=dbg, call_census=1):
         nv.census_read()
-        op.fprop(xv, yv, stats)
-        op.dgrad(dyv, dxv)
+        for launch in (lambda: op.fprop(xv, yv, stats), lambda: op.dgrad(dyv, dxv)):
+            launch()
+            if stamps is not None:
+                torch.cuda.synchronize()
+                stamps.append(_read_stamps())
         census = nv.census_read()
     torch.cuda.synchronize()
     return yv.dense().contiguous().cpu(), stats.cpu(), dxv.dense().contiguous().cpu(), census
@@ -151,6 +165,37 @@ def test_epi_forward_and_data_gradient(name):
     _check_bounds(name, msgs, y1, dx1, r, Ci, Co)
     _check_stats(name + ' knob 1', msgs, st1, y1, Co)
     msgs = [m for m in msgs if m]
+    assert not msgs, '\n'.join(msgs)
+
+
+# ------------------------------------------------------------------------------------------------ timing instantiations
+@pytest.mark.parametrize('epi', [1, 0])
+def test_stamped_timing_instantiation_keeps_the_bits(epi):
+    """segnb_tune "fprop_dma_dbg" = 32 (stamps only, nothing removed) runs the DBG instantiations -- of WsEpi under knob 1, of the
+    plain order under knob 0 -- on several tiles per persistent block with rows pending across tiles: the outputs and every
+    statistics replica are the bits of the fprop_dma_dbg = 0 run, and matrix wave 0 of block 0 left its four stamps (tap start,
+    MFMAs issued, store row issued, past the barrier) on every tap of its first tile, non-zero and non-decreasing"""
+    name = '32x32 64->64 5 CUs'
+    N, H, W, Ci, Co, cu_pct, cfg = PLAIN[name]
+    w, b, x, dy, _ = _plain_case(name, N, H, W, Ci, Co)
+    y0, st0, dx0, c0 = _launch_plain(w, b, x, dy, epi, cu_pct, cfg)
+    before, stamps = _read_stamps(), []
+    y1, st1, dx1, c1 = _launch_plain(w, b, x, dy, epi, cu_pct, cfg, dbg=32, stamps=stamps)
+    assert c1 == c0 and c1.get('kernel:fprop_dma') == 2 and c1.get('epi:1', 0) == 2 * epi, (c1, c0)
+    msgs = []
+    for what, a, ref in (('y', y1, y0), ('dx', dx1, dx0), ('statistics (16 replicas)', st1, st0)):
+        _same(name, msgs, what, a, ref, 'the fprop_dma_dbg = 0 run')
+    ntaps = (Ci // 64) * 9          # the first tile of block 0: steps 0 .. ntaps - 1 of the matrix role
+    for what, st in zip(('forward', 'data gradient'), stamps):
+        m = st[0, :ntaps].astype(np.int64)
+        print('%s knob %d %s: stamps of the first tile relative to its start\n%s' % (name, epi, what, m - m[0, 0]))
+        if not (m != 0).all():
+            msgs.append('%s: a stamp of the first tile is zero' % what)
+        if not (np.diff(m, axis=1) >= 0).all():
+            msgs.append('%s: the four stamps of a tap decrease' % what)
+        if not (st[0, :ntaps] != before[0, :ntaps]).all():
+            msgs.append('%s: the launch left a stamp of the first tile as it found it' % what)
+        before = st
     assert not msgs, '\n'.join(msgs)
 
 
@@ -210,7 +255,7 @@ def test_epi_activation_mask_data_gradient():
 
 # ------------------------------------------------------------------------------------------------ 2 x 2-window plane gather
 # The data gradient of an up segment (UpCatConvOp.up).  Its store rows are chosen per step at run time (one or two a step), and
-# a run-time choice per tap does not fit the registers (fprop_dma.hip: epi_tap), so the 2 x 2-window forms have no WsEpi
+# that is the tap body's run-time mode (fprop_dma.hip: tap, ROW_RT), so the 2 x 2-window forms have no WsEpi
 # instantiation: under knob 1 they keep the plain order and their bits.
 # (N, S high resolution, Cu, Cs, Co, store rows per step or None where the gate declines the gather, so the general kernel runs it)
 UPD = {

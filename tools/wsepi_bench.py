@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Stand-alone times of the conv_fprop_ws_kernel launches of the ZF_UNET bs=32 224x224 step that the WsEpi instantiations serve
-(segnb_tune "fprop_dma_epi": the previous tile's store rows inside the MFMA stream of their tap) -- 3 x 3 window, 16 x 16 or
+(segnb_tune "fprop_dma_epi": the previous tile's store rows on peeled, straight-line taps) -- 3 x 3 window, 16 x 16 or
 14 x 14 tiles, 112^2 .. 14^2: forward with statistics and data gradient of encK.l1 / .l2 (= decK.l2), the virtual-concat forward
 of decK.l1 and its skip-segment data gradient -- and the three plane-gather launches (data gradient of decK.l1's up segment at
 56^2, 28^2 and 14^2 low resolution; below 12 columns another kernel serves it), which share the halo waves' tile switch.
