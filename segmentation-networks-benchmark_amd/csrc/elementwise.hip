@@ -1,8 +1,9 @@
 // The element-wise passes that are not BatchNorm (that family is norm_act.hip), NHWC, gfx950: the flat optimizer steps (SGD,
-// RMSprop, Adam), segnb_add, the general MaxPool2d(k, stride, pad) forward and its two backward forms, bilinear x2 upsampling
-// and the NHWC -> NCHW fp32 move.  One thread per 8-channel chunk, grid-stride loops; the launch geometry helpers are ew.h,
+// RMSprop, Adam), segnb_add, the general MaxPool2d(k, stride, pad) forward and its two backward forms, bilinear and nearest x2
+// upsampling and the NHWC -> NCHW fp32 move.  One thread per 8-channel chunk, grid-stride loops; the launch geometry helpers are ew.h,
 // and every launch is written once, generically in the element type (segnb_dispatch_dtype, common.h).
 #include "ew.h"
+#include "../../include/segnb_upsample.h"
 
 namespace {
 
@@ -405,6 +406,134 @@ extern "C" int segnb_upsample_bilinear2x_bwd(int dtype, const void* g_out, int l
             using T = SEGNB_TAG_T(tag);
             hipLaunchKernelGGL(upsample_bilinear2x_bwd_kernel<T>, dim3(grid), dim3(NTHR), 0, (hipStream_t)stream, (const T*)g_out,
                                ld_go, N, H, W, Cp / 8, (T*)dx, ld_dx);
+        }))
+        return rc;
+    SEGNB_LAUNCH_CHECK();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// nn.Upsample(scale_factor=2, mode='nearest') of lib/models/unet.py:53 (include/segnb_upsample.h): the bilinear pair above with
+// the weights removed.  One lane per 16 bytes (8 bf16 / 4 fp32 channels) of one LOW-resolution pixel, the lanes of a wave over
+// consecutive channels and then consecutive pixels of a row: the forward reads 1 and writes 4 vectors (the two of an output row
+// are neighbours in memory), the backward reads 4 and writes 1.  Pixel row r = n * H + h of the source is rows 2r, 2r + 1 of
+// the upsampled tensor, so the index takes two divisions (vectors per pixel, W); I32: the item count fits 32 bits and they
+// are reciprocal multiplications (FastDiv, as maxpool_bwd_idx_kernel).
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void load16(const float* p, float (&v)[4]) {
+    const float4 a = *reinterpret_cast<const float4*>(p);
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+}
+__device__ __forceinline__ void load16(const bf16_t* p, float (&v)[8]) { load8(p, v); }
+__device__ __forceinline__ void store16(float* p, const float (&v)[4]) { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
+__device__ __forceinline__ void store16(bf16_t* p, const float (&v)[8]) { store8(p, v); }
+
+// item -> (element offset of its vector in the low-resolution view of stride ld_lo, in the upsampled view of stride ld_hi)
+template <typename T, bool I32>
+__device__ __forceinline__ void nearest_item(long long i, int W, int VPP, const FastDiv& d_vpp, const FastDiv& d_w, int ld_lo,
+                                             int ld_hi, long long& lo, long long& hi) {
+    constexpr int E = 16 / (int)sizeof(T);
+    long long pix, row;
+    int c;
+    if constexpr (I32) {
+        const int p = d_vpp.div((int)i);
+        c = (int)i - p * VPP;
+        pix = p;
+        row = d_w.div(p);
+    } else {
+        pix = i / VPP;
+        c = (int)(i - pix * VPP);
+        row = pix / W;
+    }
+    const long long w = pix - row * W;
+    lo = pix * ld_lo + c * E;
+    hi = (4 * row * W + 2 * w) * ld_hi + c * E;           // pixel (2 * row, 2 * w) of [N * 2H][2W]
+}
+
+template <typename T, bool I32>
+__global__ __launch_bounds__(NTHR) void upsample_nearest2x_fwd_kernel(const T* __restrict__ x, int ld_x, long long total, int W, int VPP,
+                                                                      T* __restrict__ out, int ld_out) {
+    const FastDiv d_vpp(VPP), d_w(W);
+    const long long below = 2ll * W * ld_out;               // the same column, one output row down
+    for (long long i = blockIdx.x * (long long)NTHR + threadIdx.x; i < total; i += (long long)gridDim.x * NTHR) {
+        long long lo, hi;
+        nearest_item<T, I32>(i, W, VPP, d_vpp, d_w, ld_x, ld_out, lo, hi);
+        const uint4 v = *reinterpret_cast<const uint4*>(x + lo);
+        *reinterpret_cast<uint4*>(out + hi) = v;
+        *reinterpret_cast<uint4*>(out + hi + ld_out) = v;
+        *reinterpret_cast<uint4*>(out + hi + below) = v;
+        *reinterpret_cast<uint4*>(out + hi + below + ld_out) = v;
+    }
+}
+
+template <typename T, bool I32>
+__global__ __launch_bounds__(NTHR) void upsample_nearest2x_bwd_kernel(const T* __restrict__ go, int ld_go, long long total, int W, int VPP,
+                                                                      T* __restrict__ dx, int ld_dx) {
+    constexpr int E = 16 / (int)sizeof(T);
+    const FastDiv d_vpp(VPP), d_w(W);
+    const long long below = 2ll * W * ld_go;
+    for (long long i = blockIdx.x * (long long)NTHR + threadIdx.x; i < total; i += (long long)gridDim.x * NTHR) {
+        long long lo, hi;
+        nearest_item<T, I32>(i, W, VPP, d_vpp, d_w, ld_dx, ld_go, lo, hi);
+        float a[E], b[E], c[E], d[E];
+        load16(go + hi, a);
+        load16(go + hi + ld_go, b);
+        load16(go + hi + below, c);
+        load16(go + hi + below + ld_go, d);
+#pragma unroll
+        for (int e = 0; e < E; ++e) a[e] = ((a[e] + b[e]) + c[e]) + d[e];      // scan order, as the g_up of the BatchNorm and ELU passes
+        store16(dx + lo, a);
+    }
+}
+
+// the checks of both directions, under the caller's name; lo / hi: the low-resolution and the upsampled view
+static int check_nearest2x(const char* who, const void* lo, int ld_lo, const void* hi, int ld_hi, int N, int H, int W, int Cp) {
+    SEGNB_CHECK_ARG_AS(who, N > 0 && H > 0 && W > 0 && Cp > 0 && Cp % 8 == 0, "bad NHWC shape (Cp % 8 != 0?)");
+    SEGNB_CHECK_ARG_AS(who, (long long)N * H * W * 16 < (1ll << 31), "upsampled pixel count exceeds int32");
+    SEGNB_CHECK_ARG_AS(who, lo != nullptr && hi != nullptr, "NULL tensor");
+    SEGNB_CHECK_ARG_AS(who, ld_lo >= Cp && ld_hi >= Cp && ld_lo % 8 == 0 && ld_hi % 8 == 0, "pixel stride below Cp or not a multiple of 8");
+    SEGNB_CHECK_ARG_AS(who, (((uintptr_t)lo | (uintptr_t)hi) & 15) == 0, "tensors must be 16-byte aligned");
+    SEGNB_CHECK_ARG_AS(who, lo != hi, "the two tensors may not alias");
+    return 0;
+}
+
+// 8 blocks per CU of 256 CUs, the rest by the grid-stride loop: 32 KiB of loads per CU and trip in the forward, 128 KiB in the backward
+constexpr int NEAREST_MAX_BLOCKS = 2048;
+
+extern "C" int segnb_upsample_nearest2x_fwd(int dtype, const void* x, int ld_x, int N, int H, int W, int Cp, void* out, int ld_out,
+                                            segnb_stream_t stream) {
+    SEGNB_PLAN_RECORD(segnb_upsample_nearest2x_fwd, dtype, x, ld_x, N, H, W, Cp, out, ld_out, stream);
+    if (int rc = check_nearest2x(__func__, x, ld_x, out, ld_out, N, H, W, Cp)) return rc;
+    if (int rc = segnb_dispatch_dtype(dtype, "segnb_upsample_nearest2x_fwd", [&](auto tag) SEGNB_INLINE_LAMBDA {
+            using T = SEGNB_TAG_T(tag);
+            const int vpp = Cp / (16 / (int)sizeof(T));
+            const long long total = (long long)N * H * W * vpp;
+            int grid = ceil_div(total, NTHR);
+            if (grid > NEAREST_MAX_BLOCKS) grid = NEAREST_MAX_BLOCKS;
+            segnb_dispatch_bool(total < (1ll << 30), [&](auto I32) SEGNB_INLINE_LAMBDA {
+                hipLaunchKernelGGL((upsample_nearest2x_fwd_kernel<T, decltype(I32)::value>), dim3(grid), dim3(NTHR), 0, (hipStream_t)stream,
+                                   (const T*)x, ld_x, total, W, vpp, (T*)out, ld_out);
+            });
+        }))
+        return rc;
+    SEGNB_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int segnb_upsample_nearest2x_bwd(int dtype, const void* g_out, int ld_go, int N, int H, int W, int Cp, void* dx, int ld_dx,
+                                            segnb_stream_t stream) {
+    SEGNB_PLAN_RECORD(segnb_upsample_nearest2x_bwd, dtype, g_out, ld_go, N, H, W, Cp, dx, ld_dx, stream);
+    if (int rc = check_nearest2x(__func__, dx, ld_dx, g_out, ld_go, N, H, W, Cp)) return rc;
+    if (int rc = segnb_dispatch_dtype(dtype, "segnb_upsample_nearest2x_bwd", [&](auto tag) SEGNB_INLINE_LAMBDA {
+            using T = SEGNB_TAG_T(tag);
+            const int vpp = Cp / (16 / (int)sizeof(T));
+            const long long total = (long long)N * H * W * vpp;
+            int grid = ceil_div(total, NTHR);
+            if (grid > NEAREST_MAX_BLOCKS) grid = NEAREST_MAX_BLOCKS;
+            segnb_dispatch_bool(total < (1ll << 30), [&](auto I32) SEGNB_INLINE_LAMBDA {
+                hipLaunchKernelGGL((upsample_nearest2x_bwd_kernel<T, decltype(I32)::value>), dim3(grid), dim3(NTHR), 0, (hipStream_t)stream,
+                                   (const T*)g_out, ld_go, total, W, vpp, (T*)dx, ld_dx);
+            });
         }))
         return rc;
     SEGNB_LAUNCH_CHECK();

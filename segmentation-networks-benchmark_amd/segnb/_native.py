@@ -237,6 +237,13 @@ ELU_SIGNATURES = {
 }
 ELU_PLAIN = {'segnb_elu_ok': (c_int, [c_int, c_int, c_int, c_int, c_int])}
 
+# the nearest x2 upsample passes (nn.Upsample(scale_factor=2, mode='nearest') of unet.py:53), declared in include/segnb_upsample.h
+# (csrc/elementwise.hip, beside the bilinear pair whose argument order they share)
+UP_SIGNATURES = {
+    'segnb_upsample_nearest2x_fwd': [c_int, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P],
+    'segnb_upsample_nearest2x_bwd': [c_int, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P],
+}
+
 _lib = None
 _test_backend = None
 
@@ -261,7 +268,7 @@ def load():
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
     for name, argtypes in (list(SIGNATURES.items()) + list(MC_SIGNATURES.items()) + list(GCN_SIGNATURES.items())
-                           + list(ELU_SIGNATURES.items())):
+                           + list(ELU_SIGNATURES.items()) + list(UP_SIGNATURES.items())):
         fn = getattr(lib, name)         # AttributeError if the ABI and the header drift apart
         fn.argtypes = argtypes
         fn.restype = c_int

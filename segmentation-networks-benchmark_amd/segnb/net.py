@@ -9,7 +9,7 @@ Gradients of multi-consumer tensors (ResNet identity branches, dense concatenati
 ``contribute``: the first consumer's gradient buffer is adopted as is, later ones are added in place
 (segnb_add).  torch.cat is zero-copy as in the ZF_UNET plan: producers write into channel slices of one buffer.
 
-Used by lib.models.{unet16, linknet, tiramisu}; ZF_UNET keeps its hand-scheduled plan (fused pool/upsample
+Used by lib.models.{unet16, linknet, tiramisu, squeezenet, unet, unet_abn}; ZF_UNET keeps its hand-scheduled plan (fused pool/upsample
 routing, batched pack/unpack).
 """
 import contextlib
@@ -865,6 +865,32 @@ def upsample_bilinear2x(tape, x, tag='up'):
             return
         dx = tape.view(site + '/dx', xv.N, xv.H, xv.W, xv.Cp)
         nv.call('segnb_upsample_bilinear2x_bwd', rt.code, oa.g.ptr, oa.g.ld, xv.N, xv.H, xv.W, xv.Cp, dx.ptr, dx.ld, rt.stream)
+        tape.contribute(x, dx)
+
+    tape.record(backward)
+    return oa
+
+
+def upsample_nearest2x(tape, x, out=None, tag='up'):
+    """nn.Upsample(scale_factor=2, mode='nearest') (unet.py:53: up with upsample=True).
+
+    out: optional View to write into (the [skip | up] slice of a concat buffer); its gradient is then a slice of the concat
+    gradient, which the backward reads at that view's own pixel stride."""
+    rt, xv = tape.rt, x.v
+    site = tape.site(tag)
+    tape.consume(x)
+    ov = out if out is not None else tape.view(site + '/o', xv.N, 2 * xv.H, 2 * xv.W, xv.Cp)
+    if (ov.N, ov.H, ov.W, ov.Cp) != (xv.N, 2 * xv.H, 2 * xv.W, xv.Cp):
+        raise ValueError('upsample_nearest2x: out %s does not match the upsampled input %s'
+                         % ((ov.N, ov.H, ov.W, ov.Cp), (xv.N, 2 * xv.H, 2 * xv.W, xv.Cp)))
+    nv.call('segnb_upsample_nearest2x_fwd', rt.code, xv.ptr, xv.ld, xv.N, xv.H, xv.W, xv.Cp, ov.ptr, ov.ld, rt.stream)
+    oa = Act(ov, needs_grad=x.needs_grad)          # (a copy of a tensor nobody differentiates: its readers compute no gradient for it)
+
+    def backward():
+        if oa.g is None or not x.needs_grad:
+            return
+        dx = tape.view(site + '/dx', xv.N, xv.H, xv.W, xv.Cp)
+        nv.call('segnb_upsample_nearest2x_bwd', rt.code, oa.g.ptr, oa.g.ld, xv.N, xv.H, xv.W, xv.Cp, dx.ptr, dx.ld, rt.stream)
         tape.contribute(x, dx)
 
     tape.record(backward)

@@ -38,6 +38,12 @@ def get_loss(loss):
 
 def get_model(model_name, patch_size=None, num_channels=3):
     name = str.lower(model_name)
+    if name == 'unet':
+        from lib.models.unet import UNet
+        return UNet()                           # (the reference passes no arguments: torch_train.py:103-107)
+    if name == 'unet_abn':
+        from lib.models.unet_abn import UNetABN
+        return UNetABN()
     if name == 'zf_unet':
         from lib.models.zf_unet import ZF_UNET
         return ZF_UNET()

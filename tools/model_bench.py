@@ -27,6 +27,7 @@ def main():
     from lib.models.tiramisu import FCDenseNet103, FCDenseNet67
     from lib.models.unet16 import UNet16
     from lib.models.squeezenet import SqueezeNet
+    from lib.models.unet import UNet
     cfgs = [('ZF_UNET 512x512 bs=16 train', ZF_UNET, 16, 512, True, 414.1),
             ('LinkNet34 512x512 bs=16 train', LinkNet34, 16, 512, True, 138.5),
             ('FCDenseNet103 256x256 bs=8 train', lambda: FCDenseNet103(n_classes=1), 8, 256, True, 156.1),
@@ -34,6 +35,10 @@ def main():
             # (SqueezeNet: 2 * MACs of its 52 convolutions at 512 x 512 -- 240.2 GFLOP forward -- times three, less the first
             # layer's data gradient; 512 x 512 is the size in the reference file's own __main__)
             ('SqueezeNet 512x512 bs=16 train', SqueezeNet, 16, 512, True, 719.2),
+            # (UNet, 32 filters: 2 * MACs of its 18 3x3 convolutions and the 1x1 classifier at 512 x 512 -- 9.89 G MACs at 512^2,
+            # 6.64 G at each of 256^2, 128^2 and 64^2, 1.21 G at 32^2: 62.1 GFLOP forward -- times three, less the first layer's
+            # 0.45 GFLOP data gradient)
+            ('UNet 512x512 bs=16 train', UNet, 16, 512, True, 185.8),
             ('UNet16 1024x1024 bs=4 eval forward', UNet16, 4, 1024, False, 1279.0)]
     for name, ctor, B, S, train, gflop in cfgs:
         if args.only and args.only not in name:
