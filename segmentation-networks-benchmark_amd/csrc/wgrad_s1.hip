@@ -10,14 +10,19 @@
 // just a different pixel ROW of the same x tile, so ONE x tile (with halo) and ONE dy tile feed all nine
 // taps: x and dy are read once per (co-tile, ci-tile) instead of once per tap.
 //
-// Block = 256 threads.  Work item ("iteration") = R rows x WT columns of output pixels of one image.
+// Work item ("iteration") = R rows x WT columns of output pixels of one image (or R whole small images: WgTile, FLAT).
 //   x tile  : (R+2) x (WT+2) pixels x BCI channels,   dy tile : R x WT pixels x BCO channels
 //   K slab  = 16 consecutive pixels of one row = one v_mfma_f32_32x32x16_bf16 per (32co x 32ci x tap)
-//   tile 32x32 : the four waves split the slabs (K) of an iteration, 9 x 16 accumulators each
-//   tile 64x64 : wave (i,j) owns sub-tile (32i.., 32j..) for all slabs
+//   tile 32x32 : 256 threads; the four waves split the slabs (K) of an iteration, 9 x 16 accumulators each, and stage the tiles
+//                themselves
+//   tile 64x64 : 512 threads; four matrix waves -- wave (G, j) owns all 64 co x 32 ci (half j) for half of the taps (G), see
+//                "tap-split wave tiles" below -- plus four fetch waves that stage the next tile
 // Row strides are = 64 or 192 (mod 256) bytes so the four pixel rows a half-wave reads hit disjoint banks.
-// Single LDS buffer + register prefetch of the next iteration; iterations of a block are a contiguous
-// range (split over blocks), results merged with fp32 atomics into the packed [Co][9*Ci] workspace.
+// ONE LDS buffer: the next iteration's tiles wait in registers during the slab loop and are stored between two barriers.
+// The iterations of a layer are split into contiguous ranges ("pixel splits"); block (tile, split) OWNS its [BCO][9][BCI] piece
+// of partial slab `split` of the [nslab][Co][9*Ci] fp32 workspace and writes it with plain stores -- no atomics, no zeroing --
+// and a reduce kernel sums the slabs in a fixed order.  A single-slab launch with a segnb_wgrad_target stores straight into the
+// parameter's gradient.  The strided / wide-window sibling conv_wgrad_sx_kernel and the host side of both follow below.
 #include "device.h"
 
 #include <cstdlib>
@@ -51,24 +56,6 @@ __device__ __forceinline__ unsigned lds_addr(const void* p) { return (unsigned)(
 #define SEGNB_MFMA_V(acc, af, bf) \
     asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(af), "v"(bf))
 #define SEGNB_WAIT_LGKM(n) asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(n))
-
-#ifndef SEGNB_WG_TS
-#define SEGNB_WG_TS 1
-#endif
-#ifndef SEGNB_WG_WS_DB
-#define SEGNB_WG_WS_DB 0     // specialised blocks: 1 = two tile buffers (one barrier per iteration; same speed alone, but the
-                            // 128 KB block keeps other kernels off the CU: +0.8 % step time beside the main stream)
-#endif
-#ifndef SEGNB_WG_PACE
-#define SEGNB_WG_PACE 0      // s_sleep argument (x 64 clocks) after each paced tile store (0: none)
-#endif
-#ifndef SEGNB_WG_TALL
-#define SEGNB_WG_TALL 1
-#endif
-#ifndef SEGNB_WG_EXP
-#define SEGNB_WG_EXP 0       // timing experiments (wrong results): 1 = no global loads after the first tile, 2 = no MFMA loop,
-                              // 4 = no slab stores
-#endif
 
 struct WgS1Args {
     const bf16_t* x;
@@ -111,11 +98,10 @@ __device__ __forceinline__ void wg_tap(f32x16_t (&acc)[9], const bf16x4_t (&fa)[
 // slab S0 of SPW: request A of slab S0+1, then the nine taps.  Reads still allowed in flight when B_t of the
 // current slab is needed = everything issued after it = 2*(8-t) [rest of this slab] + 2 [next A] + 2*t [next
 // B_0..t-1] = 18 -> the 4-bit counter clamps it to 15; on the last slab 2*(8-t).
-template <int S0, int SPW, int KSPLIT, int SEGS, int WT, int XC, int SX, int SY, int MID, typename F>
+template <int S0, int SPW, int KSPLIT, int SEGS, int WT, int XC, int SX, int SY>
 __device__ __forceinline__ void wg_slabs(f32x16_t (&acc)[9], bf16x4_t (&fa)[2][2], bf16x4_t (&fb)[2][9][2],
-                                         unsigned va, const unsigned (&vb)[9], F& mid) {
+                                         unsigned va, const unsigned (&vb)[9]) {
     if constexpr (S0 < SPW) {
-        if constexpr (S0 == MID) mid();          // double-buffered tiles: the next iteration's LDS stores go here
         constexpr int cur = S0 & 1, nxt = cur ^ 1;
         constexpr bool more = S0 + 1 < SPW;
         constexpr int sn = (S0 + 1) * KSPLIT;
@@ -131,7 +117,7 @@ __device__ __forceinline__ void wg_slabs(f32x16_t (&acc)[9], bf16x4_t (&fa)[2][2
         wg_tap<6, more ? 15 : 4, more, ob, SX>(acc, fa[cur], fb[cur], fb[nxt], vb);
         wg_tap<7, more ? 15 : 2, more, ob, SX>(acc, fa[cur], fb[cur], fb[nxt], vb);
         wg_tap<8, more ? 15 : 0, more, ob, SX>(acc, fa[cur], fb[cur], fb[nxt], vb);
-        wg_slabs<S0 + 1, SPW, KSPLIT, SEGS, WT, XC, SX, SY, MID>(acc, fa, fb, va, vb, mid);
+        wg_slabs<S0 + 1, SPW, KSPLIT, SEGS, WT, XC, SX, SY>(acc, fa, fb, va, vb);
     }
 }
 
@@ -197,27 +183,26 @@ __device__ __forceinline__ void ts_first(bf16x4_t (&fa0)[2][2], bf16x4_t (&fb0)[
     }
 }
 
-template <int G, int S0, int SPW, int SEGS, int WT, int XC, int SX, int SY, int MID, typename F>
+template <int G, int S0, int SPW, int SEGS, int WT, int XC, int SX, int SY>
 __device__ __forceinline__ void ts_slabs(f32x16_t (&acc)[9], bf16x4_t (&fa)[2][2][2], bf16x4_t (&fb)[2][5][2],
-                                         unsigned va, const unsigned (&vb)[5], F& mid) {
+                                         unsigned va, const unsigned (&vb)[5]) {
     if constexpr (S0 < SPW) {
-        if constexpr (S0 == MID) mid();
         constexpr int cur = S0 & 1, nxt = cur ^ 1;
         constexpr bool more = S0 + 1 < SPW;
         constexpr int sn = S0 + 1;
         constexpr int oa = ((sn / SEGS) * WT + (sn % SEGS) * 16) * SY;
         constexpr int ob = ((sn / SEGS) * XC + (sn % SEGS) * 16) * SX;
         ts_units<G, 0, more, oa, ob, SX, SY>(acc, fa[cur], fb[cur], fa[nxt], fb[nxt], va, vb);
-        ts_slabs<G, S0 + 1, SPW, SEGS, WT, XC, SX, SY, MID>(acc, fa, fb, va, vb, mid);
+        ts_slabs<G, S0 + 1, SPW, SEGS, WT, XC, SX, SY>(acc, fa, fb, va, vb);
     }
 }
 
 // one iteration's slab loop of a tap-split wave (prologue requests + SPW slabs)
-template <int G, int SPW, int SEGS, int WT, int XC, int SX, int SY, int MID, typename F>
-__device__ __forceinline__ void ts_iteration(f32x16_t (&acc)[9], unsigned va, const unsigned (&vb)[5], F& mid) {
+template <int G, int SPW, int SEGS, int WT, int XC, int SX, int SY>
+__device__ __forceinline__ void ts_iteration(f32x16_t (&acc)[9], unsigned va, const unsigned (&vb)[5]) {
     bf16x4_t fa[2][2][2], fb[2][5][2];
     ts_first<G, 0, SX, SY>(fa[0], fb[0], va, vb);
-    ts_slabs<G, 0, SPW, SEGS, WT, XC, SX, SY, MID>(acc, fa, fb, va, vb, mid);
+    ts_slabs<G, 0, SPW, SEGS, WT, XC, SX, SY>(acc, fa, fb, va, vb);
 }
 
 template <int T, int SXB>
@@ -227,8 +212,6 @@ __device__ __forceinline__ void wg_first(bf16x4_t (&fb0)[9][2], const unsigned (
         wg_first<T + 1, SXB>(fb0, vb);
     }
 }
-
-constexpr bool wg_double_buffered(int tile_bytes) { return 2 * tile_bytes <= 160 * 1024; }
 
 constexpr int lds_stride(int channels) {
     // bytes; multiple of 16, >= 2*channels, == 64 or 192 (mod 256)
@@ -253,27 +236,14 @@ struct WgTile {
     static constexpr int YSTEP = FLAT ? PD : WT, XSTEP = FLAT ? XT : WT + 2;    // positions between those rows
 };
 
-// 64x64 tiles whose two buffers fit run WAVE-SPECIALISED: 4 matrix waves (tap-split units) + 4 fetch waves that stage the
-// next tile (global -> registers -> other LDS buffer).  With one wave per SIMD doing both, every staging instruction
-// (~300 VALU/VMEM/DS per iteration, mostly address arithmetic) sat between two MFMAs of an in-order wave: measured
-// 2.1 us per iteration = 1.5 us of MFMAs + 0.6 us of staging, whatever the prefetch distance or LDS read count.
-template <int BCO, int BCI, int R, int WT, bool FLAT>
-constexpr bool wg_specialised() {
-    using TL = WgTile<R, WT, FLAT>;
-    return SEGNB_WG_TS && BCO == 64 && BCI == 64;
-}
-// ... and with TWO tile buffers where they fit (SEGNB_WG_WS_DB): the fetch waves keep two tiles in flight in registers and store
-// the next one into the other buffer under the matrix waves' slab loop
-template <int BCO, int BCI, int R, int WT, bool FLAT>
-constexpr bool wg_ws_db() {
-    using TL = WgTile<R, WT, FLAT>;
-    return SEGNB_WG_WS_DB && wg_specialised<BCO, BCI, R, WT, FLAT>() &&
-           wg_double_buffered(TL::XROWS * lds_stride(BCI) + TL::YROWS * lds_stride(BCO));
-}
+// 64x64 tiles run WAVE-SPECIALISED: 4 matrix waves (tap-split units) + 4 fetch waves that stage the next tile (global ->
+// registers, and into the LDS buffer between the two barriers that end an iteration).  With one wave per SIMD doing both, every
+// staging instruction (~300 VALU/VMEM/DS per iteration, mostly address arithmetic) sat between two MFMAs of an in-order wave:
+// measured 2.1 us per iteration = 1.5 us of MFMAs + 0.6 us of staging, whatever the prefetch distance or LDS read count.
+constexpr bool wg_specialised(int bco, int bci) { return bco == 64 && bci == 64; }
 
 template <int BCO, int BCI, int R, int WT, bool FLAT = false, bool BNA = false>
-__global__ __launch_bounds__((wg_specialised<BCO, BCI, R, WT, FLAT>() ? 512 : 256), 1) void conv_wgrad_s1x9_kernel(
-    const WgS1Args a) {
+__global__ __launch_bounds__((wg_specialised(BCO, BCI) ? 512 : 256), 1) void conv_wgrad_s1x9_kernel(const WgS1Args a) {
     static_assert(!BNA || (!FLAT && BCO == 32), "the recomputed dy operand is built for the thin 32 x 32 tiles");
     using TL = WgTile<R, WT, FLAT>;
     constexpr int TCO = BCO / 32, TCI = BCI / 32;
@@ -288,17 +258,13 @@ __global__ __launch_bounds__((wg_specialised<BCO, BCI, R, WT, FLAT>() ? 512 : 25
     constexpr int YCH = TL::YROWS * (BCO / 8);
     constexpr int XPT = (XCH + 255) / 256, YPT = (YCH + 255) / 256;
 
-    // two tile buffers when they fit (every non-FLAT shape): the LDS stores of iteration it+1 are issued in the middle
-    // of iteration it's slab loop, under its MFMAs, and one barrier per iteration separates the buffers' roles
-    // (single buffer: MFMA drain -> barrier -> stores -> barrier -> first fragment reads, all exposed, every iteration)
-    constexpr int BUF = TL::XROWS * SX + TL::YROWS * SY;
-    constexpr bool DB = wg_ws_db<BCO, BCI, R, WT, FLAT>();
-
+    // ONE tile buffer (x tile, then dy tile): tile it+1 waits in registers during iteration it's slab loop and is stored between
+    // two barriers -- MFMA drain -> barrier -> stores -> barrier -> first fragment reads, every iteration
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* sX = smem;
     unsigned char* sY = smem + TL::XROWS * SX;
 
-    constexpr bool TS = wg_specialised<BCO, BCI, R, WT, FLAT>();
+    constexpr bool TS = wg_specialised(BCO, BCI);
     constexpr int NT = TS ? 512 : 256;
     const bool fetcher = TS && threadIdx.x >= 256;                 // waves 4..7 of a specialised block
     const int tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;
@@ -350,70 +316,60 @@ __global__ __launch_bounds__((wg_specialised<BCO, BCI, R, WT, FLAT>() ? 512 : 25
         }
     }
     uint4 rx[XPT], ry[YPT];
-    uint4 rx2[DB ? XPT : 1], ry2[DB ? YPT : 1];        // second tile in flight (double-buffered fetch waves)
-    auto gload_to = [&](int it, auto& rx, auto& ry) {
-        if constexpr (FLAT) {
-#pragma unroll
-            for (int u = 0; u < XPT; ++u) {
-                const int c = tid + u * 256;
-                const int row = c / (BCI / 8), cc = c - row * (BCI / 8);
-                const int g = row / TL::XT, q = row - g * TL::XT;
-                const int n = it * R + g;
-                const int hi = q / TL::W2 + a.dhmin, wi = q % TL::W2 + a.dwmin;
-                const int ch = ci0 + cc * 8;
-                uint4 v = make_uint4(0, 0, 0, 0);
-                if (c < XCH && n < a.N && ch < a.Ci && (unsigned)hi < (unsigned)a.Hi && (unsigned)wi < (unsigned)a.Wi) {
-                    if (a.u != nullptr && ch < a.Cu)
-                        v = *reinterpret_cast<const uint4*>(a.u + ((long long)(n * (a.Hi >> 1) + (hi >> 1)) * (a.Wi >> 1) + (wi >> 1)) * a.ld_u + ch);
-                    else
-                        v = *reinterpret_cast<const uint4*>(a.x + ((long long)(n * a.Hi + hi) * a.Wi + wi) * a.ld_x + (ch - (a.u != nullptr ? a.Cu : 0)));
-                }
-                rx[u] = v;
-            }
-#pragma unroll
-            for (int u = 0; u < YPT; ++u) {
-                const int c = tid + u * 256;
-                const int row = c / (BCO / 8), cc = c - row * (BCO / 8);
-                const int g = row / TL::PD, pp = row - g * TL::PD;
-                const int n = it * R + g;
-                const int ho = pp / TL::W2, wo = pp % TL::W2;
-                const int ch = co0 + cc * 8;
-                uint4 v = make_uint4(0, 0, 0, 0);
-                if (c < YCH && n < a.N && ch < a.Co && ho < a.H && wo < a.W)
-                    v = *reinterpret_cast<const uint4*>(a.dy + ((long long)(n * a.H + ho) * a.W + wo) * a.ld_dy + ch);
-                ry[u] = v;
-            }
-            return;
+    // v = 16 bytes (8 channels from `ch`) of x-tile pixel (n, hi, wi), in bounds: channels below Cu of a virtual concat are the
+    // nearest-x2 upsample of u, the others (all of them without one) come from x.  (Assigning through the reference keeps the code
+    // of the two written-out copies; a value-returning form compiles to other code.)
+    auto x_chunk = [&](int n, int hi, int wi, int ch, uint4& v) {
+        if (a.u != nullptr && ch < a.Cu)
+            v = *reinterpret_cast<const uint4*>(a.u + ((long long)(n * (a.Hi >> 1) + (hi >> 1)) * (a.Wi >> 1) + (wi >> 1)) * a.ld_u + ch);
+        else
+            v = *reinterpret_cast<const uint4*>(a.x + ((long long)(n * a.Hi + hi) * a.Wi + wi) * a.ld_x + (ch - (a.u != nullptr ? a.Cu : 0)));
+    };
+    auto gload = [&](int it) {
+        // position `row` of the x tile (its window origin in dh, dw) or of the dy tile (0, 0) -> image n, pixel (h, w).
+        // Row tiles: iteration `it` is tile (hb, wb) of image n0, COLS positions per tile row.  FLAT: image it * R + g, which
+        // may lie past the batch, PER positions per image in rows of W + 2.
+        int n0 = 0, h0 = 0, w0 = 0;
+        if constexpr (!FLAT) {
+            n0 = it / (a.HB * a.WB);
+            const int rem = it - n0 * (a.HB * a.WB);
+            const int hb = rem / a.WB, wb = rem - hb * a.WB;
+            h0 = hb * R, w0 = wb * WT;
         }
-        const int n = it / (a.HB * a.WB);
-        const int rem = it - n * (a.HB * a.WB);
-        const int hb = rem / a.WB, wb = rem - hb * a.WB;
-        const int h0 = hb * R, w0 = wb * WT;
+        auto pixel = [&](int row, auto halo, int dh, int dw, int& n, int& h, int& w) {
+            if constexpr (FLAT) {
+                constexpr int PER = decltype(halo)::value ? TL::XT : TL::PD;
+                const int g = row / PER, q = row - g * PER;
+                n = it * R + g;
+                h = q / TL::W2 + dh, w = q % TL::W2 + dw;
+            } else {
+                constexpr int COLS = decltype(halo)::value ? XC : WT;
+                const int r = row / COLS, col = row - r * COLS;
+                n = n0;
+                h = h0 + dh + r, w = w0 + dw + col;
+            }
+        };
 #pragma unroll
         for (int u = 0; u < XPT; ++u) {
-            const int c = tid + u * 256;                       // chunk -> (pixel of the x tile, 8-channel chunk)
-            const int pix = c / (BCI / 8), cc = c - pix * (BCI / 8);
-            const int xr = pix / XC, xc = pix - xr * XC;
-            const int hi = h0 + a.dhmin + xr, wi = w0 + a.dwmin + xc;
+            const int c = tid + u * 256;                       // chunk -> (position in the x tile, 8-channel chunk)
+            const int row = c / (BCI / 8), cc = c - row * (BCI / 8);
+            int n, hi, wi;
+            pixel(row, std::true_type{}, a.dhmin, a.dwmin, n, hi, wi);
             const int ch = ci0 + cc * 8;
             uint4 v = make_uint4(0, 0, 0, 0);
-            if (c < XCH && ch < a.Ci && (unsigned)hi < (unsigned)a.Hi && (unsigned)wi < (unsigned)a.Wi) {
-                if (a.u != nullptr && ch < a.Cu)
-                    v = *reinterpret_cast<const uint4*>(a.u + ((long long)(n * (a.Hi >> 1) + (hi >> 1)) * (a.Wi >> 1) + (wi >> 1)) * a.ld_u + ch);
-                else
-                    v = *reinterpret_cast<const uint4*>(a.x + ((long long)(n * a.Hi + hi) * a.Wi + wi) * a.ld_x + (ch - (a.u != nullptr ? a.Cu : 0)));
-            }
+            if (c < XCH && (!FLAT || n < a.N) && ch < a.Ci && (unsigned)hi < (unsigned)a.Hi && (unsigned)wi < (unsigned)a.Wi)
+                x_chunk(n, hi, wi, ch, v);
             rx[u] = v;
         }
 #pragma unroll
         for (int u = 0; u < YPT; ++u) {
             const int c = tid + u * 256;
-            const int pix = c / (BCO / 8), cc = c - pix * (BCO / 8);
-            const int yr = pix / WT, yc = pix - yr * WT;
-            const int ho = h0 + yr, wo = w0 + yc;
+            const int row = c / (BCO / 8), cc = c - row * (BCO / 8);
+            int n, ho, wo;
+            pixel(row, std::false_type{}, 0, 0, n, ho, wo);
             const int ch = co0 + cc * 8;
             uint4 v = make_uint4(0, 0, 0, 0);
-            if (c < YCH && ch < a.Co && ho < a.H && wo < a.W) {
+            if (c < YCH && (!FLAT || n < a.N) && ch < a.Co && ho < a.H && wo < a.W) {
                 if constexpr (BNA) {
                     // dy = BatchNorm-backward apply of (g, y), bit for bit what bn_bwd_apply_kernel (direct form) would have
                     // stored -- its two expressions, bn_expr.h: round(g act'(z)), then round(a (. - c1 - yhat c2)); the
@@ -437,33 +393,24 @@ __global__ __launch_bounds__((wg_specialised<BCO, BCI, R, WT, FLAT>() ? 512 : 25
             ry[u] = v;
         }
     };
-    auto gload = [&](int it) { gload_to(it, rx, ry); };
-    // paced: (double-buffered fetch waves) a pause after every store, so that the tile trickles into the other buffer under the
-    // matrix waves' slab loop instead of arriving as one burst their fragment reads queue behind
-    auto lstore_from = [&](int bo, auto paced, const auto& rx, const auto& ry) {
-        constexpr bool PACED = decltype(paced)::value;
+    auto lstore = [&]() {
 #pragma unroll
         for (int u = 0; u < XPT; ++u) {
             const int c = tid + u * 256;
             if (c < XCH) {
                 const int pix = c / (BCI / 8), cc = c - pix * (BCI / 8);
-                *reinterpret_cast<uint4*>(sX + bo + pix * SX + cc * 16) = rx[u];
+                *reinterpret_cast<uint4*>(sX + pix * SX + cc * 16) = rx[u];
             }
-            if constexpr (PACED && SEGNB_WG_PACE > 0) __builtin_amdgcn_s_sleep(SEGNB_WG_PACE);
         }
 #pragma unroll
         for (int u = 0; u < YPT; ++u) {
             const int c = tid + u * 256;
             if (c < YCH) {
                 const int pix = c / (BCO / 8), cc = c - pix * (BCO / 8);
-                *reinterpret_cast<uint4*>(sY + bo + pix * SY + cc * 16) = ry[u];
+                *reinterpret_cast<uint4*>(sY + pix * SY + cc * 16) = ry[u];
             }
-            if constexpr (PACED && SEGNB_WG_PACE > 0) __builtin_amdgcn_s_sleep(SEGNB_WG_PACE);
         }
     };
-    auto lstore = [&](int bo, auto paced) { lstore_from(bo, paced, rx, ry); };
-    constexpr std::false_type burst{};
-    constexpr std::true_type paced{};
 
     // fragment addressing: 16-lane group g reads 4 pixel rows x 16 channels; lane 4q+p supplies the address of
     // pixel row q, channels 4p..4p+3 and receives channel (l&15) of the 4 rows (probe: tools/probe_tr.hip)
@@ -480,35 +427,15 @@ __global__ __launch_bounds__((wg_specialised<BCO, BCI, R, WT, FLAT>() ? 512 : 25
 
     if constexpr (TS) {
         if (fetcher) {
-            // fetch waves: tile it+1 -> registers -> the buffer the matrix waves are not reading; same barrier sequence
+            // fetch waves: tile it+1 -> registers while the matrix waves run tile it, then into the buffer; same barrier sequence
             gload(it_begin);
-            lstore(0, burst);
-            if constexpr (DB) {
-                // tiles it+1 (set A) and it+2 (set B) in flight; each iteration stores the older set into the buffer the matrix
-                // waves are not reading and re-issues that set two tiles ahead: a tile has two slab loops to land
-                if (it_begin + 1 < it_end) gload_to(it_begin + 1, rx, ry);
-                if (it_begin + 2 < it_end) gload_to(it_begin + 2, rx2, ry2);
-                __syncthreads();
-                int cur = 0;
-                for (int it = it_begin; it < it_end; it += 2) {
-                    if (it + 1 < it_end) lstore_from((cur ^ 1) * BUF, paced, rx, ry);
-                    if (it + 3 < it_end) gload_to(it + 3, rx, ry);
-                    __syncthreads();
-                    if (it + 1 >= it_end) break;
-                    if (it + 2 < it_end) lstore_from(cur * BUF, paced, rx2, ry2);
-                    if (it + 4 < it_end) gload_to(it + 4, rx2, ry2);
-                    __syncthreads();
-                }
-                return;
-            }
+            lstore();
             __syncthreads();
             for (int it = it_begin; it < it_end; ++it) {
-#if !(SEGNB_WG_EXP & 1)
                 if (it + 1 < it_end) gload(it + 1);
-#endif
                 __syncthreads();                    // the matrix waves are done with this tile
                 if (it + 1 < it_end) {
-                    lstore(0, burst);
+                    lstore();
                     __syncthreads();
                 }
             }
@@ -534,7 +461,7 @@ __global__ __launch_bounds__((wg_specialised<BCO, BCI, R, WT, FLAT>() ? 512 : 25
 
     if constexpr (!TS) {
         gload(it_begin);
-        lstore(0, burst);
+        lstore();
     }
     __syncthreads();
     constexpr int SPW = NSLAB / KSPLIT;        // slabs per wave and iteration
@@ -550,69 +477,26 @@ __global__ __launch_bounds__((wg_specialised<BCO, BCI, R, WT, FLAT>() ? 512 : 25
     // accumulators stay in their AGPRs across it
     auto pixel_loop = [&](auto Gc) {
         constexpr int G = decltype(Gc)::value;
-        if constexpr (DB) {
-            int cur = 0;
-            for (int it = it_begin; it < it_end; ++it) {
-                const bool more = it + 1 < it_end;
-                if constexpr (!TS) {
-                    if (more) gload(it + 1);
-                }
-                const unsigned bo = (unsigned)(cur * BUF);
-                const unsigned vac = va + bo;
-                auto mid = [&]() {
-                    if constexpr (!TS) {
-                        if (more) lstore((cur ^ 1) * BUF, burst);
-                    }
-                };
-#if SEGNB_WG_EXP & 2
-                mid();
-                if (false) {
-#else
-                if constexpr (TS) {
-#endif
-                    unsigned vtc[5];
+        for (int it = it_begin; it < it_end; ++it) {
+            if constexpr (!TS) {
+                if (it + 1 < it_end) gload(it + 1);
+            }
+            if constexpr (TS) {
+                unsigned vtc[5];
 #pragma unroll
-                    for (int b = 0; b < 5; ++b) vtc[b] = vb[4 * G + b] + bo;
-                    ts_iteration<G, SPW, SEGS, TL::YSTEP, TL::XSTEP, SX, SY, (SPW + 1) / 2>(acc, vac, vtc, mid);
-                } else if constexpr (!(SEGNB_WG_EXP & 2)) {
-                    unsigned vbc[9];
-#pragma unroll
-                    for (int t = 0; t < 9; ++t) vbc[t] = vb[t] + bo;
-                    bf16x4_t fa[2][2], fb[2][9][2];
-                    SEGNB_TR_READ2(fa[0][0], fa[0][1], vac, 0, 4 * SY);          // prologue: slab 0 -> fragment set 0
-                    wg_first<0, SX>(fb[0], vbc);
-                    wg_slabs<0, SPW, KSPLIT, SEGS, TL::YSTEP, TL::XSTEP, SX, SY, (SPW + 1) / 2>(acc, fa, fb, vac, vbc,
-                                                                                                mid);
-                }
-                __syncthreads();                // this buffer read by everyone, the other one written by everyone
-                cur ^= 1;
+                for (int b = 0; b < 5; ++b) vtc[b] = vb[4 * G + b];
+                ts_iteration<G, SPW, SEGS, TL::YSTEP, TL::XSTEP, SX, SY>(acc, va, vtc);
+            } else {
+                bf16x4_t fa[2][2], fb[2][9][2];
+                SEGNB_TR_READ2(fa[0][0], fa[0][1], va, 0, 4 * SY);          // prologue: slab 0 -> fragment set 0
+                wg_first<0, SX>(fb[0], vb);
+                wg_slabs<0, SPW, KSPLIT, SEGS, TL::YSTEP, TL::XSTEP, SX, SY>(acc, fa, fb, va, vb);
             }
             asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::);      // last MFMA results land before anyone reads the accumulators
-        } else {
-            auto mid = [] {};
-            for (int it = it_begin; it < it_end; ++it) {
-                if constexpr (!TS) {
-                    if (it + 1 < it_end) gload(it + 1);
-                }
-                if constexpr (TS) {
-#if !(SEGNB_WG_EXP & 2)
-                    unsigned vtc[5];
-#pragma unroll
-                    for (int b = 0; b < 5; ++b) vtc[b] = vb[4 * G + b];
-                    ts_iteration<G, SPW, SEGS, TL::YSTEP, TL::XSTEP, SX, SY, -1>(acc, va, vtc, mid);
-#endif
-                } else {
-                    bf16x4_t fa[2][2], fb[2][9][2];
-                    SEGNB_TR_READ2(fa[0][0], fa[0][1], va, 0, 4 * SY);          // prologue: slab 0 -> fragment set 0
-                    wg_first<0, SX>(fb[0], vb);
-                    wg_slabs<0, SPW, KSPLIT, SEGS, TL::YSTEP, TL::XSTEP, SX, SY, -1>(acc, fa, fb, va, vb, mid);
-                }
-                asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::);      // last MFMA results land before anyone reads the accumulators
-                __syncthreads();                    // everyone done reading this iteration's tiles
-                if (it + 1 < it_end) {
-                    if constexpr (!TS) lstore(0, burst);
-                    __syncthreads();
-                }
+            __syncthreads();                    // everyone done reading this iteration's tiles
+            if (it + 1 < it_end) {
+                if constexpr (!TS) lstore();
+                __syncthreads();
             }
         }
     };
@@ -645,17 +529,6 @@ __global__ __launch_bounds__((wg_specialised<BCO, BCI, R, WT, FLAT>() ? 512 : 25
             for (int e = 0; e < 16; ++e) acc[t][e] += sAcc[(t * 16 + e) * 64 + lane];
     }
     const int ci = ci0 + sci * 32 + (lane & 31);
-#if SEGNB_WG_EXP & 4
-    {
-        float sum = 0.f;
-#pragma unroll
-        for (int u = 0; u < 9; ++u)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) sum += acc[u][e];
-        if (sum == 12345.f) slab[0] = sum;
-        return;
-    }
-#endif
     if (a.gw != nullptr) {
         // one slab (no pixel split): this block holds the FINAL sums of its tile -- they leave in the parameter's own layout
         // [Co][Ci][3][3], no workspace, no unpack pass.
@@ -673,8 +546,6 @@ __global__ __launch_bounds__((wg_specialised<BCO, BCI, R, WT, FLAT>() ? 512 : 25
             const int nrow4 = vec ? civ * 9 / 4 : 0;
 #pragma unroll
             for (int rd = 0; rd < 4; ++rd) {
-                constexpr int dummy = 0;
-                (void)dummy;
                 const int c = rd >> 1, r = rd & 1;
                 if (rd > 0) __syncthreads();                     // the previous round has been copied out
 #pragma unroll
@@ -984,7 +855,7 @@ __global__ __launch_bounds__(256) void slab_reduce_few_kernel(float4* __restrict
 // (224x224 / 112x112, HBM-bound) keep all CUs (1 -> 5.56, 0.5 -> 5.60, 0.25 -> 5.72 with the wide ones at 0.5).
 // SEGNB_WG_CU_FRACTION overrides the wide share (read once); the thin (HBM-bound) launches keep all CUs, the flattened 7x7 /
 // 14x14 tiles take the wide share (0.25 .. 1 measured within +-0.5 %).
-int s1_slabs(int tiles, bool thin, bool flat = false) {
+int s1_slabs(int tiles, bool thin) {
     static const double frac_wide = [] {
         const char* e = getenv("SEGNB_WG_CU_FRACTION");
         const double r = e ? atof(e) : 0.5;
@@ -995,90 +866,106 @@ int s1_slabs(int tiles, bool thin, bool flat = false) {
         const double r = e ? atof(e) : 1.0;
         return r <= 0.0 ? 1.0 : r;
     }();
-    constexpr double frac_flat = -1.0;
     const int pct = segnb_knob_wg_cu_pct();
     const double wide = pct > 0 ? pct / 100.0 : frac_wide;
-    const double frac = thin ? frac_thin : ((flat && frac_flat > 0.0) ? frac_flat : wide);
-    int S = (int)(segnb_num_cus() * frac) / tiles;
+    int S = (int)(segnb_num_cus() * (thin ? frac_thin : wide)) / tiles;
     return S < 1 ? 1 : S;
 }
 
-template <int BCO, int BCI, int R, int WT, bool FLAT = false, bool BNA = false>
-int launch_s1(WgS1Args& a, int nslab, hipStream_t stream, bool partial, const segnb_wgrad_target* tgt = nullptr) {
-    using TL = WgTile<R, WT, FLAT>;
-    constexpr int tile_bytes = TL::XROWS * lds_stride(BCI) + TL::YROWS * lds_stride(BCO);
-    constexpr int smem = wg_ws_db<BCO, BCI, R, WT, FLAT>() ? 2 * tile_bytes : tile_bytes;
-    static_assert(smem <= 160 * 1024, "tiles fit the LDS");
-    static const int attr_rc = segnb_opt_in_lds("wgrad_s1", smem, conv_wgrad_s1x9_kernel<BCO, BCI, R, WT, FLAT, BNA>);
-    if (attr_rc) return attr_rc;
-    a.HB = (a.H + R - 1) / R;
-    a.WB = (a.W + WT - 1) / WT;
-    a.IT = FLAT ? (a.N + R - 1) / R : a.N * a.HB * a.WB;         // FLAT: R whole images per iteration
-    const int ncot = (a.Co + BCO - 1) / BCO;
-    a.TCI_TILES = (a.Ci + BCI - 1) / BCI;
-    const int tiles = ncot * a.TCI_TILES;
-    const int S = s1_slabs(tiles, BCO == 32, FLAT);
+// (co, ci) tiles of a layer = blocks per pixel split
+int wg_tiles(int Co, int Ci, int bco, int bci) { return ((Co + bco - 1) / bco) * ((Ci + bci - 1) / bci); }
+
+// What launch_s1 and launch_sx share once the tile shape has fixed a.IT and the tile count: the workspace's slab count is checked
+// against the geometry's, the iterations are split over the slabs, `launch(S)` starts the tile kernel and -- unless the caller
+// sums the slabs itself (partial) -- slab 0 += slabs 1 .. S-1.  (Not segnb_slab_reduce: its deep kernel sums in another order.)
+template <typename Args, typename Launch>
+int wg_split_launch(Args& a, int tiles, bool thin, int nslab, hipStream_t stream, bool partial, Launch launch) {
+    const int S = s1_slabs(tiles, thin);
     if (S != nslab) {
-        segnb_set_error("segnb_conv_wgrad: workspace has %d slabs, this geometry needs %d (segnb_conv_wgrad_slabs)",
-                        nslab, S);
+        segnb_set_error("segnb_conv_wgrad: workspace has %d slabs, this geometry needs %d (segnb_conv_wgrad_slabs)", nslab, S);
         return SEGNB_E_BADARG;
     }
     a.its_per_split = (a.IT + S - 1) / S;
     a.slab_stride = (long long)a.Co * a.Ktot;
-    a.gw = nullptr;
-    if (tgt != nullptr && S == 1) {
-        a.gw = tgt->gw;
-        a.gw_s_out = tgt->s_out;
-        a.gw_s_in = tgt->s_in; a.gw_ci_off = tgt->ci_off; a.gw_Ci = tgt->Ci; a.gw_Co = tgt->Co; a.gw_acc = tgt->accumulate;
-        for (int t = 0; t < 9; ++t) a.gw_kpos[t] = tgt->kpos[t];
-    }
-    hipLaunchKernelGGL((conv_wgrad_s1x9_kernel<BCO, BCI, R, WT, FLAT, BNA>), dim3(tiles * S),
-                       dim3(wg_specialised<BCO, BCI, R, WT, FLAT>() ? 512 : 256), smem, stream, a);
+    launch(S);
     if (S > 1 && !partial) {
         const long long total = a.slab_stride;
         if (S <= 16 && total % 4 == 0)
             hipLaunchKernelGGL(slab_reduce_few_kernel, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, stream,
                                reinterpret_cast<float4*>(a.dwp), total / 4, S);
         else
-            hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((total + 63) / 64)), dim3(256), 0, stream, a.dwp,
-                               total, S);
+            hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((total + 63) / 64)), dim3(256), 0, stream, a.dwp, total, S);
     }
     return 0;
 }
 
-// tile configuration of the fast path for a geometry: 0 = not handled here (general kernel, one slab)
-struct S1Choice {
-    int cfg;        // 1: 32x32 R8 WT32, 2: 64x64 R4 WT32, 3: 64x64 R8 WT16, 4: flat 7x7 x4 images, 5: flat 14x14,
-                    // 6: 32x32 R16 WT32 (halo rows 18/16 instead of 10/8 of the HBM-bound thin layers)
+template <int BCO, int BCI, int R, int WT, bool FLAT = false, bool BNA = false>
+int launch_s1(WgS1Args& a, int nslab, hipStream_t stream, bool partial, const segnb_wgrad_target* tgt) {
+    using TL = WgTile<R, WT, FLAT>;
+    constexpr int smem = TL::XROWS * lds_stride(BCI) + TL::YROWS * lds_stride(BCO);
+    static_assert(smem <= 160 * 1024, "tiles fit the LDS");
+    static const int attr_rc = segnb_opt_in_lds("wgrad_s1", smem, conv_wgrad_s1x9_kernel<BCO, BCI, R, WT, FLAT, BNA>);
+    if (attr_rc) return attr_rc;
+    a.HB = (a.H + R - 1) / R;
+    a.WB = (a.W + WT - 1) / WT;
+    a.IT = FLAT ? (a.N + R - 1) / R : a.N * a.HB * a.WB;         // FLAT: R whole images per iteration
+    a.TCI_TILES = (a.Ci + BCI - 1) / BCI;
+    const int tiles = wg_tiles(a.Co, a.Ci, BCO, BCI);
+    return wg_split_launch(a, tiles, BCO == 32, nslab, stream, partial, [&](int S) {
+        a.gw = nullptr;
+        if (tgt != nullptr && S == 1) {
+            a.gw = tgt->gw;
+            a.gw_s_out = tgt->s_out;
+            a.gw_s_in = tgt->s_in; a.gw_ci_off = tgt->ci_off; a.gw_Ci = tgt->Ci; a.gw_Co = tgt->Co; a.gw_acc = tgt->accumulate;
+            for (int t = 0; t < 9; ++t) a.gw_kpos[t] = tgt->kpos[t];
+        }
+        hipLaunchKernelGGL((conv_wgrad_s1x9_kernel<BCO, BCI, R, WT, FLAT, BNA>), dim3(tiles * S),
+                           dim3(wg_specialised(BCO, BCI) ? 512 : 256), smem, stream, a);
+    });
+}
+
+// The tile configurations of conv_wgrad_s1x9_kernel, one row per instantiation.  Thin rows (32 x 32 tiles: a layer with at most
+// 32 channels on one side) also come with dy recomputed from the BatchNorm-backward operands (BNA).
+using S1Launch = int (*)(WgS1Args&, int, hipStream_t, bool, const segnb_wgrad_target*);
+struct S1Config {
     int bco, bci;
+    bool flat;              // whole 7 x 7 / 14 x 14 images in the padded-row flattening
+    S1Launch launch;
+    S1Launch launch_bna;    // null: no BNA form
 };
-S1Choice s1_choose(const segnb_conv_geom* g) {
-    S1Choice c = {0, 0, 0};
-    if (!whole_output_3x3_s1(g)) return c;
-    const bool thin = g->Co <= 32 || g->Ci <= 32;
-    if (thin) {
-        if (g->Wo < 24) return c;
-        c = {(g->Ho % 16 == 0 && g->Ho >= 64 && SEGNB_WG_TALL) ? 6 : 1, 32, 32};
-    } else if (g->Wo > 16) {
+enum S1Row { S1_THIN_R8, S1_THIN_R16, S1_R4, S1_R8, S1_R7, S1_W16, S1_FLAT7, S1_FLAT14 };
+const S1Config S1_TABLE[] = {
+    /* S1_THIN_R8  */ {32, 32, false, launch_s1<32, 32, 8, 32>, launch_s1<32, 32, 8, 32, false, true>},
+    /* S1_THIN_R16 */ {32, 32, false, launch_s1<32, 32, 16, 32>, launch_s1<32, 32, 16, 32, false, true>},
+    /* S1_R4       */ {64, 64, false, launch_s1<64, 64, 4, 32>, nullptr},
+    /* S1_R8       */ {64, 64, false, launch_s1<64, 64, 8, 32>, nullptr},
+    /* S1_R7       */ {64, 64, false, launch_s1<64, 64, 7, 32>, nullptr},
+    /* S1_W16      */ {64, 64, false, launch_s1<64, 64, 8, 16>, nullptr},
+    /* S1_FLAT7    */ {64, 64, true, launch_s1<64, 64, 4, 7, true>, nullptr},          // four images per iteration
+    /* S1_FLAT14   */ {64, 64, true, launch_s1<64, 64, 1, 14, true>, nullptr},
+};
+
+// tile configuration of the fast path for a geometry; null: not served here (general kernel, one slab)
+const S1Config* s1_choose(const segnb_conv_geom* g) {
+    if (!whole_output_3x3_s1(g)) return nullptr;
+    if (g->Co <= 32 || g->Ci <= 32) {
+        if (g->Wo < 24) return nullptr;
+        // 16-row tiles where they divide a tall image: halo rows 18/16 instead of 10/8 for these HBM-bound layers
+        return &S1_TABLE[g->Ho % 16 == 0 && g->Ho >= 64 ? S1_THIN_R16 : S1_THIN_R8];
+    }
+    if (g->Wo > 16) {
+        // 16-column tiles where they cover the width exactly and 32-column tiles do not (112 = 7 x 16 against 4 x 32: an
+        // eighth of the slabs were padding)
+        if (g->Wo % 16 == 0 && g->Wo % 32 != 0) return &S1_TABLE[S1_W16];
         // rows per iteration: 8, or 7, where they divide the image height (x tile 10 rows for 8, 9 for 7; half as many tile
         // hand-overs per pixel), else 4 (6 for 4).  Measured alone over the 14 such layers of the timed configuration: 1788 ->
-        // 1667 us; in situ -0.6 % step time.  SEGNB_WG_ROWS=4 restores the short tiles.
-        constexpr int rows = 8;
-        // 16-column tiles where they cover the width exactly and 32-column tiles do not (112 = 7 x 16 against 4 x 32: an
-        // eighth of the slabs were padding); SEGNB_WG_W16=0: off
-        constexpr bool w16 = true;
-        if (w16 && g->Wo % 16 == 0 && g->Wo % 32 != 0)
-            c = {3, 64, 64};
-        else
-            c = {(rows == 8 && g->Ho % 8 == 0) ? 7 : ((rows >= 7 && g->Ho % 7 == 0) ? 8 : 2), 64, 64};
-    } else if (g->Wo == 14 && g->Ho == 14) {
-        c = {5, 64, 64};
-    } else if (g->Wo >= 12) {
-        c = {3, 64, 64};
-    } else if (g->Wo == 7 && g->Ho == 7) {
-        c = {4, 64, 64};
+        // 1667 us; in situ -0.6 % step time.
+        return &S1_TABLE[g->Ho % 8 == 0 ? S1_R8 : (g->Ho % 7 == 0 ? S1_R7 : S1_R4)];
     }
-    return c;
+    if (g->Wo == 14 && g->Ho == 14) return &S1_TABLE[S1_FLAT14];
+    if (g->Wo >= 12) return &S1_TABLE[S1_W16];
+    if (g->Wo == 7 && g->Ho == 7) return &S1_TABLE[S1_FLAT7];
+    return nullptr;
 }
 
 
@@ -1263,41 +1150,6 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_sx_kernel(const WgSxArgs a)
     }
 }
 
-struct SxChoice {
-    int cfg;        // 0: not served.  1: 7x7 window stride 2, 8 channels (stem); 2: 3x3 stride 2, 32-channel tiles, 32 columns;
-                    // 3: the same on 16-column tiles (outputs narrower than 32); 9 / 10: 4x4 stride 2 likewise; 4..7: 1x1 stride 1 (a plain dy^T x GEMM: the
-                    // pixels of the whole batch as ONE row of 256-pixel tiles) with 16 / 32 / 64 / 128 input channels per block
-    int bci;        // 8: 2x2 window stride 1, at most 32 output channels (LinkNet34's finalconv3, linknet.py:45)
-    int bco = 64;
-};
-SxChoice sx_choose(const segnb_conv_geom* g) {
-    SxChoice c = {0, 0, 64};
-    static const bool off = getenv("SEGNB_WGRAD_SX") != nullptr && getenv("SEGNB_WGRAD_SX")[0] == '0';
-    if (off || !whole_output(g)) return c;
-    if (g->in_step == 1 && g->ntaps == 1 && g->dh[0] == 0 && g->dw[0] == 0 && g->Hi == g->Ho && g->Wi == g->Wo &&
-        g->Ho * g->Wo >= 256) {                      // (per image: the choice may not depend on the batch size)
-        if (g->Ci <= 16) c = {4, 16};
-        else if (g->Ci <= 32) c = {5, 32};
-        else if (g->Ci < 96) c = {6, 64};
-        else c = {7, 128};
-        return c;
-    }
-    const segnb_tap_win win = segnb_tap_window(g);
-    const int kh = win.kh, kw = win.kw;
-    if (g->in_step == 1) {
-        if (g->ntaps == 4 && kh == 2 && kw == 2 && g->Ci % 32 == 0 && g->Co <= 32 && g->Wo >= 24) c = {8, 32, 32};
-        return c;
-    }
-    if (g->in_step != 2) return c;
-    if (g->ntaps != kh * kw) return c;
-    if (kh == 7 && kw == 7 && g->Ci == 8 && g->Wo >= 32) c = {1, 8};
-    else if (kh == 3 && kw == 3 && g->Ci % 32 == 0 && g->Wo >= 24) c = {2, 32};
-    else if (kh == 3 && kw == 3 && g->Ci % 32 == 0 && g->Wo >= 12) c = {3, 32};
-    else if (kh == 4 && kw == 4 && g->Ci % 32 == 0 && g->Wo >= 24) c = {9, 32};        // (UNet16's ConvTranspose2d(4, 2, 1), unet16.py:30)
-    else if (kh == 4 && kw == 4 && g->Ci % 32 == 0 && g->Wo >= 12) c = {10, 32};
-    return c;
-}
-
 template <int S, int BCI, int R, int WT, int KH, int KW, int BCO = 64>
 int launch_sx(WgSxArgs& a, int nslab, hipStream_t stream, bool partial) {
     constexpr int XR = (R - 1) * S + KH, XC = (WT - 1) * S + KW;
@@ -1309,25 +1161,54 @@ int launch_sx(WgSxArgs& a, int nslab, hipStream_t stream, bool partial) {
     a.WB = (a.W + WT - 1) / WT;
     a.IT = a.N * a.HB * a.WB;
     a.TCI_TILES = (a.Ci + BCI - 1) / BCI;
-    const int tiles = ((a.Co + BCO - 1) / BCO) * a.TCI_TILES;
-    const int S_ = s1_slabs(tiles, true);
-    if (S_ != nslab) {
-        segnb_set_error("segnb_conv_wgrad: workspace has %d slabs, this geometry needs %d (segnb_conv_wgrad_slabs)", nslab, S_);
-        return SEGNB_E_BADARG;
-    }
-    a.its_per_split = (a.IT + S_ - 1) / S_;
-    a.slab_stride = (long long)a.Co * a.Ktot;
-    hipLaunchKernelGGL((conv_wgrad_sx_kernel<S, BCI, R, WT, KH, KW, BCO>), dim3(tiles * S_), dim3(256), smem, stream, a);
-    if (S_ > 1 && !partial) {
-        const long long total = a.slab_stride;
-        if (S_ <= 16 && total % 4 == 0)
-            hipLaunchKernelGGL(slab_reduce_few_kernel, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, stream,
-                               reinterpret_cast<float4*>(a.dwp), total / 4, S_);
-        else
-            hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((total + 63) / 64)), dim3(256), 0, stream, a.dwp, total, S_);
-    }
-    return 0;
+    const int tiles = wg_tiles(a.Co, a.Ci, BCO, BCI);
+    return wg_split_launch(a, tiles, true, nslab, stream, partial, [&](int S_) {
+        hipLaunchKernelGGL((conv_wgrad_sx_kernel<S, BCI, R, WT, KH, KW, BCO>), dim3(tiles * S_), dim3(256), smem, stream, a);
+    });
 }
+
+// The tile configurations of conv_wgrad_sx_kernel, one row per instantiation
+using SxLaunch = int (*)(WgSxArgs&, int, hipStream_t, bool);
+struct SxConfig {
+    int bci, bco;
+    bool batch_row;         // 1x1 stride 1 (a plain dy^T x GEMM, no halo): the pixels of the whole batch as ONE row of 256-pixel tiles
+    SxLaunch launch;
+};
+enum SxRow { SX_7X7S2, SX_3X3S2_W32, SX_3X3S2_W16, SX_4X4S2_W32, SX_4X4S2_W16, SX_1X1_C16, SX_1X1_C32, SX_1X1_C64, SX_1X1_C128,
+             SX_2X2 };
+const SxConfig SX_TABLE[] = {
+    /* SX_7X7S2     */ {8, 64, false, launch_sx<2, 8, 8, 32, 7, 7>},           // the stem: 8 channels
+    /* SX_3X3S2_W32 */ {32, 64, false, launch_sx<2, 32, 4, 32, 3, 3>},
+    /* SX_3X3S2_W16 */ {32, 64, false, launch_sx<2, 32, 8, 16, 3, 3>},         // outputs narrower than 32: 16-column tiles
+    /* SX_4X4S2_W32 */ {32, 64, false, launch_sx<2, 32, 4, 32, 4, 4>},         // (UNet16's ConvTranspose2d(4, 2, 1), unet16.py:30)
+    /* SX_4X4S2_W16 */ {32, 64, false, launch_sx<2, 32, 8, 16, 4, 4>},
+    /* SX_1X1_C16   */ {16, 64, true, launch_sx<1, 16, 1, 256, 1, 1>},
+    /* SX_1X1_C32   */ {32, 64, true, launch_sx<1, 32, 1, 256, 1, 1>},
+    /* SX_1X1_C64   */ {64, 64, true, launch_sx<1, 64, 1, 256, 1, 1>},
+    /* SX_1X1_C128  */ {128, 64, true, launch_sx<1, 128, 1, 256, 1, 1>},
+    /* SX_2X2       */ {32, 32, false, launch_sx<1, 32, 8, 32, 2, 2, 32>},     // stride 1, at most 32 output channels (LinkNet34's
+                                                                               // finalconv3, linknet.py:45)
+};
+
+// null: not served
+const SxConfig* sx_choose(const segnb_conv_geom* g) {
+    static const bool off = getenv("SEGNB_WGRAD_SX") != nullptr && getenv("SEGNB_WGRAD_SX")[0] == '0';
+    if (off || !whole_output(g)) return nullptr;
+    if (g->in_step == 1 && g->ntaps == 1 && g->dh[0] == 0 && g->dw[0] == 0 && g->Hi == g->Ho && g->Wi == g->Wo &&
+        g->Ho * g->Wo >= 256)                        // (per image: the choice may not depend on the batch size)
+        return &SX_TABLE[g->Ci <= 16 ? SX_1X1_C16 : g->Ci <= 32 ? SX_1X1_C32 : g->Ci < 96 ? SX_1X1_C64 : SX_1X1_C128];
+    const segnb_tap_win win = segnb_tap_window(g);
+    const int kh = win.kh, kw = win.kw;
+    if (g->in_step == 1)
+        return g->ntaps == 4 && kh == 2 && kw == 2 && g->Ci % 32 == 0 && g->Co <= 32 && g->Wo >= 24 ? &SX_TABLE[SX_2X2] : nullptr;
+    if (g->in_step != 2 || g->ntaps != kh * kw) return nullptr;
+    if (kh == 7 && kw == 7 && g->Ci == 8 && g->Wo >= 32) return &SX_TABLE[SX_7X7S2];
+    if (g->Ci % 32 != 0 || g->Wo < 12) return nullptr;
+    if (kh == 3 && kw == 3) return &SX_TABLE[g->Wo >= 24 ? SX_3X3S2_W32 : SX_3X3S2_W16];
+    if (kh == 4 && kw == 4) return &SX_TABLE[g->Wo >= 24 ? SX_4X4S2_W32 : SX_4X4S2_W16];
+    return nullptr;
+}
+
 
 }  // namespace
 
@@ -1372,9 +1253,8 @@ void segnb_wgrad_to_param(float* dwp, int Cop, int ntaps, int Cip, int nslab, co
 
 // partial slabs segnb_conv_wgrad writes for this geometry on the fast path (0: not a fast-path geometry)
 int segnb_wgrad_s1_slabs(const segnb_conv_geom* g) {
-    const S1Choice c = s1_choose(g);
-    if (!c.cfg) return 0;
-    return s1_slabs(((g->Co + c.bco - 1) / c.bco) * ((g->Ci + c.bci - 1) / c.bci), c.bco == 32, c.cfg == 4 || c.cfg == 5);
+    const S1Config* c = s1_choose(g);
+    return c != nullptr ? s1_slabs(wg_tiles(g->Co, g->Ci, c->bco, c->bci), c->bco == 32) : 0;
 }
 
 // declined when the geometry is not a stride-1 3x3 bf16 case (the caller falls through to the general kernel)
@@ -1382,11 +1262,11 @@ int segnb_wgrad_s1_try(segnb_try_outcome* did, const segnb_conv_geom* g, const v
                        hipStream_t stream, bool partial, const segnb_wgrad_bnapply* bna, const segnb_upcat_src* uc,
                        const segnb_wgrad_target* tgt) {
     *did = SEGNB_TRY_DECLINED;
-    const S1Choice c = s1_choose(g);
-    if (!c.cfg) return 0;
+    const S1Config* c = s1_choose(g);
+    if (c == nullptr) return 0;
     if (tgt != nullptr) partial = true;           // the slabs are summed by segnb_wgrad_to_param
     if (uc != nullptr && (uc->Cu % 8 != 0 || uc->Cu <= 0 || uc->Cu >= g->Ci || (g->Hi & 1) || (g->Wi & 1))) return 0;
-    if (bna != nullptr && c.cfg != 1 && c.cfg != 6) return 0;      // (thin 32 x 32 tiles only)
+    if (bna != nullptr && c->launch_bna == nullptr) return 0;      // (thin 32 x 32 tiles only)
     const segnb_tap_win win = segnb_tap_window(g);
     WgS1Args a;
     a.x = (const bf16_t*)in;
@@ -1400,21 +1280,8 @@ int segnb_wgrad_s1_try(segnb_try_outcome* did, const segnb_conv_geom* g, const v
     a.u = uc != nullptr ? (const bf16_t*)uc->u : nullptr;
     a.Cu = uc != nullptr ? uc->Cu : 0;
     a.ld_u = uc != nullptr ? uc->ld_u : 0;
-    a.bna = segnb_wgrad_bnapply{};
-    int rc;
-    if (bna != nullptr) {
-        a.bna = *bna;
-        rc = c.cfg == 1 ? launch_s1<32, 32, 8, 32, false, true>(a, nslab, stream, partial, tgt)
-                        : launch_s1<32, 32, 16, 32, false, true>(a, nslab, stream, partial, tgt);
-    } else if (c.cfg == 1) rc = launch_s1<32, 32, 8, 32>(a, nslab, stream, partial, tgt);
-    else if (c.cfg == 6) rc = launch_s1<32, 32, 16, 32>(a, nslab, stream, partial, tgt);
-    else if (c.cfg == 2) rc = launch_s1<64, 64, 4, 32>(a, nslab, stream, partial, tgt);
-    else if (c.cfg == 7) rc = launch_s1<64, 64, 8, 32>(a, nslab, stream, partial, tgt);
-    else if (c.cfg == 8) rc = launch_s1<64, 64, 7, 32>(a, nslab, stream, partial, tgt);
-    else if (c.cfg == 3) rc = launch_s1<64, 64, 8, 16>(a, nslab, stream, partial, tgt);
-    else if (c.cfg == 4) rc = launch_s1<64, 64, 4, 7, true>(a, nslab, stream, partial, tgt);
-    else rc = launch_s1<64, 64, 1, 14, true>(a, nslab, stream, partial, tgt);
-    if (rc) return rc;
+    a.bna = bna != nullptr ? *bna : segnb_wgrad_bnapply{};
+    if (int rc = (bna != nullptr ? c->launch_bna : c->launch)(a, nslab, stream, partial, tgt)) return rc;
     // (launch_s1 checked nslab against the geometry's slab count: a single-slab launch writes the target from its accumulators)
     *did = tgt != nullptr && nslab == 1 ? SEGNB_TRY_DELIVERED : SEGNB_TRY_LAUNCHED;
     return 0;
@@ -1423,16 +1290,15 @@ int segnb_wgrad_s1_try(segnb_try_outcome* did, const segnb_conv_geom* g, const v
 
 // the strided / wide-window tile kernel (conv_wgrad_sx_kernel): slabs it writes (0: geometry not served) and the launch
 int segnb_wgrad_sx_slabs(const segnb_conv_geom* g) {
-    const SxChoice c = sx_choose(g);
-    if (!c.cfg) return 0;
-    return s1_slabs(((g->Co + c.bco - 1) / c.bco) * ((g->Ci + c.bci - 1) / c.bci), true);
+    const SxConfig* c = sx_choose(g);
+    return c != nullptr ? s1_slabs(wg_tiles(g->Co, g->Ci, c->bco, c->bci), true) : 0;
 }
 
 int segnb_wgrad_sx_try(segnb_try_outcome* did, const segnb_conv_geom* g, const void* in, const void* dout, float* dwp, int nslab,
                        hipStream_t stream, bool partial) {
     *did = SEGNB_TRY_DECLINED;
-    const SxChoice c = sx_choose(g);
-    if (!c.cfg) return 0;
+    const SxConfig* c = sx_choose(g);
+    if (c == nullptr) return 0;
     const segnb_tap_win win = segnb_tap_window(g);
     WgSxArgs a;
     a.x = (const bf16_t*)in;
@@ -1444,21 +1310,10 @@ int segnb_wgrad_sx_try(segnb_try_outcome* did, const segnb_conv_geom* g, const v
     a.ntaps = g->ntaps;
     segnb_rel_taps(g, win, a.dh, a.dw);
     a.Ktot = g->ntaps * g->Ci;
-    int rc;
-    if (c.cfg >= 4 && c.cfg <= 7) {
-        a.W = a.Wi = g->N * g->Ho * g->Wo;          // 1x1: no halo, the batch is one row of pixels
+    if (c->batch_row) {
+        a.W = a.Wi = g->N * g->Ho * g->Wo;
         a.N = a.H = a.Hi = 1;
-        rc = c.cfg == 4 ? launch_sx<1, 16, 1, 256, 1, 1>(a, nslab, stream, partial)
-           : c.cfg == 5 ? launch_sx<1, 32, 1, 256, 1, 1>(a, nslab, stream, partial)
-           : c.cfg == 6 ? launch_sx<1, 64, 1, 256, 1, 1>(a, nslab, stream, partial)
-                        : launch_sx<1, 128, 1, 256, 1, 1>(a, nslab, stream, partial);
-        return segnb_try_launched(did, rc);
     }
-    if (c.cfg == 8) rc = launch_sx<1, 32, 8, 32, 2, 2, 32>(a, nslab, stream, partial);
-    else if (c.cfg == 1) rc = launch_sx<2, 8, 8, 32, 7, 7>(a, nslab, stream, partial);
-    else if (c.cfg == 2) rc = launch_sx<2, 32, 4, 32, 3, 3>(a, nslab, stream, partial);
-    else if (c.cfg == 9) rc = launch_sx<2, 32, 4, 32, 4, 4>(a, nslab, stream, partial);
-    else if (c.cfg == 10) rc = launch_sx<2, 32, 8, 16, 4, 4>(a, nslab, stream, partial);
-    else rc = launch_sx<2, 32, 8, 16, 3, 3>(a, nslab, stream, partial);
-    return segnb_try_launched(did, rc);
+    return segnb_try_launched(did, c->launch(a, nslab, stream, partial));
 }
+

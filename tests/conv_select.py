@@ -47,6 +47,23 @@ CASES = {
     'thin_48_16': ('bf16', 2, 32, 64, 48, 16, 3, 1, True),
     # fprop_sx.hip segnb_fprop_sx_try: in_step == 2, 8 input channels, QW >= 24 (an input 48 wide)
     'sx_8_32_stride2': ('bf16', 1, 8, 48, 8, 32, 3, 2, True),
+    # wgrad_s1.hip s1_choose: one geometry per row of its configuration table
+    'wg_thin_r8': ('bf16', 2, 24, 32, 64, 32, 3, 1, True),           # Co <= 32, Wo >= 24, Ho % 16 != 0
+    'wg_thin_r16': ('bf16', 1, 64, 32, 64, 32, 3, 1, True),          # Ho % 16 == 0 and Ho >= 64
+    'wg_wide_r4': ('bf16', 2, 20, 40, 64, 64, 3, 1, True),           # Ho divisible by neither 8 nor 7
+    'wg_wide_r8_ragged': ('bf16', 2, 16, 40, 72, 40, 3, 1, True),    # Ho % 8 == 0; ragged channels in both tiles
+    'wg_wide_r7': ('bf16', 2, 14, 40, 64, 64, 3, 1, True),           # Ho % 7 == 0, Wo > 16
+    'wg_w16_wide': ('bf16', 2, 16, 48, 64, 64, 3, 1, True),          # Wo % 16 == 0, Wo % 32 != 0
+    'wg_w16_narrow': ('bf16', 2, 12, 12, 64, 64, 3, 1, True),        # 12 <= Wo <= 16, not 14 x 14
+    'wg_flat14': ('bf16', 2, 14, 14, 64, 64, 3, 1, True),
+    'wg_flat7': ('bf16', 5, 7, 7, 64, 64, 3, 1, True),               # four images per iteration: the last one is ragged
+    # wgrad_s1.hip sx_choose: the rows this format can express (the 4 x 4 stride-2 and 2 x 2 rows: test_strided_wgrad_takes_the_tile_kernel)
+    'wsx_1x1_16': ('bf16', 2, 16, 16, 16, 64, 1, 1, True),
+    'wsx_1x1_32': ('bf16', 2, 16, 16, 32, 64, 1, 1, True),
+    'wsx_1x1_128': ('bf16', 2, 16, 16, 128, 64, 1, 1, True),         # ('wsx_1x1' above is the 64-channel row)
+    'wsx_3x3s2_w32': ('bf16', 2, 48, 48, 32, 64, 3, 2, True),        # Wo = 24
+    'wsx_3x3s2_w16': ('bf16', 2, 24, 24, 32, 64, 3, 2, True),        # Wo = 12
+    'wsx_7x7s2': ('bf16', 2, 64, 64, 8, 64, 7, 2, True),             # the stem, Wo >= 32
 }
 # selectors that no case above reaches, and the gate that keeps them away
 UNREACHED = {}
