@@ -8,7 +8,7 @@ FLAGS="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wall -Wno-unused-function -fn
 mkdir -p obj
 pids=()
 for f in conv_igemm pack fprop_s1 fprop_dma fprop_rw fprop_roll fprop_c8 fprop_sx fprop_thin wgrad_s1 wgrad_roll norm_act elementwise head_loss mc_loss gcn elu tiles runtime; do
-  if [ ! -f obj/$f.o ] || [ $f.hip -nt obj/$f.o ] || [ common.h -nt obj/$f.o ] || [ bn_expr.h -nt obj/$f.o ] || [ device.h -nt obj/$f.o ] || [ ew.h -nt obj/$f.o ] || [ fprop_dma.h -nt obj/$f.o ] || [ tile_div.h -nt obj/$f.o ] || [ ../../include/segnb_hip.h -nt obj/$f.o ] || [ ../../include/segnb_mc_loss.h -nt obj/$f.o ] || [ ../../include/segnb_gcn.h -nt obj/$f.o ] || [ ../../include/segnb_elu.h -nt obj/$f.o ] || [ ../../include/segnb_upsample.h -nt obj/$f.o ]; then
+  if [ ! -f obj/$f.o ] || [ $f.hip -nt obj/$f.o ] || [ common.h -nt obj/$f.o ] || [ bn_expr.h -nt obj/$f.o ] || [ device.h -nt obj/$f.o ] || [ ew.h -nt obj/$f.o ] || [ fprop_dma.h -nt obj/$f.o ] || [ tile_div.h -nt obj/$f.o ] || [ ws_select.h -nt obj/$f.o ] || [ ../../include/segnb_hip.h -nt obj/$f.o ] || [ ../../include/segnb_mc_loss.h -nt obj/$f.o ] || [ ../../include/segnb_gcn.h -nt obj/$f.o ] || [ ../../include/segnb_elu.h -nt obj/$f.o ] || [ ../../include/segnb_upsample.h -nt obj/$f.o ]; then
     $HIPCC $FLAGS -c $f.hip -o obj/$f.o &
     pids+=($!)
   fi

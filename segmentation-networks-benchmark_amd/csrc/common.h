@@ -129,7 +129,6 @@ int segnb_knob_fprop_dma_cfg();
 int segnb_knob_fprop_dma_dbg();
 int segnb_knob_fprop_dma_epi();   // -1 default, 0 / 1: store rows of conv_fprop_ws_kernel on taps chosen at run time / on peeled taps
 int segnb_knob_fprop_nostats();   // 1: launches without statistics run the statistics-free instantiation of conv_fprop_ws_kernel
-int segnb_knob_rw_store_waves();  // 2 or 4 store waves in conv_fprop_rw_kernel
 int segnb_knob_bnreduce_fused();  // 1: segnb_conv_fprop_bnreduce_ok may say yes
 int segnb_knob_fprop_deepk();     // 1: conv_fprop_deepk_kernel serves the shapes it applies to
 int segnb_knob_fprop_thin();      // 1: conv_thin_kernel (fprop_thin.hip) serves <= 16 -> >= 48 channel stride-1 3x3 launches
@@ -209,7 +208,6 @@ int segnb_knob_fprop_drop();      // 1: segnb_conv_fprop_drop_ok may say yes
 int segnb_knob_fprop_mask();      // 1: conv_fprop_ws_kernel serves activation-mask data gradients (segnb_conv_fprop_bnreduce, coef NULL)
 int segnb_fprop_dma_actmask_ok(const segnb_conv_geom* g);
 int segnb_fprop_roll_actmask_ok(const segnb_conv_geom* g);     // fprop_roll.hip: conv_roll_kernel (EPI = 3) serves g      // fprop_dma.hip: the MASK instantiation serves g
-int segnb_knob_fprop_mf16();      // 1: conv_fprop_ws_kernel issues v_mfma_f32_16x16x32_bf16, 0: 32x32x16
 int segnb_knob_fprop_rw();
 int segnb_knob_fprop_ksplit();   // conv_fprop_ws_kernel split K: 0 off, 1 automatic (default), 2 / 4 forced where it applies
 // head backward's per-(device, stream) partial-sum scratch and its fixed-order finish launch (head_loss.hip)

@@ -36,7 +36,9 @@
 
 #include "fprop_dma.h"
 #include "tile_div.h"
+#include "ws_select.h"
 
+#include <array>
 #include <mutex>
 #include <vector>
 
@@ -1304,44 +1306,46 @@ int ksplit_workspace(hipStream_t stream, size_t slab_bytes, int ntiles, float** 
     return 0;
 }
 
-// split K pays where a launch has fewer (pixel tile, channel tile) pairs than half the CUs it may use: the 7 x 7 level of
-// lib/models/zf_unet.py:44-56 (8 tall row tiles x 8..16 channel tiles at bs = 32).  Returns the number of slices (1 = no split)
-template <class C>
-int ksplit_factor(const WsArgs& a, int it_total, int ntl, int nch) {
-    if (!C::TALL || !segnb_knob_fprop_ksplit()) return 1;
-    if (a.ep_act >= 0 || a.dbg || a.up_out != nullptr) return 1;
-    const long long tiles = (long long)it_total * ntl;
-    int cus = segnb_knob_conv_cus();
-    // A data gradient (no statistics) of a two-stream backward runs beside the weight-gradient stream, which sizes its launches
-    // for a share of the CUs (wgrad_s1.hip: s1_slabs): slices beyond the CUs that are left would queue behind their partners
-    // and only add the hand-over
-    // (measured, same box, alternating runs: 4.92 ms per step with half or all of the CUs budgeted for the data gradients)
-    if (a.stats == nullptr) cus /= 2;
-    int ks = 1;
-    if (tiles * 2 <= cus && nch % 2 == 0 && nch / 2 >= 2) ks = 2;
-    if (tiles * 4 <= cus && nch % 4 == 0 && nch / 4 >= 2) ks = 4;
-    const int forced = segnb_knob_fprop_ksplit();
-    if (forced > 1 && nch % forced == 0 && nch / forced >= 2 && (forced == 2 || forced == 4)) ks = forced;
-    if (tiles * ks * 65536ll >= (1ll << 31)) return 1;
-    return ks;
+// ---- the launchers: one table row of ws_select.h = one WsCfg = one launcher ---------------------------------------------------------
+template <int ROW>
+using WsRowCfg = WsCfg<WS_TILES[ROW].BN, WS_TILES[ROW].R, WS_TILES[ROW].WT, WS_TILES[ROW].CW_M, WS_TILES[ROW].TALL, WS_TILES[ROW].MF16,
+                       WS_TILES[ROW].NTAP, WS_TILES[ROW].UP>;
+using WsKernel = void (*)(const WsArgs);
+
+// form of ws_select.h -> instantiation, for a configuration K = C or WsEpi<C>
+template <class K, int FORM>
+WsKernel ws_form_kernel() {
+    if constexpr (FORM == WS_STATS) return conv_fprop_ws_kernel<K, false>;
+    else if constexpr (FORM == WS_NOSTATS) return conv_fprop_ws_kernel<K, false, false, false>;
+    else if constexpr (FORM == WS_MASK) return conv_fprop_ws_kernel<K, false, false, true, false, true>;
+    else if constexpr (FORM == WS_EP) return conv_fprop_ws_kernel<K, false, true, false>;      // (never with statistics: segnb_conv_fprop_act takes none)
+    else if constexpr (FORM == WS_DBG) return conv_fprop_ws_kernel<K, true>;
+    else if constexpr (FORM == WS_KS_STATS) return conv_fprop_ws_kernel<K, false, false, true, true>;
+    else return conv_fprop_ws_kernel<K, false, false, false, true>;
 }
 
-// Which order of the store rows serves a launch (segnb_tune "fprop_dma_epi"): the WsEpi instantiations exist for the 16x16x32
-// configurations of the 3 x 3 window the ZF_UNET step launches without split K -- 14 x 14 and 16 x 16 tiles (statistics, none,
-// activation mask, timing build); everything else (8 x 32 tiles, the 2 x 2-window forms, the tall 7 x 7 form and its split K, the
-// affine epilogue, the 32x32x16 stream) keeps the plain order whatever the knob says.
-// by_default: what the configuration takes at knob -1 (tools/wsepi_bench.py, profiles/wsepi_ab.txt).
-template <class C>
-constexpr bool ws_has_epi() {
-    return C::MF16 && !C::TALL && C::BN == 64 && C::NTAP == 9 && ((C::R == 14 && C::WT == 14) || (C::R == 16 && C::WT == 16));
-}
-bool ws_epi_selected(bool by_default) {
-    const int k = segnb_knob_fprop_dma_epi();
-    const bool on = k < 0 ? by_default : k != 0;
-    if (on && g_segnb_census_on) segnb_census("epi:1");
-    return on;
-}
-constexpr bool WS_EPI_DEFAULT = true;
+// The kernels of a row, [WsEpi][form], NULL where the row has no such form: the forms WS_TILES lists, each opted in to its dynamic
+// LDS (the MASK form: 2 KB of mask bytes behind the layout) when the row is first used -- what can be launched was opted in.
+template <int ROW>
+struct WsRowKernels {
+    using C = WsRowCfg<ROW>;
+    static_assert(C::BM == WS_TILES[ROW].BM && (C::MASK_OK || !((WS_TILES[ROW].forms >> WS_MASK) & 1u)), "WS_TILES restates WsCfg");
+    WsKernel kern[2][WS_NFORMS] = {};
+    int rc = 0;
+    static constexpr int lds(int form) { return C::SMEM + (form == WS_MASK ? 2048 : 0); }
+    template <int F>
+    void take() {
+        if constexpr ((WS_TILES[ROW].forms >> F) & 1u) kern[0][F] = ws_form_kernel<C, F>();
+        if constexpr ((WS_TILES[ROW].epi_forms >> F) & 1u) kern[1][F] = ws_form_kernel<WsEpi<C>, F>();
+    }
+    template <int... F>
+    WsRowKernels(std::integer_sequence<int, F...>) {
+        (take<F>(), ...);
+        for (int i = 0; i < 2 * WS_NFORMS && rc == 0; ++i)
+            if (kern[i / WS_NFORMS][i % WS_NFORMS] != nullptr)
+                rc = segnb_opt_in_lds("fprop_ws", lds(i % WS_NFORMS), kern[i / WS_NFORMS][i % WS_NFORMS]);
+    }
+};
 
 // The tile switch's two divisions as multiplier / shift pairs (tile_div.h), once a.HB, a.WB and a.GM are set.  A halo wave passes
 // tile indices up to IT - 1 + 2 GM (the look-ahead of a block's last tiles); false when they leave the range the pairs are held to.
@@ -1352,328 +1356,151 @@ bool ws_tile_div(WsArgs& a) {
     return true;
 }
 
-// persistent blocks per channel tile: the CUs a launch may use (segnb_tune "conv_cu_pct") over its ntl channel tiles
-int ws_blocks(int ntl) {
-    const int gm = segnb_knob_conv_cus() / ntl;
-    return gm < 1 ? 1 : gm;
-}
-
-// The tile grid of a launch, once for the four launchers: HB x WB tiles per image, IT in all (the tall form: row tiles of the
-// virtual image), ntl channel tiles, GM persistent blocks per channel tile, and the tile switch's division pairs.  False where
-// ws_tile_div declines; the tall form walks virtual rows -- it has no tile grid to divide by and skips the division.
+// The tile grid of a launch: HB x WB tiles per image, IT in all (the tall form: row tiles of the virtual image), ntl channel tiles,
+// GM persistent blocks per channel tile on cus CUs, the division pairs (false: ws_tile_div declines; the tall form has no grid to divide by)
 template <class C>
-bool ws_tile_grid(WsArgs& a, int ntl) {
+bool ws_tile_grid(WsArgs& a, int ntl, int cus) {
     a.HB = (a.H + C::R - 1) / C::R;
     a.WB = (a.W + C::WT - 1) / C::WT;
     a.IT = C::TALL ? (a.N * (a.H + 1) + C::R - 1) / C::R : a.N * a.HB * a.WB;
     a.NTL = ntl;
     a.KS = 1;
     a.ntmajor = C::TALL ? 1 : 0;
-    int gm = ws_blocks(ntl);
+    int gm = ws_blocks(cus, ntl);
     if (gm > a.IT) gm = a.IT;
     a.GM = gm;
     a.div_hw = a.div_w = tile_div_make(1);
     return C::TALL || ws_tile_div(a);
 }
 
-// Which instantiation serves a launch whose grid is set, and the launch: activation mask / no statistics / timing build / plain, for
-// a configuration K = C or WsEpi<C>.  The affine epilogue (EP) exists in the plain order only.  PAIR: the configuration has the
-// statistics / no-statistics pair and nothing else (the 14 x 14 tile: ws14_serves).
-template <class K, bool PAIR = false>
-int ws_launch_form(const WsArgs& a, hipStream_t stream) {
-    const dim3 grid(a.GM * a.NTL), block(K::NT);
-    if constexpr (!PAIR) {
-        if (a.bn_y != nullptr) {      // activation mask of the producing layer (MASK instantiation: 256 x 64 tiles of the 16x16x32 form)
-            if constexpr (K::MASK_OK) {
-                hipLaunchKernelGGL((conv_fprop_ws_kernel<K, false, false, true, false, true>), grid, block, K::SMEM + 2048, stream, a);
-                return 0;
-            } else {
-                return SEGNB_LAUNCH_DECLINED;
-            }
-        }
-        if constexpr (!ws_epi_of<K>::value) {
-            if (a.ep_act >= 0) {      // (never with statistics: segnb_conv_fprop_act takes none)
-                hipLaunchKernelGGL((conv_fprop_ws_kernel<K, false, true, false>), grid, block, K::SMEM, stream, a);
-                return 0;
-            }
-        }
-    }
-    if (a.stats == nullptr && !a.dbg && segnb_knob_fprop_nostats()) {
-        hipLaunchKernelGGL((conv_fprop_ws_kernel<K, false, false, false>), grid, block, K::SMEM, stream, a);
-        return 0;
-    }
-    if constexpr (!PAIR) {
-        if (a.dbg) {
-            hipLaunchKernelGGL((conv_fprop_ws_kernel<K, true>), grid, block, K::SMEM, stream, a);
-            return 0;
-        }
-    }
-    hipLaunchKernelGGL((conv_fprop_ws_kernel<K, false>), grid, block, K::SMEM, stream, a);
-    return 0;
-}
-
-template <class C>
-int launch_ws(WsArgs& a, hipStream_t stream) {
-    if (a.bn_y != nullptr && !C::MASK_OK) return SEGNB_LAUNCH_DECLINED;      // (activation mask: 16 x 16 tiles, 16x16x32 form)
-    static const int attr_rc = [] {
-        int rc = segnb_opt_in_lds("fprop_ws", C::SMEM, conv_fprop_ws_kernel<C, false>, conv_fprop_ws_kernel<C, true>,
-                                  conv_fprop_ws_kernel<C, false, true, false>, conv_fprop_ws_kernel<C, false, false, false>);
-        if constexpr (C::MASK_OK) {
-            if (rc == 0) rc = segnb_opt_in_lds("fprop_ws", C::SMEM + 2048, conv_fprop_ws_kernel<C, false, false, true, false, true>);
-        }
-        if constexpr (C::TALL) {
-            if (rc == 0)
-                rc = segnb_opt_in_lds("fprop_ws", C::SMEM, conv_fprop_ws_kernel<C, false, false, true, true>,
-                                      conv_fprop_ws_kernel<C, false, false, false, true>);
-        }
-        if constexpr (ws_has_epi<C>()) {
-            using CE = WsEpi<C>;
-            if (rc == 0)
-                rc = segnb_opt_in_lds("fprop_ws", C::SMEM, conv_fprop_ws_kernel<CE, false>, conv_fprop_ws_kernel<CE, true>,
-                                      conv_fprop_ws_kernel<CE, false, false, false>);
-            if constexpr (C::MASK_OK) {
-                if (rc == 0) rc = segnb_opt_in_lds("fprop_ws", C::SMEM + 2048, conv_fprop_ws_kernel<CE, false, false, true, false, true>);
-            }
-        }
-        return rc;
-    }();
-    if (attr_rc) return attr_rc;
-    if (C::TALL && (a.W > C::WT || a.Hi != a.H || a.Wi != a.W)) return SEGNB_LAUNCH_DECLINED;
-    if (!ws_tile_grid<C>(a, (a.Co + C::BN - 1) / C::BN)) return SEGNB_LAUNCH_DECLINED;
+// The launch of what ws_select chose on row ROW: chunk counts, grid, split K where the workspace is there, the kernel [order][form]
+template <int ROW>
+int launch_ws_row(const WsChoice& c, int cus, WsArgs& a, hipStream_t stream) {
+    using C = WsRowCfg<ROW>;
+    static const WsRowKernels<ROW> k(std::make_integer_sequence<int, WS_NFORMS>{});
+    if (k.rc) return k.rc;
+    int ntl = (a.Co + C::BN - 1) / C::BN;
     a.NCH = a.Ci / 64;
+    if constexpr (C::NTAP == 4) {
+        if constexpr (C::UPD) {      // a K chunk = (plane, 64 channels), or two planes of 32
+            a.P32 = a.Ci == 32;
+            a.NCHP = a.P32 ? 1 : a.Ci / 64;
+            a.NCH = a.P32 ? 2 : 4 * a.NCHP;
+        } else {                     // four phases in one launch: a block owns one (phase, channel tile)
+            a.NTLR = ntl;
+            a.NCHP = a.NCH;
+            ntl *= 4;
+        }
+        a.RPS = a.NCH * C::NTAP - 1 < C::RPT ? 2 : 1;               // the previous tile's store rows ride on steps 1.., one or two each
+        if ((a.NCH * C::NTAP - 1) * a.RPS < C::RPT) return SEGNB_LAUNCH_DECLINED;
+    }
+    if (!ws_tile_grid<C>(a, ntl, cus)) return SEGNB_LAUNCH_DECLINED;
+    int form = c.form;
     if constexpr (C::TALL) {
-        const int ks = ksplit_factor<C>(a, a.IT, a.NTL, a.NCH);
-        if (ks > 1 && ksplit_workspace(stream, (size_t)a.IT * a.NTL * ks * 65536, a.IT * a.NTL, &a.ks_slab, &a.ks_cnt) == 0) {
+        const size_t slabs = (size_t)a.IT * a.NTL * c.ks * 65536;
+        if (c.ks > 1 && ksplit_workspace(stream, slabs, a.IT * a.NTL, &a.ks_slab, &a.ks_cnt) == 0) {
             // one tile slice per block: grid = tiles x KS, every block walks NCH / KS chunks
-            a.KS = ks;
-            a.NCH /= ks;
+            a.KS = c.ks;
+            a.NCH /= c.ks;
             a.GM = a.IT;
-            a.ks_slab_bytes = (unsigned)((size_t)a.IT * a.NTL * ks * 65536);
-            const dim3 grid(a.IT * a.NTL * ks);
-            if (a.stats != nullptr || !segnb_knob_fprop_nostats())
-                hipLaunchKernelGGL((conv_fprop_ws_kernel<C, false, false, true, true>), grid, dim3(C::NT), C::SMEM, stream, a);
-            else
-                hipLaunchKernelGGL((conv_fprop_ws_kernel<C, false, false, false, true>), grid, dim3(C::NT), C::SMEM, stream, a);
-            return 0;
+            a.ks_slab_bytes = (unsigned)slabs;
+            form = c.ks_form;
         }
     }
-    if constexpr (ws_has_epi<C>()) {
-        // the store rows on straight-line taps (WsEpi): every form of this configuration but the affine epilogue's
-        if (a.ep_act < 0 && ws_epi_selected(WS_EPI_DEFAULT)) return ws_launch_form<WsEpi<C>>(a, stream);
+    if (g_segnb_census_on) {      // (beside the selector's "kernel:fprop_dma": which row served it, in which order of the store rows)
+        segnb_census(WS_TILES[ROW].tag);
+        if (c.epi) segnb_census("epi:1");
     }
-    return ws_launch_form<C>(a, stream);
-}
-
-// 14 x 14-pixel tiles in 224 matrix rows (cfg 3) for images whose sides are multiples of 14: the tile count, block order and
-// rounds of a launch are those of the 16 x 16 tiles (1, 4, 16 tiles per image at 14^2, 28^2, 56^2) and every tile issues 14
-// MFMAs per K slice and SIMD instead of 16.  The per-element K order (chunk, tap, K slice) is the 16 x 16 form's, so the
-// stored outputs are the same bits; the statistics are summed in another order.  Two instantiations: with statistics (the
-// forwards, the virtual concat among them) and without (the data gradients); everything else stays on the 256-row tiles.
-using WsCfg14 = WsCfg<64, 14, 14, 2, false, true>;
-
-bool ws14_serves(const WsArgs& a) {
-    return a.H % 14 == 0 && a.W % 14 == 0 && a.W <= 56 && a.Co > 32 && a.bn_y == nullptr && a.ep_act < 0 && !a.dbg &&
-           a.up_out == nullptr && segnb_knob_fprop_mf16();
-}
-
-int launch_ws14(WsArgs& a, hipStream_t stream) {
-    using C = WsCfg14;
-    using CE = WsEpi<C>;
-    static const int attr_rc = segnb_opt_in_lds("fprop_ws", C::SMEM, conv_fprop_ws_kernel<C, false>, conv_fprop_ws_kernel<C, false, false, false>,
-                                                conv_fprop_ws_kernel<CE, false>, conv_fprop_ws_kernel<CE, false, false, false>);
-    if (attr_rc) return attr_rc;
-    if (!ws_tile_grid<C>(a, (a.Co + C::BN - 1) / C::BN)) return SEGNB_LAUNCH_DECLINED;      // (sides are multiples of 14: whole tiles)
-    a.NCH = a.Ci / 64;
-    if (g_segnb_census_on) segnb_census("tile:ws14");      // (beside the selector's "kernel:fprop_dma": which tile served it)
-    if (ws_epi_selected(WS_EPI_DEFAULT)) return ws_launch_form<CE, true>(a, stream);
-    return ws_launch_form<C, true>(a, stream);
-}
-
-// the plane gather (data gradient of an upsampled segment): one instantiation (no statistics, no epilogue)
-template <class C>
-int launch_ws_upd(WsArgs& a, hipStream_t stream) {
-    static const int attr_rc = segnb_opt_in_lds("fprop_ws", C::SMEM, conv_fprop_ws_kernel<C, false, false, false>);
-    if (attr_rc) return attr_rc;
-    a.P32 = a.Ci == 32;
-    a.NCHP = a.P32 ? 1 : a.Ci / 64;
-    a.NCH = a.P32 ? 2 : 4 * a.NCHP;
-    a.RPS = a.NCH * C::NTAP - 1 < C::RPT ? 2 : 1;               // the previous tile's store rows ride on steps 1.., one or two each
-    if ((a.NCH * C::NTAP - 1) * a.RPS < C::RPT) return SEGNB_LAUNCH_DECLINED;
-    if (!ws_tile_grid<C>(a, (a.Co + C::BN - 1) / C::BN)) return SEGNB_LAUNCH_DECLINED;
-    hipLaunchKernelGGL((conv_fprop_ws_kernel<C, false, false, false>), dim3(a.GM * a.NTL), dim3(C::NT), C::SMEM, stream, a);
+    const WsKernel kern = k.kern[c.epi][form];
+    hipLaunchKernelGGL(kern, dim3(a.GM * a.NTL * a.KS), dim3(C::NT), k.lds(form), stream, a);
     return 0;
 }
 
-// the forward of an up-sampled segment: four phases in one launch, accumulating (WsCfg UP_ = 2)
-template <class C>
-int launch_ws_upf(WsArgs& a, hipStream_t stream) {
-    static const int attr_rc = segnb_opt_in_lds("fprop_ws", C::SMEM, conv_fprop_ws_kernel<C, false, false, true>);
-    if (attr_rc) return attr_rc;
-    a.NTLR = (a.Co + C::BN - 1) / C::BN;
-    a.NCH = a.Ci / 64;
-    a.NCHP = a.NCH;
-    a.P32 = 0;
-    a.RPS = a.NCH * C::NTAP - 1 < C::RPT ? 2 : 1;               // store rows per step
-    if ((a.NCH * C::NTAP - 1) * a.RPS < C::RPT) return SEGNB_LAUNCH_DECLINED;
-    if (!ws_tile_grid<C>(a, 4 * a.NTLR)) return SEGNB_LAUNCH_DECLINED;
-    hipLaunchKernelGGL((conv_fprop_ws_kernel<C, false, false, true>), dim3(a.GM * a.NTL), dim3(C::NT), C::SMEM, stream, a);
-    return 0;
+using WsLauncher = int (*)(const WsChoice&, int, WsArgs&, hipStream_t);
+template <int... ROW>
+constexpr std::array<WsLauncher, sizeof...(ROW)> ws_launchers(std::integer_sequence<int, ROW...>) {
+    return {{launch_ws_row<ROW>...}};
+}
+constexpr auto WS_LAUNCH = ws_launchers(std::make_integer_sequence<int, WS_NROWS>{});
+
+WsKnobs ws_knobs() {
+    return {segnb_knob_fprop_dma() != 0, segnb_knob_fprop_upd() != 0, segnb_knob_fprop_mask() != 0, segnb_knob_fprop_dma_cfg(),
+            segnb_knob_fprop_dma_epi(), segnb_knob_fprop_ksplit(), segnb_knob_fprop_nostats(), segnb_knob_conv_cus(), WS14_DEFAULT_LEVELS};
 }
 
-// ntaps 16, in_step 2: out[Y, X] = sum_{a, b < 4} in[2 Y + a - 1, 2 X + b - 1] . W[a * 4 + b]  (segnb.convplan.convt_dgrad of a
-// 4 x 4 / stride-2 / pad-1 transposed convolution -- UpConvOp, unet16.py:38, linknet.py:16)
-bool upd_geometry(const segnb_conv_geom* g) {
-    if (g->ntaps != 16 || g->in_step != 2 || !whole_output(g) || g->Hi != 2 * g->Ho || g->Wi != 2 * g->Wo) return false;
-    if ((g->Ci % 64 != 0 && g->Ci != 32) || g->Co <= 32 || g->Wo < 12) return false;
-    for (int t = 0; t < 16; ++t)
-        if (g->dh[t] != t / 4 - 1 || g->dw[t] != t % 4 - 1) return false;
+// The facts of geometry g for ws_select, operands aside; false: not a window of this file.  3 x 3 / stride 1, each position once; or
+// ntaps 16, in_step 2: out[Y, X] = sum_{a, b < 4} in[2 Y + a - 1, 2 X + b - 1] . W[a * 4 + b]  (segnb.convplan.convt_dgrad, UpConvOp)
+bool ws_facts(const segnb_conv_geom* g, WsFacts& f) {
+    f = WsFacts{g->N, g->Ho, g->Wo, g->Hi, g->Wi, g->Ci, g->Co};
+    f.row_major = true;
+    if (g->ntaps == 16) {
+        if (g->in_step != 2 || !whole_output(g)) return false;
+        f.window = WS_WIN_UPD;
+        for (int t = 0; t < 16; ++t) f.row_major = f.row_major && g->dh[t] == t / 4 - 1 && g->dw[t] == t % 4 - 1;
+        return true;
+    }
+    if (!whole_output_3x3_s1(g)) return false;
+    f.window = WS_WIN_3x3;
+    for (int t = 0; t < 9; ++t) f.row_major = f.row_major && g->dw[t] == g->dw[t % 3] && g->dh[t] == g->dh[3 * (t / 3)];
+    f.row_major = f.row_major && segnb_window_once_3x3(g, segnb_tap_window(g));
     return true;
 }
 
-int try_upd(const segnb_conv_geom* g, WsArgs& a, hipStream_t stream) {
-    if (!upd_geometry(g)) return SEGNB_LAUNCH_DECLINED;
-    a.Ktot = 16 * g->Ci;
-    a.dhmin = a.dwmin = 0;
-    for (int t = 0; t < 9; ++t) a.dh[t] = a.dw[t] = 0;
-    a.dh[2] = a.dh[3] = 1;          // 2 x 2 window, row-major: (0,0) (0,1) (1,0) (1,1)
-    a.dw[1] = a.dw[3] = 1;
-    // 8 x 32 or 16 x 16 output tiles: fewer rounds of (equal) tiles on the persistent blocks wins, ties go to 16 x 16
-    const int gm = ws_blocks((g->Co + 63) / 64);
-    const long long it0 = (long long)g->N * ((g->Ho + 7) / 8) * ((g->Wo + 31) / 32);
-    const long long it1 = (long long)g->N * ((g->Ho + 15) / 16) * ((g->Wo + 15) / 16);
-    int cfg = segnb_knob_fprop_dma_cfg();
-    if (cfg < 0) cfg = (it0 + gm - 1) / gm < (it1 + gm - 1) / gm ? 0 : 1;
-    if (cfg == 0) return launch_ws_upd<WsCfg<64, 8, 32, 4, false, true, 4, 1>>(a, stream);
-    return launch_ws_upd<WsCfg<64, 16, 16, 4, false, true, 4, 1>>(a, stream);
-}
-
-// The levels at which the 14 x 14 tile is the default (bit k: square images of 14 << k pixels).  Measured per launch of the
-// bs = 32 224 x 224 step, parent build against this one, alternating on one box (tools/tile14_bench.py, profiles/tile14_ab.txt):
-// forced, all 18 launches at 56^2, 28^2 and 14^2 are 6-12 % faster (741 -> 678 us in sum: 8.6 % of the 12.5 % fewer MFMA rows).
-// By default it serves the 12 of them whose every stored bit AND statistic stays the parent's -- the data gradients of the three
-// levels and the forwards at 14^2 (dispatch_fd: same_stats) -- 1.9-8.3 us each, 741 -> 700 us.  The LDS pays for part of the rest:
-// SQ_LDS_BANK_CONFLICT 6 -> 12 % and SQ_LDS_IDX_ACTIVE 19 -> 29 % of the wave cycles (7 + 2 fragment reads per 14 MFMAs instead
-// of 4 + 4 per 16), SQ_WAIT_INST_LDS unchanged at 2 %.  Other sizes made of 14 x 14 tiles (42^2, 28 x 56 ...)
-// were not measured: they take the tile under the knob only.
-constexpr unsigned WS14_DEFAULT_LEVELS = 7u;
-
-int dispatch_fd(WsArgs& a, hipStream_t stream) {
-    // A/B testing (segnb_tune / environment): "fprop_dma" = 0 disables this path, "fprop_dma_cfg" forces a configuration
-    // (0: 8 x 32, 1: 16 x 16, 2: tall 36 x 7, 3: 14 x 14 in 224 rows -- a launch the 14 x 14 form does not serve takes its
-    // default tile: declined, not refused)
-    int cfg = segnb_knob_fprop_dma_cfg();
-    bool row_major_taps = true;          // the 16x16x32 form indexes its address tables by (t / 3, t % 3)
-    for (int t = 0; t < 9; ++t) row_major_taps = row_major_taps && a.dw[t] == a.dw[t % 3] && a.dh[t] == a.dh[3 * (t / 3)];
-    const bool can14 = row_major_taps && ws14_serves(a);
-    if (cfg == 3 && !can14) cfg = -1;
-    if (cfg < 0) {
-        // measured per ZF_UNET layer at bs=32 (tools/layer_bench.py --cfg): 64-channel output tiles win on every level
-        // from 14x14 to 112x112 -- twice the tiles of a 128-channel form (measured, since removed) on layers that have
-        // only 200-800 of them;
-        // 16 x 16 pixel tiles tie or beat 8 x 32 except for the widest data gradients.  Outputs of <= 32 channels
-        // (half of every tile padding) and 7x7 images stay with fprop_s1 / the general kernel.
-        if (a.Co <= 32) return SEGNB_LAUNCH_DECLINED;
-        // 7 x 7 images (the deepest ZF_UNET level): tall-image tiles of 36 x 7 virtual pixels -- 8 row tiles x 16 channel
-        // tiles = 128 blocks of 144 taps each beat the general kernel's 400 tiles of 64 x 64 (76 -> ~45 us for 1024 -> 1024)
-        if (a.W <= 8) {
-            if (a.W != 7 || a.H != 7) return SEGNB_LAUNCH_DECLINED;
-            return launch_ws<WsCfg<64, 36, 7, 4, true, false>>(a, stream);      // odd halo pitch: 32x32x16 form
-        }
-        // 8 x 32 or 16 x 16 pixel tiles: whichever needs fewer rounds of (equal) tiles on the persistent blocks --
-        // re-measured with the final kernel, the round count decides every case (e.g. 128 -> 384 @56x56: 11 vs 12
-        // rounds, 104 vs 122 us; 64 -> 192 @112x112: 21 vs 19 rounds, 133 vs 116 us); ties go to 16 x 16
-        const int gm = ws_blocks((a.Co + 63) / 64);
-        const long long it0 = (long long)a.N * ((a.H + 7) / 8) * ((a.W + 31) / 32);
-        const long long it1 = (long long)a.N * ((a.H + 15) / 16) * ((a.W + 15) / 16);
-        const long long r0 = (it0 + gm - 1) / gm, r1 = (it1 + gm - 1) / gm;
-        cfg = r0 < r1 ? 0 : 1;
-        if (a.bn_y != nullptr) cfg = 1;      // (activation mask: the 16 x 16 tile form has the 2 KB of LDS left for the mask bytes)
-        // 14 x 14 tiles in 224 rows where the image is made of them: the time of a launch is its rounds x the MFMA rows of a
-        // tile, so the choice minimises that product (ties stay where they were) -- at the levels where it was measured to win
-        // A launch that takes statistics keeps them bit for bit only where the two tilings hold the same pixels per tile -- one
-        // tile per 14 x 14 image (conv_fprop_ws_kernel's store rows) -- so at 28^2 and 56^2 the forwards stay on 16 x 16 tiles:
-        // another summation order moves the training step's outputs by per cents
-        const bool same_stats = a.stats == nullptr || a.W == 14;
-        if (can14 && same_stats && a.H == a.W && ((a.W == 14 && (WS14_DEFAULT_LEVELS & 1u)) || (a.W == 28 && (WS14_DEFAULT_LEVELS & 2u)) ||
-                                                  (a.W == 56 && (WS14_DEFAULT_LEVELS & 4u)))) {
-            const long long it3 = (long long)a.N * (a.H / 14) * (a.W / 14);
-            const long long r3 = (it3 + gm - 1) / gm;
-            if (r3 * WsCfg14::BM < (cfg == 0 ? r0 : r1) * 256) cfg = 3;
-        }
-    }
-    if (cfg == 3) return launch_ws14(a, stream);
-    if (segnb_knob_fprop_mf16() && row_major_taps) {
-        switch (cfg) {
-            case 0: return launch_ws<WsCfg<64, 8, 32, 4, false, true>>(a, stream);
-            case 1: return launch_ws<WsCfg<64, 16, 16, 4, false, true>>(a, stream);
-            case 2: return launch_ws<WsCfg<64, 36, 7, 4, true, false>>(a, stream);
-            default: return SEGNB_LAUNCH_DECLINED;
-        }
-    }
-    switch (cfg) {
-        case 0: return launch_ws<WsCfg<64, 8, 32, 4, false, false>>(a, stream);
-        case 1: return launch_ws<WsCfg<64, 16, 16, 4, false, false>>(a, stream);
-        case 2: return launch_ws<WsCfg<64, 36, 7, 4, true, false>>(a, stream);
-        default: return SEGNB_LAUNCH_DECLINED;
-    }
-}
-
-}  // namespace
-
-// out[n, 2 Y + py, 2 X + px, :] += sum_{a, b < 2} in[n, Y + py - 1 + a, X + px - 1 + b, :] . W[phase][:, tap, :]  for the four
-// phases (py, px); wpacked = [4][CoW][4][Ci] (phase-major, the tap lists of segnb.convplan.convt_fwd(4, 2, 1)); statistics of
-// the sums
-int segnb_fprop_upf_try(segnb_try_outcome* did, int N, int H, int W, int Ci, int ld_in, const void* in, unsigned in_bytes,
-                        const void* wpacked, unsigned w_bytes, int Co, int CoW, void* out, int ld_out, double* stats, hipStream_t stream,
-                        const float* bias, int bias_n, int no_prev, int ep_act, float ep_slope) {
-    *did = SEGNB_TRY_DECLINED;
-    if (!segnb_knob_fprop_dma() || !segnb_knob_fprop_upd()) return 0;
-    if (Ci % 64 != 0 || Ci < 128 || (Co <= 32 && !no_prev) || W < 12) return 0;
-    WsArgs a;
+// Operands and extents of a launch into a value-initialised WsArgs (what a path does not use stays zero in the kernarg); ntaps of the
+// K extent: 9, the 16 of the plane gather, the 4 of one phase.  False: the out_pix pixels of the output pass a buffer descriptor.
+bool ws_args(WsArgs& a, const WsFacts& f, int ntaps, int ld_x, int ld_out, long long out_pix, const void* in, unsigned in_bytes,
+             const void* wpacked, unsigned w_bytes, const float* bias, int bias_n, void* out, double* stats) {
     a.x = (const bf16_t*)in;
     a.w = (const bf16_t*)wpacked;
     a.x_bytes = in_bytes;
     a.w_bytes = w_bytes;
     a.bias = bias;
     a.bias_n = bias_n;
-    a.no_prev = no_prev;
     a.out = (bf16_t*)out;
     a.stats = stats;
-    a.N = N; a.H = H; a.W = W; a.Hi = H; a.Wi = W;
-    a.Ci = Ci; a.Co = Co; a.ld_x = ld_in; a.ld_out = ld_out;
-    a.CoW = CoW;
-    a.Ktot = 4 * Ci;
-    if (!segnb_fits_desc(segnb_nhwc_bytes((long long)N * 4 * H * W, ld_out, Co, 2), &a.out_bytes)) return 0;
-    a.dhmin = a.dwmin = 0;
-    for (int t = 0; t < 9; ++t) a.dh[t] = a.dw[t] = 0;
-    a.dh[2] = a.dh[3] = 1;
-    a.dw[1] = a.dw[3] = 1;
-    a.dbg = 0;
-    a.u = nullptr;
-    a.up_out = nullptr;
-    a.bn_y = nullptr;
-    a.ep_act = ep_act;          // (UPF: applied in the accumulator staging of this instantiation, not the EP one)
-    a.ep_coef = nullptr;
-    a.ep_slope = ep_slope;
-    const int gm = ws_blocks(4 * ((Co + 63) / 64));
-    const long long it0 = (long long)N * ((H + 7) / 8) * ((W + 31) / 32);
-    const long long it1 = (long long)N * ((H + 15) / 16) * ((W + 15) / 16);
-    int cfg = segnb_knob_fprop_dma_cfg();
-    if (cfg < 0) cfg = (it0 + gm - 1) / gm < (it1 + gm - 1) / gm ? 0 : 1;
-    const int rc = cfg == 0 ? launch_ws_upf<WsCfg<64, 8, 32, 4, false, true, 4, 2>>(a, stream)
-                            : launch_ws_upf<WsCfg<64, 16, 16, 4, false, true, 4, 2>>(a, stream);
-    return segnb_try_launched(did, rc);
+    a.N = f.N; a.H = f.H; a.W = f.W; a.Hi = f.Hi; a.Wi = f.Wi;
+    a.Ci = f.Ci; a.Co = f.Co; a.ld_x = ld_x; a.ld_out = ld_out;
+    a.Ktot = ntaps * f.Ci;
+    a.bn_act = SEGNB_ACT_NONE;
+    a.ep_act = -1;
+    if (f.window != WS_WIN_3x3) {      // 2 x 2 window at the origin, row-major: (0,0) (0,1) (1,0) (1,1)
+        a.dh[2] = a.dh[3] = 1;
+        a.dw[1] = a.dw[3] = 1;
+    }
+    return segnb_fits_desc(segnb_nhwc_bytes(out_pix, ld_out, f.Co, 2), &a.out_bytes);
 }
 
-// 1 when the MASK instantiation serves the data gradient g (segnb_conv_fprop_actmask_ok): what segnb_fprop_dma_try + dispatch_fd accept
-int segnb_fprop_dma_actmask_ok(const segnb_conv_geom* g) {
-    if (!segnb_knob_fprop_dma() || !segnb_knob_fprop_mask() || !segnb_knob_fprop_mf16() || segnb_knob_fprop_dma_cfg() == 2 ||
-        segnb_fprop_general_forced())
+}  // namespace
+
+// out[n, 2 Y + py, 2 X + px, :] += sum_{a, b < 2} in[n, Y + py - 1 + a, X + px - 1 + b, :] . W[phase][:, tap, :]  for the four phases
+// (py, px); wpacked = [4][CoW][4][Ci] (phase-major, the tap lists of segnb.convplan.convt_fwd(4, 2, 1)); statistics of the sums
+int segnb_fprop_upf_try(segnb_try_outcome* did, int N, int H, int W, int Ci, int ld_in, const void* in, unsigned in_bytes,
+                        const void* wpacked, unsigned w_bytes, int Co, int CoW, void* out, int ld_out, double* stats, hipStream_t stream,
+                        const float* bias, int bias_n, int no_prev, int ep_act, float ep_slope) {
+    *did = SEGNB_TRY_DECLINED;
+    WsFacts f = {N, H, W, H, W, Ci, Co};
+    f.window = WS_WIN_UPF;
+    f.row_major = true;
+    f.stats = stats != nullptr;
+    f.no_prev = no_prev != 0;
+    const WsKnobs k = ws_knobs();
+    const WsChoice c = ws_select(f, k);
+    WsArgs a{};
+    if (c.row == WS_NONE || !ws_args(a, f, 4, ld_in, ld_out, (long long)N * 4 * H * W, in, in_bytes, wpacked, w_bytes, bias, bias_n, out, stats))
         return 0;
-    if (!whole_output_3x3_s1(g) || g->Ci % 64 != 0 || g->Co <= 32 || g->Co % 8 != 0 || g->Wo <= 8) return 0;
-    for (int t = 0; t < 9; ++t)          // row-major 3 x 3 window (either direction): the 16x16x32 form's address tables
-        if (g->dh[t] != g->dh[3 * (t / 3)] || g->dw[t] != g->dw[t % 3]) return 0;
-    if (!segnb_window_once_3x3(g, segnb_tap_window(g))) return 0;
+    a.no_prev = no_prev;
+    a.CoW = CoW;
+    a.ep_act = ep_act;          // (UPF: applied in the accumulator staging of this instantiation, not the EP one)
+    a.ep_slope = ep_slope;
+    return segnb_try_launched(did, WS_LAUNCH[c.row](c, k.cus, a, stream));
+}
+
+// 1 when the MASK instantiation serves the data gradient g (segnb_conv_fprop_actmask_ok): what segnb_fprop_dma_try accepts
+int segnb_fprop_dma_actmask_ok(const segnb_conv_geom* g) {
+    WsFacts f;
+    if (segnb_fprop_general_forced() || !ws_facts(g, f) || f.window != WS_WIN_3x3 || g->Co % 8 != 0) return 0;      // (y in 8-channel chunks)
+    f.mask = f.stats = true;
+    if (ws_select(f, ws_knobs()).row == WS_NONE) return 0;
     return segnb_fits_desc(segnb_nhwc_bytes((long long)g->N * g->Hi * g->Wi, g->ld_in, g->Ci, 2)) &&
                    segnb_fits_desc(segnb_nhwc_bytes((long long)g->N * g->Ho * g->Wo, g->ld_out, g->Co, 2))
                ? 1
@@ -1681,9 +1508,11 @@ int segnb_fprop_dma_actmask_ok(const segnb_conv_geom* g) {
 }
 
 extern "C" int segnb_conv_fprop_upd_ok(const segnb_conv_geom* g, int dtype) {
-    if (g == nullptr || dtype != SEGNB_BF16) return 0;
-    if (!segnb_knob_fprop_dma() || !segnb_knob_fprop_upd() || segnb_fprop_general_forced()) return 0;
-    return upd_geometry(g) && segnb_fits_desc(segnb_nhwc_bytes((long long)g->N * g->Ho * g->Wo, g->ld_out, g->Co, 2)) ? 1 : 0;
+    WsFacts f;
+    if (g == nullptr || dtype != SEGNB_BF16 || segnb_fprop_general_forced() || !ws_facts(g, f) || f.window != WS_WIN_UPD) return 0;
+    return ws_select(f, ws_knobs()).row != WS_NONE && segnb_fits_desc(segnb_nhwc_bytes((long long)g->N * g->Ho * g->Wo, g->ld_out, g->Co, 2))
+               ? 1
+               : 0;
 }
 
 // timing builds: copy the stamps of the last stamped launch to the host (3 roles x 256 steps x 4 clocks)
@@ -1697,60 +1526,35 @@ int segnb_fprop_dma_try(segnb_try_outcome* did, const segnb_conv_geom* g, const 
                         hipStream_t stream, const segnb_act_epilogue* ep, const segnb_upcat_src* uc,
                         const segnb_bn_reduce_epilogue* bn) {
     *did = SEGNB_TRY_DECLINED;
-    if (!segnb_knob_fprop_dma()) return 0;
-    // (fused BatchNorm-backward REDUCTIONS: fprop_rw.hip / fprop_roll.hip; here only the activation mask of a layer without
-    // BatchNorm -- coef NULL -- on a plain data gradient: the MASK instantiation)
-    if (bn != nullptr && (bn->coef != nullptr || bn->y == nullptr || bn->sums == nullptr || ep != nullptr || uc != nullptr ||
-                          stats != nullptr || bias != nullptr || !segnb_taps_3x3(g) || !segnb_knob_fprop_mask()))
+    WsFacts f;
+    if (!ws_facts(g, f)) return 0;
+    // (fused BatchNorm-backward REDUCTIONS: fprop_rw.hip / fprop_roll.hip; here only the activation mask of a layer without BatchNorm
+    // -- coef NULL -- on a plain data gradient: the MASK instantiation, y in 16-byte loads of 8-channel chunks)
+    if (bn != nullptr && (bn->coef != nullptr || bn->y == nullptr || bn->sums == nullptr || stats != nullptr || bias != nullptr ||
+                          bn->ld_y % 8 != 0))
         return 0;
-    if (g->ntaps == 16 && ep == nullptr && stats == nullptr && bias == nullptr && segnb_knob_fprop_upd()) {
-        WsArgs a;
-        a.x = (const bf16_t*)in;
-        a.w = (const bf16_t*)wpacked;
-        a.x_bytes = in_bytes;
-        a.w_bytes = w_bytes;
-        a.bias = nullptr;
-        a.bias_n = 0;
-        a.out = (bf16_t*)out;
-        a.stats = nullptr;
-        a.N = g->N; a.H = g->Ho; a.W = g->Wo; a.Hi = g->Hi; a.Wi = g->Wi;
-        a.Ci = g->Ci; a.Co = g->Co; a.ld_x = g->ld_in; a.ld_out = g->ld_out;
-        if (!segnb_fits_desc(segnb_nhwc_bytes((long long)g->N * g->Ho * g->Wo, g->ld_out, g->Co, 2), &a.out_bytes)) return 0;
-        a.dbg = 0;
-        a.u = nullptr;
-        a.up_out = nullptr;
-    a.no_prev = 0;
-        a.bn_y = nullptr;
-        a.ep_act = -1;
-        a.ep_coef = nullptr;
-        a.ep_slope = 0.f;
-        const int rc = try_upd(g, a, stream);
-        return segnb_try_launched(did, rc);
+    f.mask = bn != nullptr;
+    f.stats = stats != nullptr || f.mask;
+    f.ep = ep != nullptr;
+    f.upcat = uc != nullptr;
+    f.bias = bias != nullptr;
+    const int dbg = f.window == WS_WIN_3x3 ? segnb_knob_fprop_dma_dbg() : 0;      // (timing builds: the 3 x 3 window only)
+    f.dbg = dbg != 0;
+    const WsKnobs k = ws_knobs();
+    const WsChoice c = ws_select(f, k);
+    WsArgs a{};
+    if (c.row == WS_NONE || !ws_args(a, f, g->ntaps, g->ld_in, g->ld_out, (long long)g->N * g->Ho * g->Wo, in, in_bytes, wpacked, w_bytes,
+                                     bias, bias_n, out, stats))
+        return 0;
+    if (f.window == WS_WIN_3x3) {
+        const segnb_tap_win win = segnb_tap_window(g);
+        a.dhmin = win.dhmin; a.dwmin = win.dwmin;
+        segnb_rel_taps(g, win, a.dh, a.dw);
     }
-    if (!whole_output_3x3_s1(g) || g->Ci % 64 != 0) return 0;
-    const segnb_tap_win win = segnb_tap_window(g);
-    WsArgs a;
-    a.x = (const bf16_t*)in;
-    a.w = (const bf16_t*)wpacked;
-    a.x_bytes = in_bytes;
-    a.w_bytes = w_bytes;
-    a.bias = bias;
-    a.bias_n = bias_n;
-    a.out = (bf16_t*)out;
-    a.stats = stats;
-    a.N = g->N; a.H = g->Ho; a.W = g->Wo; a.Hi = g->Hi; a.Wi = g->Wi;
-    a.Ci = g->Ci; a.Co = g->Co; a.ld_x = g->ld_in; a.ld_out = g->ld_out;
-    a.Ktot = 9 * g->Ci;
-    if (!segnb_fits_desc(segnb_nhwc_bytes((long long)g->N * g->Ho * g->Wo, g->ld_out, g->Co, 2), &a.out_bytes)) return 0;
-    a.dhmin = win.dhmin; a.dwmin = win.dwmin;
-    segnb_rel_taps(g, win, a.dh, a.dw);
-    a.dbg = segnb_knob_fprop_dma_dbg();
-    a.up_out = nullptr;
-    a.no_prev = 0;
-    a.u = nullptr;
+    a.dbg = dbg;
     if (uc != nullptr) {
         // virtual concat: in = the skip tensor (channels Cu.. of the logical input), uc->u = the low-resolution tensor
-        if (uc->Cu % 64 != 0 || uc->Cu <= 0 || uc->Cu >= g->Ci || (g->Hi & 1) || (g->Wi & 1) || g->Wo <= 8) return 0;
+        if (uc->Cu % 64 != 0 || uc->Cu <= 0 || uc->Cu >= g->Ci || (g->Hi & 1) || (g->Wi & 1)) return 0;
         a.u = (const bf16_t*)uc->u;
         a.ld_u = uc->ld_u;
         a.NCHU = uc->Cu / 64;
@@ -1758,15 +1562,12 @@ int segnb_fprop_dma_try(segnb_try_outcome* did, const segnb_conv_geom* g, const 
         a.Wu = g->Wi / 2;
         if (!segnb_fits_desc(segnb_nhwc_bytes((long long)g->N * a.Hu * a.Wu, uc->ld_u, uc->Cu, 2), &a.u_bytes)) return 0;
     }
-    a.bn_y = nullptr;
-    a.bn_act = SEGNB_ACT_NONE;
-    a.bn_slope = 0.f;
     if (bn != nullptr) {
-        // (16-byte loads of 8-channel chunks; bn->coef is NULL here -- the gate at the top -- and so is a.bn_coef)
-        if (bn->ld_y % 8 != 0 || !take_bn_reduce(a, g, bn)) return 0;
+        // (bn->coef is NULL here -- the gate above -- and so is a.bn_coef)
+        if (!take_bn_reduce(a, g, bn)) return 0;
         a.stats = bn->sums;          // [REPL][2][Co]: slot 0 = sum dz (the bias gradient's source), slot 1 = sum dz^2 (cleared with it)
     }
     take_act_epilogue(a, ep);
-    const int rc = dispatch_fd(a, stream);
-    return segnb_try_launched(did, rc);
+    return segnb_try_launched(did, WS_LAUNCH[c.row](c, k.cus, a, stream));
 }
+

@@ -12,6 +12,9 @@
 //   * same wave specialisation, transposed accumulators, LDS-staged 16-byte stores and store-pass statistics as
 //     fprop_dma.hip.
 #include "fprop_dma.h"
+#include "ws_select.h"
+
+#include <array>
 
 namespace {
 
@@ -461,12 +464,20 @@ __global__ __launch_bounds__(C::NT) void conv_fprop_rw_kernel(const FdArgs a) {
     }
 }
 
-template <class C>
-int launch_rw(FdArgs& a, hipStream_t stream) {
-    static const int attr_rc = segnb_opt_in_lds("fprop_rw", C::SMEM, conv_fprop_rw_kernel<C, false>, conv_fprop_rw_kernel<C, true>,
-                                                conv_fprop_rw_kernel<C, false, true>);
+// ---- the launchers: one row of RW_TILES (ws_select.h) = one RwCfg = one launcher ---------------------------------------------------
+template <int ROW>
+using RwRowCfg = RwCfg<RW_TILES[ROW].BN, RW_TILES[ROW].NS, RW_TILES[ROW].NSW, RW_TILES[ROW].R, RW_TILES[ROW].WT>;
+using RwKernel = void (*)(const FdArgs);
+enum { RW_PLAIN, RW_DBG, RW_EP, RW_NFORMS };      // timing builds: separately instantiated, the production kernel carries no run-time checks
+
+template <int ROW>
+int launch_rw_row(FdArgs& a, hipStream_t stream) {
+    using C = RwRowCfg<ROW>;
+    // the forms of a row, once: what is launched below is what is opted in here
+    static const RwKernel kern[RW_NFORMS] = {conv_fprop_rw_kernel<C, false>, conv_fprop_rw_kernel<C, true>, conv_fprop_rw_kernel<C, false, true>};
+    static const int attr_rc = segnb_opt_in_lds("fprop_rw", C::SMEM, kern[RW_PLAIN], kern[RW_DBG], kern[RW_EP]);
     if (attr_rc) return attr_rc;
-    if (a.NCH * 9 * C::BN * 64 > C::W_MAX) return SEGNB_LAUNCH_DECLINED;
+    if (a.NCH * 9 * C::BN * 64 > C::W_MAX) return SEGNB_LAUNCH_DECLINED;      // (the resident weights beside ring and staging)
     a.HB = (a.H + C::R - 1) / C::R;
     a.WB = (a.W + C::WT - 1) / C::WT;
     a.IT = a.N * a.HB * a.WB;
@@ -474,26 +485,22 @@ int launch_rw(FdArgs& a, hipStream_t stream) {
     int gm = segnb_knob_conv_cus();
     if (gm > a.IT) gm = a.IT;
     a.GM = gm;
-    if (a.ep_act >= 0)
-        hipLaunchKernelGGL((conv_fprop_rw_kernel<C, false, true>), dim3(a.GM), dim3(C::NT), C::SMEM, stream, a);
-    else if (a.dbg)       // timing builds: separately instantiated, the production kernel carries no run-time checks
-        hipLaunchKernelGGL((conv_fprop_rw_kernel<C, true>), dim3(a.GM), dim3(C::NT), C::SMEM, stream, a);
-    else
-        hipLaunchKernelGGL((conv_fprop_rw_kernel<C, false>), dim3(a.GM), dim3(C::NT), C::SMEM, stream, a);
+    const RwKernel k = kern[a.ep_act >= 0 ? RW_EP : a.dbg ? RW_DBG : RW_PLAIN];
+    hipLaunchKernelGGL(k, dim3(a.GM), dim3(C::NT), C::SMEM, stream, a);
     return 0;
 }
 
-}  // namespace
+using RwLauncher = int (*)(FdArgs&, hipStream_t);
+template <int... ROW>
+constexpr std::array<RwLauncher, sizeof...(ROW)> rw_launchers(std::integer_sequence<int, ROW...>) {
+    return {{launch_rw_row<ROW>...}};
+}
+constexpr auto RW_LAUNCH = rw_launchers(std::make_integer_sequence<int, RW_NROWS>{});
 
-int segnb_fprop_rw_try(segnb_try_outcome* did, const segnb_conv_geom* g, const void* in, unsigned in_bytes, const void* wpacked,
-                       unsigned w_bytes, const float* bias, int bias_n, void* out, double* stats,
-                       hipStream_t stream, const segnb_bn_reduce_epilogue* bn, const segnb_act_epilogue* ep,
-                       const segnb_upcat_src* uc, const segnb_upcat_src* upsum) {
-    *did = SEGNB_TRY_DECLINED;
-    if (!segnb_knob_fprop_dma() || !segnb_knob_fprop_rw()) return 0;
-    if (!whole_output_3x3_s1(g) || g->Ci % 32 != 0 || g->Ci > 96 || g->Co > 96 || g->Wo < 12) return 0;
+// Operands and extents of geometry g into a value-initialised FdArgs; false: the output passes a buffer descriptor
+bool rw_args(FdArgs& a, const segnb_conv_geom* g, const void* in, unsigned in_bytes, const void* wpacked, unsigned w_bytes,
+             const float* bias, int bias_n, void* out, double* stats) {
     const segnb_tap_win win = segnb_tap_window(g);
-    FdArgs a;
     a.x = (const bf16_t*)in;
     a.w = (const bf16_t*)wpacked;
     a.x_bytes = in_bytes;
@@ -506,12 +513,24 @@ int segnb_fprop_rw_try(segnb_try_outcome* did, const segnb_conv_geom* g, const v
     a.Ci = g->Ci; a.Co = g->Co; a.ld_x = g->ld_in; a.ld_out = g->ld_out;
     a.Ktot = 9 * g->Ci;
     a.NCH = g->Ci / 32;
-    if (!segnb_fits_desc(segnb_nhwc_bytes((long long)g->N * g->Ho * g->Wo, g->ld_out, g->Co, 2), &a.out_bytes)) return 0;
     a.dhmin = win.dhmin; a.dwmin = win.dwmin;
     segnb_rel_taps(g, win, a.dh, a.dw);
     a.dbg = segnb_knob_fprop_dma_dbg();
-    a.up_out = nullptr;
-    a.no_prev = 0;
+    return segnb_fits_desc(segnb_nhwc_bytes((long long)g->N * g->Ho * g->Wo, g->ld_out, g->Co, 2), &a.out_bytes);
+}
+
+}  // namespace
+
+int segnb_fprop_rw_try(segnb_try_outcome* did, const segnb_conv_geom* g, const void* in, unsigned in_bytes, const void* wpacked,
+                       unsigned w_bytes, const float* bias, int bias_n, void* out, double* stats,
+                       hipStream_t stream, const segnb_bn_reduce_epilogue* bn, const segnb_act_epilogue* ep,
+                       const segnb_upcat_src* uc, const segnb_upcat_src* upsum) {
+    *did = SEGNB_TRY_DECLINED;
+    if (!segnb_knob_fprop_dma() || !segnb_knob_fprop_rw()) return 0;
+    if (!whole_output_3x3_s1(g) || g->Ci % 32 != 0) return 0;
+    const int row = rw_select(g->Co, g->Ci / 32, g->Wo, stats != nullptr);
+    FdArgs a{};
+    if (row == RW_NONE || !rw_args(a, g, in, in_bytes, wpacked, w_bytes, bias, bias_n, out, stats)) return 0;
     if (upsum != nullptr) {
         // (segnb_upcat_src reused as the destination: u = the low-resolution gradient, Cu = leading channels that go there)
         if (upsum->Cu % 8 != 0 || upsum->Cu <= 0 || upsum->Cu >= g->Co || (g->Ho & 1) || (g->Wo & 1) || stats != nullptr ||
@@ -521,7 +540,6 @@ int segnb_fprop_rw_try(segnb_try_outcome* did, const segnb_conv_geom* g, const v
         a.up_C = upsum->Cu;
         a.up_ld = upsum->ld_u;
     }
-    a.u = nullptr;
     if (uc != nullptr) {
         // virtual concat: `in` = the skip tensor (logical channels Cu..), uc->u = the tensor the first Cu channels are upsampled from
         if (uc->Cu % 32 != 0 || uc->Cu <= 0 || uc->Cu >= g->Ci || (g->Hi & 1) || (g->Wi & 1) || a.dbg) return 0;
@@ -532,33 +550,11 @@ int segnb_fprop_rw_try(segnb_try_outcome* did, const segnb_conv_geom* g, const v
         a.Wu = g->Wi / 2;
         if (!segnb_fits_desc(segnb_nhwc_bytes((long long)g->N * a.Hu * a.Wu, uc->ld_u, uc->Cu, 2), &a.u_bytes)) return 0;
     }
-    a.bn_y = nullptr;
     take_act_epilogue(a, ep);
     if (bn != nullptr) {
         if (stats != nullptr || g->Co > 64) return 0;                 // one accumulator set per launch; 96-wide: no statistics threads
         if (!take_bn_reduce(a, g, bn)) return 0;
     }
-    int rc;
-    // ring depth by what the resident weights leave of the 160 KiB.  96-channel outputs (the data gradient of the
-    // 96 -> 32 concat layer: 53 KiB of staging beside 55 KiB of weights) run on a two-stage ring and without the
-    // BatchNorm statistics (twelve chunks per row do not divide the store threads; a data gradient has none)
-    const int nsw = segnb_knob_rw_store_waves();
-    // 8 x 32 pixel tiles on wide images: longer contiguous rows per fetch / store (224 x 224: 65 vs 69 us forward, 54 vs 58
-    // data gradient, same box); 16 x 16 stays better at 112 x 112 (40 vs 45 us)
-    if (g->Co <= 32 && (nsw == 8 || (nsw == 4 && g->Wo >= 192)))
-        rc = a.NCH == 1 ? launch_rw<RwCfg<32, 5, 4, 8, 32>>(a, stream)
-             : a.NCH == 2 ? launch_rw<RwCfg<32, 4, 4, 8, 32>>(a, stream) : launch_rw<RwCfg<32, 3, 4, 8, 32>>(a, stream);
-    else if (g->Co <= 32 && nsw == 4)
-        rc = a.NCH == 1 ? launch_rw<RwCfg<32, 5, 4>>(a, stream)
-             : a.NCH == 2 ? launch_rw<RwCfg<32, 4, 4>>(a, stream) : launch_rw<RwCfg<32, 3, 4>>(a, stream);
-    else if (g->Co <= 32)
-        rc = a.NCH == 1 ? launch_rw<RwCfg<32, 5>>(a, stream)
-             : a.NCH == 2 ? launch_rw<RwCfg<32, 4>>(a, stream) : launch_rw<RwCfg<32, 3>>(a, stream);
-    else if (g->Co <= 64)
-        rc = nsw == 4 ? launch_rw<RwCfg<64, 3, 4>>(a, stream) : launch_rw<RwCfg<64, 3>>(a, stream);
-    else if (stats == nullptr)
-        rc = launch_rw<RwCfg<96, 2>>(a, stream);
-    else
-        return 0;
-    return segnb_try_launched(did, rc);
+    return segnb_try_launched(did, RW_LAUNCH[row](a, stream));
 }
+

@@ -305,14 +305,6 @@ int segnb_knob_fprop_deepk() {
 }
 static int g_fprop_thin = 1;       // thin input (<= 16 channels), wide output: conv_thin_kernel (tune key only: tests, A/B)
 int segnb_knob_fprop_thin() { return g_fprop_thin; }
-static int g_fprop_mf16 = -2;      // conv_fprop_ws_kernel on v_mfma_f32_16x16x32_bf16 (1, default) or 32x32x16 (0)
-int segnb_knob_fprop_mf16() {
-    if (g_fprop_mf16 == -2) {
-        const char* e = getenv("SEGNB_FPROP_MF16");
-        g_fprop_mf16 = (e != nullptr && e[0] == '0') ? 0 : 1;
-    }
-    return g_fprop_mf16;
-}
 static int g_fprop_upd = -2;       // plane-gather form of conv_fprop_ws_kernel for 4x4 / stride-2 gathers (A/B: SEGNB_FPROP_UPD=0)
 int segnb_knob_fprop_upd() {
     if (g_fprop_upd == -2) {
@@ -339,8 +331,6 @@ int segnb_knob_fprop_drop() {
 }
 static int g_fprop_nostats = 1;    // conv_fprop_ws_kernel: statistics-free instantiation for launches without statistics (A/B)
 int segnb_knob_fprop_nostats() { return g_fprop_nostats; }
-static int g_rw_store_waves = 4;   // store waves of conv_fprop_rw_kernel: 4 (default) or 2 (round 1)
-int segnb_knob_rw_store_waves() { return g_rw_store_waves; }
 static int g_bnreduce_fused = -2;  // data-gradient launches that also do the next BatchNorm-backward reduction (A/B: SEGNB_BNREDUCE_FUSED=0)
 int segnb_knob_bnreduce_fused() {
     if (g_bnreduce_fused == -2) {
@@ -349,7 +339,7 @@ int segnb_knob_bnreduce_fused() {
     }
     return g_bnreduce_fused;
 }
-// split K of conv_fprop_ws_kernel (fprop_dma.hip: ksplit_factor): 0 off, 1 automatic (default), 2 / 4 forced (A/B: SEGNB_FPROP_KSPLIT)
+// split K of conv_fprop_ws_kernel (ws_select.h: ws_ksplit): 0 off, 1 automatic (default), 2 / 4 forced (A/B: SEGNB_FPROP_KSPLIT)
 static int g_fprop_ksplit = -2;
 int segnb_knob_fprop_ksplit() {
     if (g_fprop_ksplit == -2) {
@@ -450,10 +440,6 @@ extern "C" int segnb_tune(const char* key, int value) {
         g_fprop_nostats = value ? 1 : 0;
         return 0;
     }
-    if (strcmp(key, "rw_store_waves") == 0) {
-        g_rw_store_waves = value == 2 ? 2 : (value == 8 ? 8 : 4);
-        return 0;
-    }
     if (strcmp(key, "bnreduce_fused") == 0) {
         g_bnreduce_fused = value ? 1 : 0;
         return 0;
@@ -464,10 +450,6 @@ extern "C" int segnb_tune(const char* key, int value) {
     }
     if (strcmp(key, "fprop_thin") == 0) {
         g_fprop_thin = value ? 1 : 0;
-        return 0;
-    }
-    if (strcmp(key, "fprop_mf16") == 0) {
-        g_fprop_mf16 = value ? 1 : 0;
         return 0;
     }
     if (strcmp(key, "call_census") == 0) {

@@ -64,9 +64,37 @@ CASES = {
     'wsx_3x3s2_w32': ('bf16', 2, 48, 48, 32, 64, 3, 2, True),        # Wo = 24
     'wsx_3x3s2_w16': ('bf16', 2, 24, 24, 32, 64, 3, 2, True),        # Wo = 12
     'wsx_7x7s2': ('bf16', 2, 64, 64, 8, 64, 7, 2, True),             # the stem, Wo >= 32
+    # fprop_dma.hip WS_ROWS (ws_select.h: ws_select): the rows this format can express ('dma_64_64': 16 x 16, 'wg_flat14': 14 x 14)
+    'ws_8x32': ('bf16', 2, 24, 32, 64, 64, 3, 1, True, {'conv_cu_pct': 1}),      # two persistent blocks: 3 rounds of 8 x 32 against 4
+    'ws_tall_ksplit': ('bf16', 2, 7, 7, 256, 64, 3, 1, True),        # 7 x 7 images: the tall row, four chunks in two slices
+    # fprop_rw.hip RW_ROWS (ws_select.h: rw_select): one geometry per row ('rw_32_64': <64,3,4>)
+    'rw_32_32': ('bf16', 2, 12, 20, 32, 32, 3, 1, True),             # <32,5,4>
+    'rw_64_32': ('bf16', 2, 12, 20, 64, 32, 3, 1, True),             # <32,4,4>
+    'rw_96_32': ('bf16', 2, 12, 20, 96, 32, 3, 1, True),             # <32,3,4>; its data gradient (32 -> 96): <96,2>
+    # (Wo >= 192.  The rolling-window kernel stands in front of this one in the cascade and takes 32 and 64 input channels at this
+    # size -- recorded as such: <32,5,4,8,32> and <32,4,4,8,32> are rows this format does not reach at the default knobs)
+    'rw_wide_32_32': ('bf16', 1, 8, 192, 32, 32, 3, 1, True),
+    'rw_wide_64_32': ('bf16', 1, 8, 192, 64, 32, 3, 1, True),
+    'rw_wide_96_32': ('bf16', 1, 8, 192, 96, 32, 3, 1, True),        # <32,3,4,8,32>
 }
+# what segnb_tune keys of a case go back to after its launches
+KNOB_DEFAULTS = {'wgrad_roll': 0, 'conv_cu_pct': 100}
 # selectors that no case above reaches, and the gate that keeps them away
 UNREACHED = {}
+# rows of fprop_dma.hip's table that the case format cannot express: the gate, and the test that runs them
+WS_ROWS_UNREACHED = {
+    'tile:ws_upd8x32': 'plane gather (ntaps 16, in_step 2: segnb.engine.UpConvOp data gradient): fused_table() "act upconv T4x4 s2 relu", '
+                       'test_hip_ops.py',
+    'tile:ws_upd16': 'plane gather, the 16 x 16 tile: test_hip_ops.py',
+    'tile:ws_upf8x32': 'phase forward (segnb_upconv_fprop): fused_table() "act upconv T4x4 s2 relu", test_hip_ops.py',
+    'tile:ws_upf16': 'phase forward, the 16 x 16 tile: test_hip_ops.py',
+}
+# forms of the rows above that the case format cannot express
+WS_FORMS_UNREACHED = {
+    'mask': 'activation mask (segnb_conv_fprop_bnreduce without coefficients): test_ws_epi_gpu.py, test_ws_tile_switch_gpu.py',
+    'affine epilogue': 'segnb_conv_fprop_act: fused_table() "act ..." rows, test_hip_ops.py',
+    'virtual concat': 'segnb_conv_fprop_upcat: fused_table() "upcat ..." rows',
+}
 FPROP_SELECTORS = ['kernel:fprop_' + s for s in ('c8', 'thin', 'roll', 'rw', 'dma', 'deepk', 's1', 'sx', 'general')]
 WGRAD_SELECTORS = ['kernel:wgrad_' + s for s in ('roll', 'c8roll', 's1', 'sx', 'general')]
 
@@ -89,7 +117,10 @@ class census(object):
         return self
 
     def take(self):
-        return {k: v for k, v in nv.census_read().items() if k.startswith('kernel:')}
+        """the selectors counted since the last take; self.tiles: the table rows of fprop_dma.hip counted beside them"""
+        c = nv.census_read()
+        self.tiles = {k: v for k, v in c.items() if k.startswith('tile:')}
+        return {k: v for k, v in c.items() if k.startswith('kernel:')}
 
     def __exit__(self, *a):
         nv.call('segnb_tune', b'call_census', 0)
@@ -113,8 +144,9 @@ def _operands(rt, case, seed=0):
     return op, xv, dyv, Ho, Wo
 
 
-def run_case(case):
-    """-> {'names': [forward, data gradient, weight gradient census], 'y', 'dx', 'dW': SHA-256 of the output bytes}"""
+def run_case(case, tiles=None):
+    """-> {'names': [forward, data gradient, weight gradient census], 'y', 'dx', 'dW': SHA-256 of the output bytes}; tiles (a list)
+    receives the "tile:..." census of the forward and of the data gradient"""
     from segnb.engine import Runtime, View
     dtype, N, H, W, Ci, Co, k, stride, full = case[:9]
     knobs = case[9] if len(case) > 9 else {}
@@ -129,13 +161,16 @@ def run_case(case):
         with census() as c:
             op.fprop(xv, yv, stats)
             kf = c.take()
+            tf = c.tiles
             op.dgrad(dyv, dxv)
             kd = c.take()
+            if tiles is not None:
+                tiles += [tf, c.tiles]
             op.wgrad(xv, dyv, gw)
             kw = c.take()
     finally:
         for knob in knobs:
-            nv.call('segnb_tune', knob.encode(), 0)
+            nv.call('segnb_tune', knob.encode(), KNOB_DEFAULTS[knob])
     torch.cuda.synchronize()
     out = {'names': [kf, kd, kw], 'y': _sha(yv.dense()), 'dx': _sha(dxv.dense()), 'dW': _sha(gw)}
     if 'kernel:wgrad_general' in kw:

@@ -140,15 +140,39 @@ def test_whole_file_experiment_switches_are_gone():
 
 def test_ws_tile_grid_is_set_up_once():
     src = sources()
-    # the persistent blocks per channel tile and their clamp to the tile count
-    assert _count('fprop_dma.hip', 'segnb_knob_conv_cus() / ', src) == 1
+    dma, sel = src['fprop_dma.hip'], src['ws_select.h']
+    # the persistent blocks per channel tile -- the division of the CUs, in ws_select.h's ws_blocks -- and their clamp to the tile count
+    assert files_with(r'\bcus\s*/\s*ntl\b', src) == {'ws_select.h': 1}
+    assert files_with(r'segnb_knob_conv_cus\(\)\s*/', src).get('fprop_dma.hip') is None
+    assert len(re.findall(r'\bws_blocks\(cus, ntl\)', dma)) == 1
     assert _count('fprop_dma.hip', 'if (gm > a.IT) gm = a.IT;', src) == 1
-    assert len(re.findall(r'a\.HB\s*=', src['fprop_dma.hip'])) == 1 and len(re.findall(r'a\.WB\s*=', src['fprop_dma.hip'])) == 1
+    assert len(re.findall(r'a\.HB\s*=', dma)) == 1 and len(re.findall(r'a\.WB\s*=', dma)) == 1
     # ws_tile_div: defined once, called by the one grid helper
-    assert len(re.findall(r'\bws_tile_div\(a\)', src['fprop_dma.hip'])) == 1
-    # the mask / no statistics / timing / plain ladder: one launch of each instantiation form per configuration type
-    assert _count('fprop_dma.hip', 'hipLaunchKernelGGL((conv_fprop_ws_kernel<K, true>)', src) == 1
-    assert len(re.findall(r'hipLaunchKernelGGL\(\(conv_fprop_ws_kernel<CE?,', src['fprop_dma.hip'])) == 4      # split K (2), plane gather, phase forward
+    assert len(re.findall(r'\bws_tile_div\(a\)', dma)) == 1
+    # the mask / no statistics / timing / plain / split-K ladder: every instantiation form is named once (ws_form_kernel), taken
+    # into a row's kernel table from the forms ws_select.h lists, and launched from the one site that indexes that table
+    for form in ('<K, false>', '<K, false, false, false>', '<K, false, false, true, false, true>', '<K, false, true, false>', '<K, true>',
+                 '<K, false, false, true, true>', '<K, false, false, false, true>'):
+        assert _count('fprop_dma.hip', 'return conv_fprop_ws_kernel%s;' % form, src) == 1, form
+    host = dma[dma.index('int ksplit_workspace('):]
+    assert len(re.findall(r'conv_fprop_ws_kernel<', host)) == 7
+    assert len(re.findall(r'hipLaunchKernelGGL\(', dma)) == 1 and 'hipLaunchKernelGGL(kern, ' in dma
+    assert len(re.findall(r'segnb_opt_in_lds\(', dma)) == 1
+    # ... and in fprop_rw.hip: a row's three forms once, the opt-in and the launch both from that list
+    rw = src['fprop_rw.hip']
+    assert len(re.findall(r'conv_fprop_rw_kernel<', rw)) == 3 and len(re.findall(r'hipLaunchKernelGGL\(', rw)) == 1
+    assert len(re.findall(r'segnb_opt_in_lds\(', rw)) == 1
+    # the round arithmetic -- tiles over persistent blocks, rounded up -- occurs in ws_select.h only
+    assert files_with(r'\+\s*gm\s*-\s*1\)\s*/\s*gm', src) == {'ws_select.h': 1}
+    assert not re.search(r'\bit[01]\b', dma) and not re.search(r'\bit[01]\b', rw)
+    # one argument setup per file
+    assert len(re.findall(r'\.x_bytes\s*=', dma)) == 1 and len(re.findall(r'\.x_bytes\s*=', rw)) == 1
+    assert len(re.findall(r'\bWsArgs a\{\};', dma)) == 2 and len(re.findall(r'\bWsArgs a;', dma)) == 0       # (the two tries)
+    assert len(re.findall(r'\bFdArgs a\{\};', rw)) == 1 and len(re.findall(r'\bFdArgs a;', rw)) == 0
+    # the two closed switches are gone
+    assert files_with(r'fprop_mf16|FPROP_MF16|rw_store_waves', src) == {}
+    # ws_select.h is plain C++: no HIP, no knob, no allocation
+    assert not re.search(r'#include\s*[<"](hip|common|device)|segnb_knob_|\bnew\b|malloc|std::(vector|function|string)', sel)
 
 
 # ---- the host side of the kernel tries: window origin, descriptor extents, LDS opt-in, declined status --------

@@ -122,13 +122,15 @@ def test_launchers_decline_beyond_the_bound():
     """every launcher of conv_fprop_ws_kernel that walks a tile grid sets the pairs through ws_tile_div, which refuses a tile count
     (look-ahead included) beyond TILE_DIV_MAX; the kernel itself divides nowhere by the grid"""
     text = open(os.path.join(CSRC, 'fprop_dma.hip')).read()
-    # launch_ws, launch_ws14, launch_ws_upd, launch_ws_upf: the grid comes from ws_tile_grid, and a refusal declines the launch ...
-    assert len(re.findall(r'if \(!ws_tile_grid<C>\(a, [^;]*\)\) return SEGNB_LAUNCH_DECLINED;', text)) == 4
+    # launch_ws_row, the launcher of every table row: the grid comes from ws_tile_grid, and a refusal declines the launch ...
+    assert len(re.findall(r'if \(!ws_tile_grid<C>\(a, [^;]*\)\) return SEGNB_LAUNCH_DECLINED;', text)) == 1
+    assert len(re.findall(r'\bws_tile_grid<', text)) == 1 and len(re.findall(r'hipLaunchKernelGGL\(', text)) == 1
+    assert text.index('if (!ws_tile_grid<C>(') < text.index('hipLaunchKernelGGL(')
     assert len(re.findall(r'\ba\.GM\s*=\s*gm;', text)) == 1 and len(re.findall(r'\ba\.HB\s*=', text)) == 1
     # ... which is ws_tile_div's, for every form but the tall one (no tile grid: it walks virtual rows)
-    grid = text[text.index('bool ws_tile_grid(WsArgs& a, int ntl) {'):text.index('int ws_launch_form(')]
+    grid = text[text.index('bool ws_tile_grid(WsArgs& a, int ntl, int cus) {'):text.index('int launch_ws_row(')]
     assert 'return C::TALL || ws_tile_div(a);' in grid and grid.index('a.GM = gm;') < grid.index('ws_tile_div(a)')
     assert '2ll * a.GM > (long long)TILE_DIV_MAX) return false;' in text
-    kernel = text[text.index('void conv_fprop_ws_kernel('):text.index('int ksplit_factor(')]
+    kernel = text[text.index('void conv_fprop_ws_kernel('):text.index('int ksplit_workspace(')]
     for spelled in ('/ a.WB', '/ (a.HB', '% a.WB'):
         assert spelled not in kernel, spelled

@@ -30,8 +30,6 @@ def main():
     ap.add_argument('--cfg', type=int, default=None, help='segnb_tune fprop_dma_cfg')
     ap.add_argument('--dbg', type=int, default=None, help='segnb_tune fprop_dma_dbg (timing builds)')
     ap.add_argument('--rw', type=int, default=None, help='segnb_tune fprop_rw (0/1)')
-    ap.add_argument('--mf16', type=int, default=None, help='segnb_tune fprop_mf16 (0/1)')
-    ap.add_argument('--rwsw', type=int, default=None, help='segnb_tune rw_store_waves (2/4)')
     ap.add_argument('--nostats', type=int, default=None, help='segnb_tune fprop_nostats (0/1)')
     ap.add_argument('--roll', type=int, default=None, help='segnb_tune fprop_roll (0/1/2)')
     ap.add_argument('--wroll', type=int, default=None, help='segnb_tune wgrad_roll (0/1)')
@@ -53,10 +51,6 @@ def main():
         nv.call('segnb_tune', b'fprop_dma_dbg', args.dbg)
     if args.nostats is not None:
         nv.call('segnb_tune', b'fprop_nostats', args.nostats)
-    if args.rwsw is not None:
-        nv.call('segnb_tune', b'rw_store_waves', args.rwsw)
-    if args.mf16 is not None:
-        nv.call('segnb_tune', b'fprop_mf16', args.mf16)
     if args.rw is not None:
         nv.call('segnb_tune', b'fprop_rw', args.rw)
     if args.roll is not None:
